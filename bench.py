@@ -51,6 +51,7 @@ PEAK_F16_MFMA_TFLOPS = 2500.0  # same table: F16 / BF16 MFMA dense
 PEAK_HBM_GBS = 8000.0  # same guide: HBM3E ~8 TB/s
 PMC_FILE = "r6_pmc_bench.json"  # committed rocprofv3 --pmc passes over the default command (tools/profile.sh)
 STATS_FILE = "r6_rocprofv3_kernel_stats.csv"  # ... and its --kernel-trace --stats summary
+DUMP_BUDGET = 64 * 10 ** 6  # --dump-outputs: bytes written in all
 
 
 def kernel_source_digest():
@@ -238,6 +239,26 @@ def to_device(a):
 def device_sync():
     import torch
     torch.cuda.synchronize()
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET):
+    """--dump-outputs: each array as dirname/<name>.npy, float64 if it is float64 and float32 otherwise.  When the arrays
+    together exceed `budget` bytes, every array above 1 MiB is replaced by the same fixed, seeded sample of its flattened
+    elements (sorted indices), so that two builds run with the same arguments still compare element for element."""
+    arrays = {k: np.ascontiguousarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32)
+              for k, v in arrays.items()}
+    big = [k for k, a in arrays.items() if a.nbytes > 1 << 20]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        small = total - sum(arrays[k].nbytes for k in big)
+        frac = (budget - small) / float(total - small)
+        for k in big:
+            a = arrays[k].ravel()
+            idx = np.sort(np.random.default_rng(0).choice(a.size, int(a.size * frac), replace=False))
+            arrays[k] = a[idx]
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def run_mirrors(args, syn, capi, h_frames, K, fsd, dsd, code_mode):
@@ -550,7 +571,14 @@ def main(argv=None):
     ap.add_argument("--cpu-pairs", type=int, default=3,
                     help="pairs of the cpu_baseline leg (default 3: ~17 s on the GPU box's host cores; BASELINE.md section 4's protocol "
                          "is >= 20 pairs after 3 warm-up pairs: --cpu-pairs 20 takes ~2.5 min)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all): one GPU -- the last pair's relative pose, the composed "
+                         "pose, the fields of its track() result (track_*), flow / consistency / depth maps and keypoints; "
+                         "N GPUs -- the gathered relative poses and the composed trajectory (rank 0)")
     args = ap.parse_args(argv)
+    if args.dump_outputs and (args.surface != "fused" or args.sequences):
+        raise SystemExit("bench.py: --dump-outputs covers the fused pipeline's timed steps (not --surface mirrors / --sequences)")
     os.environ["DFVO_CONV_PRECISION"] = args.conv_precision  # read once by the library when the layers are packed
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -670,6 +698,7 @@ def main(argv=None):
 
     host_t = [0.0, 0.0]  # host seconds inside enqueue_nets / track (DFVO_BENCH_TRACE=1 prints them)
     t_track = []         # completion time of every track() of the last run (steady-state rate)
+    last = {}            # the last pair of the last run: its slot, track() result, relative and composed pose
 
     carry = [args.feature_carry == "on"]
 
@@ -745,6 +774,7 @@ def main(argv=None):
             rel_all[k] = rel
             status[k] = out.status
         p.sync()
+        last.update(slot=(n - 1) % SLOTS, out=out, rel=rel, pose=g)
         return rel_all, status
 
     class PingPong:  # the sequence A, B, A, B, ... as an indexable of device frames
@@ -763,6 +793,16 @@ def main(argv=None):
         if os.environ.get("DFVO_BENCH_TRACE"):
             sys.stderr.write("host ms/pair: enqueue_nets %.3f  track %.3f\n" % (host_t[0] * 1e3 / args.steps,
                                                                                 host_t[1] * 1e3 / args.steps))
+        if args.dump_outputs:  # outside the timed region; no pair has been fed since the last one
+            out, slot = last["out"], last["slot"]
+            fwd, bwd, diff, raw, dep = pipe.get_outputs(slot)
+            kp_ref, kp_cur, inl = pipe.get_keypoints(slot, cap=args.kp_bestn + 64)
+            arrays = {"pose_rel": last["rel"], "pose_composed": last["pose"], "flow_fwd": fwd, "flow_bwd": bwd,
+                      "flow_diff": diff, "depth_raw": raw, "depth": dep, "kp_ref": kp_ref, "kp_cur": kp_cur, "kp_inlier": inl}
+            for name, _ in capi.TrackOut._fields_:
+                v = getattr(out, name)
+                arrays["track_" + name] = np.array(v[:] if hasattr(v, "_length_") else [v], np.float64)
+            dump_outputs(args.dump_outputs, arrays)
         gathered = dmod.allgather_poses(rel_all, status, 1, 0)
         n_total = args.steps
     else:
@@ -782,6 +822,8 @@ def main(argv=None):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
         status = gathered[:, 16].astype(np.int64)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"poses_gathered": gathered, "trajectory": np.asarray(traj, np.float64)})
         if rank == 0 and on_gpu:  # outside the timed region: the same sequence tracked by this rank alone
             rel1, st1 = smod.track_chunk(pipe, frames, 0, n_total, rng_mode="per_pair", carry_features=carry[0])
             same = bool(np.array_equal(rel1.reshape(n_total, 16)[st1 != 1], gathered[:, :16][st1 != 1]) and np.array_equal(st1, status))

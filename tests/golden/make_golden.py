@@ -829,6 +829,39 @@ def golden_dfvo_main(n_frames=5, h=256, w=640):
                         n_frames=n_frames, h=h, w=w, seq_seed=31, traj_txt=np.array(traj))
 
 
+def golden_surface():
+    """reference_surface.json: for every reference class whose interface the mirrors reproduce
+    (tests/test_surface_cpu.py PAIRS), its public methods -- kind ('method' / 'property') and positional parameter names
+    after self -- read from the reference's source with ast"""
+    import ast
+    import json
+    from test_surface_cpu import PAIRS
+    out = {}
+    for path, classes, _, _ in PAIRS:
+        tree = ast.parse(open(os.path.join(REF, path)).read())
+        for cls in classes:
+            node = [n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == cls][0]
+            meths = {}
+            for m in node.body:
+                if isinstance(m, ast.FunctionDef) and not m.name.startswith("_"):
+                    is_prop = any(isinstance(d, ast.Name) and d.id == "property" or isinstance(d, ast.Attribute) and d.attr == "setter"
+                                  for d in m.decorator_list)
+                    meths.setdefault(m.name, ["property" if is_prop else "method", [a.arg for a in m.args.args][1:]])
+            out.setdefault(path, {})[cls] = meths
+    with open(os.path.join(HERE, "reference_surface.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+def golden_camera_modules():
+    """camera_modules.npz: every value tests/test_camera_modules_cpu.py's script observes on the reference's own SE3 /
+    Intrinsics (libs/geometry/camera_modules.py)"""
+    from test_camera_modules_cpu import script
+    ref = load_by_path("ref_camera_modules", os.path.join(REF, "libs/geometry/camera_modules.py"))
+    vals = script(ref)
+    np.savez_compressed(os.path.join(HERE, "camera_modules.npz"), **{"v%d" % i: np.asarray(v) for i, v in enumerate(vals)})
+
+
 if __name__ == "__main__":
     apply_compat()
     torch.set_num_threads(8)
@@ -837,7 +870,8 @@ if __name__ == "__main__":
             "gric": golden_gric, "tracker": golden_tracker, "lanczos": golden_lanczos, "sampled": golden_kp_sampled,
             "tracker_flow": golden_tracker_flow, "rigid": golden_rigid_flow, "bestn": golden_kp_bestn,
             "kitti_eval": golden_kitti_eval, "kitti_eval_align": golden_kitti_eval_align, "dfvo_main": golden_dfvo_main,
-            "target_size": golden_target_size, "tracker_variants": golden_tracker_variants, "pnp_tracker": golden_pnp_tracker}
+            "target_size": golden_target_size, "tracker_variants": golden_tracker_variants, "pnp_tracker": golden_pnp_tracker,
+            "surface": golden_surface, "camera_modules": golden_camera_modules}
     for name, fn in todo.items():
         if not which or name in which:
             print("==", name)

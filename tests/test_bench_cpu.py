@@ -110,6 +110,54 @@ def test_bench_two_ranks_gloo():
     assert abs(line["value"] - 2 * 5 / (line["ms_per_step"] * 5e-3)) < 1e-2 * line["value"]  # whole-job aggregate
 
 
+def test_bench_two_ranks_dump_outputs(tmp_path):
+    """--dump-outputs under two ranks: rank 0 writes the gathered relative poses and the composed trajectory of the timed
+    sequence, float64"""
+    world = 2
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker, args=(r, world, port, q, ("--dump-outputs", str(tmp_path))))
+             for r in range(world)]
+    for p in procs:
+        p.start()
+    outs = dict(q.get(timeout=120) for _ in range(world))
+    for p in procs:
+        p.join(60)
+        assert p.exitcode == 0
+    line = json.loads(outs[0].strip().splitlines()[-1])
+    assert line["steps"] == 5 and line["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path)) == ["poses_gathered.npy", "trajectory.npy"]
+    g, traj = np.load(tmp_path / "poses_gathered.npy"), np.load(tmp_path / "trajectory.npy")
+    assert g.dtype == traj.dtype == np.float64 and g.shape == (10, 17) and traj.shape == (11, 4, 4)
+    assert np.array_equal(traj[0], np.eye(4)) and not np.array_equal(traj[-1], np.eye(4))
+
+
+def test_dump_outputs_budget_and_sample(tmp_path):
+    """bench.dump_outputs: float32 / float64 only; under the budget every array as it is; over it the arrays above 1 MiB
+    become the same seeded sample of their elements, the small ones stay whole, and the files fit the budget"""
+    import bench
+    rng = np.random.default_rng(1)
+    arrays = {"pose": rng.random((4, 4)), "mask": rng.random(300) > 0.5, "count": np.arange(5, dtype=np.int32),
+              "flow": rng.random((2, 376, 1241)).astype(np.float32), "depth": rng.random((376, 1241))}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "all" / (k + ".npy"))
+        assert got.dtype == (np.float64 if v.dtype == np.float64 else np.float32) and np.array_equal(got, v), k
+    budget = 4 << 20
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, budget=budget)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(k + ".npy" for k in arrays)
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in files) <= budget
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert np.array_equal(a, b), f
+    assert np.array_equal(np.load(tmp_path / "a" / "pose.npy"), arrays["pose"])
+    flow = np.load(tmp_path / "a" / "flow.npy")
+    assert flow.ndim == 1 and 0 < flow.size < arrays["flow"].size and np.isin(flow, arrays["flow"]).all()
+
+
 def test_bench_sequences_mode_two_ranks_gloo():
     """bench.py --sequences kitti-lengths (BASELINE config 3) under gloo: eleven sequences as one job over two ranks"""
     world = 2
@@ -140,6 +188,8 @@ def test_bench_gpus_flag_self_launch(monkeypatch):
     monkeypatch.setattr(subprocess, "call", lambda cmd: seen.setdefault("cmd", cmd) and 0)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "3"])
     monkeypatch.delenv("WORLD_SIZE", raising=False)
+    # bench.main exports the precision for the library; restored afterwards, or it would override later tests' own choice
+    monkeypatch.setenv("DFVO_CONV_PRECISION", os.environ.get("DFVO_CONV_PRECISION", "f16x3"))
     try:
         bench.main(["--gpus", "8", "--steps", "3"])
     except SystemExit as e:

@@ -496,16 +496,7 @@ def test_timer_sub_keys_are_fed_from_device_stage_times(gpu):
     ks_mod = importlib.import_module("df-vo_amd.libs.matching.keypoint_sampler")
     trk_mod = importlib.import_module("df-vo_amd.libs.tracker")
     cam = cam_mod.Intrinsics([K[0, 2], K[1, 2], K[0, 0], K[1, 1]])
-    ref_timer = "/root/reference/libs/general/timer.py"
-    import os
-    if os.path.exists(ref_timer):  # build container with a GPU: the reference's own class
-        from importlib import util as ilu
-        spec = ilu.spec_from_file_location("ref_timer", ref_timer)
-        mod = ilu.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        timers = mod.Timer()
-    else:
-        timers = _RefTimer()
+    timers = _RefTimer()
     np.random.seed(4869)
     trk = trk_mod.EssTracker(cfg, cam, timers)
     frames = [fr, rigid_scene(h, w, seed=301, bad_frac=0.4)]

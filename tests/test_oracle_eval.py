@@ -1,8 +1,6 @@
-"""CPU: oracle/kitti_eval.py (restatement of the reference's trajectory metrics) against the fixture produced by the
-reference's own KittiEvalOdom methods (tests/golden/make_golden.py -> kitti_eval.npz), and -- when /root/reference is
-present (build container) -- against the reference code live."""
+"""CPU: oracle/kitti_eval.py (restatement of the reference's trajectory metrics) against the fixtures produced by the
+reference's own KittiEvalOdom methods (tests/golden/make_golden.py -> kitti_eval.npz, kitti_eval_align.npz)."""
 import os
-import sys
 import types
 
 import numpy as np
@@ -27,19 +25,6 @@ def test_kitti_eval_matches_reference_fixture():
     _check(np.load(GOLD))
 
 
-def test_kitti_eval_matches_reference_live():
-    ref = "/root/reference/tools/evaluation/odometry/kitti_odometry.py"
-    if not os.path.exists(ref):
-        import pytest
-        pytest.skip("reference not present (GPU box): the committed fixture pins the restatement")
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
-    import make_golden as G
-    fx = np.load(GOLD)
-    live = G.kitti_eval_reference(list(fx["gt"]), list(fx["res"]))
-    for k in ("t_rel", "r_rel", "ate", "rpe_t", "rpe_r"):
-        assert abs(live[k] - float(fx[k])) <= 1e-12
-
-
 ALIGN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kitti_eval_align.npz")
 MODES = [None, "scale", "scale_7dof", "7dof", "6dof"]
 CASES = ["tunnel", "drive", "drive_short"]
@@ -61,14 +46,3 @@ def test_alignment_modes_match_reference_eval_fixture():
     a = fx["drive_None"]
     assert abs(fx["drive_scale"][0] - a[0]) > 0.1 and abs(fx["drive_7dof"][2] - a[2]) > 1.0 and abs(fx["drive_6dof"][2] - a[2]) > 1.0
 
-
-def test_alignment_matches_reference_live():
-    if not os.path.exists("/root/reference/tools/evaluation/odometry/kitti_odometry.py"):
-        import pytest
-        pytest.skip("reference not present (GPU box): the committed fixture pins the restatement")
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
-    import make_golden as G
-    fx = np.load(ALIGN)
-    live = G.kitti_eval_reference_eval(fx["drive_short_gt"], fx["drive_short_res"], "6dof")
-    for k, w in zip(("t_rel", "r_rel", "ate", "rpe_t", "rpe_r"), fx["drive_short_6dof"]):
-        assert abs(live[k] - float(w)) <= 1e-12

@@ -138,92 +138,3 @@ def test_lanczos_restatement_equals_the_older_pillow(probe):
     for i in range(int(inp["pil_n"])):
         w, h = (int(v) for v in inp["pil_size"][i])
         assert np.array_equal(resize_lanczos_u8(inp["pil_img%d" % i], w, h), out["pil%d" % i]), i
-
-
-def test_reference_kp_selection_under_numpy_1x_reproduces_the_fixture(tmp_path):
-    """the reference's unmodified libs/matching/kp_selection.py executed by the second environment's numpy 1.x (its native
-    scalar np.argpartition -- the reference pin's algorithm, no CPU-feature switch) gives the committed fixture
-    tests/golden/local_bestN.npz, which make_golden.py wrote under numpy 2.x with the SIMD selection kernels disabled and
-    which the oracle restatement and the device reproduce: keypoint values AND order, local_bestN with both score methods"""
-    py, vers = _second_python()
-    ref = "/root/reference"
-    if py is None or not os.path.isdir(ref):
-        pytest.skip("needs the second python environment and /root/reference (build container only)")
-    if int(vers[0].split(".")[0]) >= 2:
-        pytest.skip("the second environment's numpy is 2.x too")
-    gold = os.path.join(HERE, "golden", "local_bestN.npz")
-    dst = str(tmp_path / "kp.npz")
-    r = subprocess.run([py, "-W", "ignore", os.path.join(HERE, "second_env_ref_kp.py"), ref, gold, dst], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    g, o = np.load(gold), np.load(dst)
-    n = 0
-    for tag in ("a", "b", "c", "d", "ra", "rb", "rc"):
-        assert bool(g[tag + "_good"]) == bool(o[tag + "_good"]), tag
-        if bool(g[tag + "_good"]):
-            assert np.array_equal(g[tag + "_kp1"], o[tag + "_kp1"]) and np.array_equal(g[tag + "_kp2"], o[tag + "_kp2"]), tag
-            n += 1
-    assert n >= 5
-    gb = np.load(os.path.join(HERE, "golden", "bestN.npz"))  # bestN_flow_kp: one argpartition over the whole map
-    for tag in "abcd":
-        assert np.array_equal(gb[tag + "_kp1"], o["bestN_" + tag + "_kp1"]) and np.array_equal(gb[tag + "_kp2"], o["bestN_" + tag + "_kp2"]), tag
-    gg = np.load(os.path.join(HERE, "golden", "gric.npz"))  # the reference's gric.py under numpy 1.x: residuals and both scores
-    # the two GRIC scores bit for bit; the 500 epipolar residuals to a few ulp: they come out of BLAS matmuls, whose summation
-    # order follows the kernel OpenBLAS dispatches for the HOST CPU (this container has run on hosts where all 500 were equal
-    # and on a Xeon where 158 differ by <= 7e-15 relative -- with both scores still equal)
-    assert np.allclose(np.asarray(gg["f_res"]), np.asarray(o["f_res"]), rtol=1e-12, atol=0.0)
-    for k in ("f_gric", "h_gric"):
-        assert np.array_equal(np.asarray(gg[k]), np.asarray(o[k])), k
-    # (the homography residual goes through np.linalg.inv and 3x3 matmuls: the two environments' BLAS / LAPACK builds differ
-    # in the last bit on a quarter of the points -- 7e-15 absolute; the GRIC score above comes out identical)
-    assert np.abs(gg["h_res"] - o["h_res"]).max() <= 1e-12 * np.abs(gg["h_res"]).max()
-
-
-def test_reference_e_tracker_under_the_older_libraries_reproduces_the_fixture(tmp_path):
-    """the reference's unmodified libs/tracker/E_tracker.py -- compute_pose_2d2d (shuffles, 5 x findEssentialMat over the
-    oracle's cv2, GRIC, recoverPose) and scale_recovery (triangulation + `RANSACRegressor(base_estimator=...)`, native to this
-    scikit-learn: no adapter) -- executed by the second environment (numpy 1.x RandomState / argpartition, scikit-learn 0.24)
-    gives tests/golden/e_tracker.npz, written under numpy 2.x / scikit-learn 1.7: poses, inlier masks and the RandomState
-    after each case identical, scale to 1e-12 (lstsq of two LAPACK builds)"""
-    py, vers = _second_python()
-    ref = "/root/reference"
-    if py is None or not os.path.isdir(ref):
-        pytest.skip("needs the second python environment and /root/reference (build container only)")
-    from oracle import cv2_shim
-    cv2_shim.lib()  # the C oracle the shim loads is built by the test interpreter
-    dst = str(tmp_path / "trk.npz")
-    r = subprocess.run([py, "-W", "ignore", os.path.join(HERE, "second_env_ref_tracker.py"), ref, os.path.dirname(HERE), dst],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    g, o = np.load(os.path.join(HERE, "golden", "e_tracker.npz")), np.load(dst)
-    print("second environment: numpy %s scikit-learn %s" % tuple(o["versions"]))
-    # Inlier masks and RandomState bit for bit.  Poses and scales to 1e-9: they pass through the second environment's BLAS / LAPACK
-    # (np.linalg.inv / svd / lstsq, matmuls), whose kernels are picked per HOST CPU -- on the hosts of rounds 3-5 every pose was
-    # bit-equal, on a round-6 Xeon they differ by up to 3e-12 (poses) / 2e-11 (scales) with masks and RandomState still equal
-    # (round 6: tests/test_oracle_second_env.py was the one CPU test that depended on the machine under the container).
-    TOL = 1e-9
-    for tag in "abcd":
-        assert np.abs(g[tag + "_pose"] - o[tag + "_pose"]).max() <= TOL, tag
-        assert np.array_equal(g[tag + "_inliers"], o[tag + "_inliers"]), tag
-        assert np.array_equal(g[tag + "_rng_after"], o[tag + "_rng_after"]), tag
-        assert abs(float(g[tag + "_scale"]) - float(o[tag + "_scale"])) <= TOL * abs(float(g[tag + "_scale"])), tag
-    gf = np.load(os.path.join(HERE, "golden", "e_tracker_flow.npz"))  # validity.method 'flow' (mean-displacement gate)
-    for tag in "abcd":
-        assert np.abs(gf[tag + "_pose"] - o["flow_" + tag + "_pose"]).max() <= TOL, tag
-        for k in ("_inliers", "_rng_after"):
-            assert np.array_equal(gf[tag + k], o["flow_" + tag + k]), (tag, k)
-    gv = np.load(os.path.join(HERE, "golden", "e_tracker_variants.npz"))  # homo_ratio validity + abs_diff scale RANSAC
-    for tag in "abpd":
-        assert np.abs(gv[tag + "_pose"] - o["var_" + tag + "_pose"]).max() <= TOL, tag
-        for k in ("_inliers", "_rng_after"):
-            assert np.array_equal(gv[tag + k], o["var_" + tag + k]), (tag, k)
-        a, b = float(gv[tag + "_scale"]), float(o["var_" + tag + "_scale"])
-        assert abs(a - b) <= TOL * max(1.0, abs(a)), (tag, a, b)
-    gs = np.load(os.path.join(HERE, "golden", "sampled_kp.npz"))  # KeypointSampler.generate_kp_samples + sampled_kp
-    for tag in "abc":
-        for k in ("_idx", "_kp1", "_kp2"):
-            assert np.array_equal(gs[tag + k], o["smp_" + tag + k]), (tag, k)
-    gp = np.load(os.path.join(HERE, "golden", "pnp_tracker.npz"))  # the reference's PnpTracker under the same environment
-    for tag in "abcde":
-        assert np.array_equal(gp[tag + "_kp1"], o["pnp_" + tag + "_kp1"]), tag
-        assert np.array_equal(gp[tag + "_rng_after"], o["pnp_" + tag + "_rng_after"]), tag
-        assert np.abs(gp[tag + "_pose"] - o["pnp_" + tag + "_pose"]).max() <= 1e-12, tag  # (np.linalg.inv of the final inversion: two LAPACKs)

@@ -14,7 +14,7 @@ G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SIMD_OFF = "AVX512F AVX512CD AVX512_SKX AVX512_CLX AVX512_CNL AVX512_ICL AVX512_SPR AVX2 FMA3"
 
 
-def test_argpartition_restatements_match_scalar_numpy():
+def test_argpartition_restatements_match_scalar_numpy(tmp_path):
     """pure-python and C restatements vs numpy itself with its SIMD sort dispatch disabled"""
     code = r"""
 import numpy as np, sys
@@ -27,7 +27,7 @@ for trial in range(60):
     out.append(np.argpartition(v, k - 1)[:k])
 np.save(sys.argv[1], np.concatenate(out))
 """
-    path = "/tmp/_np_scalar_order.npy"
+    path = str(tmp_path / "np_scalar_order.npy")
     env = dict(os.environ, NPY_DISABLE_CPU_FEATURES=SIMD_OFF)
     subprocess.check_call([sys.executable, "-c", code, path], env=env)
     want = np.load(path)

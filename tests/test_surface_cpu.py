@@ -1,15 +1,16 @@
-"""CPU (build container: needs /root/reference): the drop-in boundary as a class surface.  For every class the
-overlay substitutes, each public method of the reference's class -- and of the base class it inherits its interface from --
-must exist on the mirror under the same name with the same positional parameters.  Training-only methods are listed
-explicitly: they must exist nowhere or raise NotImplementedError; nothing is silently absent."""
-import ast
+"""CPU: the drop-in boundary as a class surface.  For every class the overlay substitutes, each public method
+of the reference's class -- and of the base class it inherits its interface from -- must exist on the mirror under the same
+name with the same positional parameters.  The reference's surface is the committed fixture tests/golden/reference_surface.json
+(tests/golden/make_golden.py reads it from the reference's source).  Training-only methods are listed explicitly: they must
+exist nowhere or raise NotImplementedError; nothing is silently absent."""
 import importlib
 import inspect
+import json
 import os
 
 import pytest
 
-REF = "/root/reference"
+SURFACE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_surface.json")
 PAIRS = [  # (reference file, reference classes whose methods form the interface, mirror module, mirror class)
     ("libs/deep_models/deep_models.py", ["DeepModel"], "df-vo_amd.libs.deep_models.deep_models", "DeepModel"),
     ("libs/deep_models/flow/lite_flow_net/lite_flow.py", ["LiteFlow"], "df-vo_amd.libs.deep_models.flow.lite_flow_net.lite_flow", "LiteFlow"),
@@ -27,23 +28,12 @@ TRAINING_INTERNALS = {"train", "generate_images_pred_flow", "compute_flow_losses
 
 
 def _ref_methods(path, cls):
-    tree = ast.parse(open(os.path.join(REF, path)).read())
-    for n in tree.body:
-        if isinstance(n, ast.ClassDef) and n.name == cls:
-            out = {}
-            for m in n.body:
-                if isinstance(m, ast.FunctionDef) and not m.name.startswith("_"):
-                    is_prop = any(isinstance(d, ast.Name) and d.id == "property" or isinstance(d, ast.Attribute) and d.attr == "setter"
-                                  for d in m.decorator_list)
-                    out.setdefault(m.name, ("property" if is_prop else "method", [a.arg for a in m.args.args][1:]))
-            return out
-    raise AssertionError("class %s not found in %s" % (cls, path))
+    with open(SURFACE) as f:
+        return {name: (kind, params) for name, (kind, params) in json.load(f)[path][cls].items()}
 
 
 @pytest.mark.parametrize("ref_file,ref_classes,mod,mirror_cls", PAIRS, ids=[p[0].split("/")[-1] + ":" + "+".join(p[1]) for p in PAIRS])
 def test_mirror_has_the_reference_surface(ref_file, ref_classes, mod, mirror_cls):
-    if not os.path.isdir(REF):
-        pytest.skip("/root/reference is only present in the build container")
     m = importlib.import_module(mod)
     checked = 0
     for rc in ref_classes:
