@@ -137,6 +137,7 @@ SIGNATURES = {
     "dfvo_correlation": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "dfvo_backward_warp": (_i, [_vp, _vp, _f, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "dfvo_deconv_dw4x4s2": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "dfvo_maxpool3x3s2": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "dfvo_lanczos_coeffs": (_i, [_i, _i, _vp, _vp, _i, _ip]),
     "dfvo_resize_lanczos_u8": (_i, [_vp, _i, _i, _vp, _i, _i, _vp]),
     "dfvo_resize_linear_u8": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp]),
@@ -246,8 +247,11 @@ def check(rc):
 
 def check_f16_range(seen, what):
     """plain (non-session) net calls under an f16x3 / f16 packing: raise when the call drove an activation beyond +-65504
-    (its output then holds inf / NaN).  `seen`: the counter before the call; returns the counter now."""
+    (its output then holds inf / NaN).  `seen`: the counter right before the call; returns the counter now.  A counter
+    below `seen` was reset during the call: everything it holds is then counted as the call's."""
     now = f16s_overflow_count()
+    if now < seen:
+        seen = 0
     if now > seen:
         raise DfvoError("f16 split out of range: %d activation group(s) beyond +-65504 in %s -- its output holds inf / NaN; pack "
                         "the nets in exact fp32 (DFVO_CONV_PRECISION=fp32 or dfvo_hip.conv_precision: fp32)" % (now - seen, what))

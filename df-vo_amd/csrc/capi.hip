@@ -203,6 +203,15 @@ int dfvo_backward_warp(const float* d_src, const float* d_flow, float mult, int 
     return DFVO_OK;
 }
 
+int dfvo_maxpool3x3s2(const float* d_src, int N, int H, int W, int C, float* d_dst, void* stream) {
+    DFVO_ARG_CHECK(d_src && d_dst && N > 0 && H > 0 && W > 0 && C > 0, "dfvo_maxpool3x3s2: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = launch_maxpool3x3s2(d_src, N, H, W, C, d_dst, s);
+    if (rc != DFVO_OK) return rc;
+    DFVO_HIP_CHECK(hipStreamSynchronize(s));
+    return DFVO_OK;
+}
+
 int dfvo_deconv_dw4x4s2(const float* d_src, int N, int H, int W, int C, int cs, const float* h_weight, float* d_dst,
                         void* stream) {
     DFVO_ARG_CHECK(d_src && h_weight && d_dst && cs >= C, "dfvo_deconv_dw4x4s2: bad argument");

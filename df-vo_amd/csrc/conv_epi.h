@@ -8,7 +8,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float apply_act(float v, int act, float a) {
     switch (act) {
         case ACT_LEAKY: return v > 0.f ? v : v * a;
-        case ACT_RELU: return v > 0.f ? v : 0.f;
+        case ACT_RELU: return (v > 0.f || v != v) ? v : 0.f;  // NaN propagates, as in torch.relu
         case ACT_ELU: return v > 0.f ? v : a * expm1f(v);
         case ACT_SIGMOID: return 1.f / (1.f + expf(-v));
         default: return v;
@@ -65,7 +65,7 @@ template <int NQ>
 struct ConvEpi {
     f32x4 b[NQ];
     int col0[NQ];
-    float slope;  // LeakyReLU a / none 1 as one formula: v > 0 ? v : v * slope; ReLU selects +0 (as apply_act does)
+    float slope;  // LeakyReLU a / none 1 as one formula: v > 0 ? v : v * slope; ReLU selects +0 (as apply_act does; NaN passes)
     bool relu;
     bool fast;    // every quad of every lane of the wave takes the vector path
 };
@@ -103,7 +103,7 @@ __device__ __forceinline__ void conv_epi_row_act(const ConvParams& p, const Conv
             f32x4 x = get(q0 + q) + c.b[q0 + q];
             if (p.res) x += r[q];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) x[e] = ELU ? (x[e] > 0.f ? x[e] : p.act_param * expm1f(x[e])) : (x[e] > 0.f ? x[e] : (c.relu ? 0.f : x[e] * c.slope));
+            for (int e = 0; e < 4; ++e) x[e] = ELU ? (x[e] > 0.f ? x[e] : p.act_param * expm1f(x[e])) : ((x[e] > 0.f || x[e] != x[e]) ? x[e] : (c.relu ? 0.f : x[e] * c.slope));
             *reinterpret_cast<f32x4*>(d + c.col0[q0 + q]) = x;
         }
     }

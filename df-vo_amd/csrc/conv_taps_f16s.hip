@@ -206,7 +206,7 @@ __global__ __launch_bounds__(64 * TH) void conv_taps_f16s_kernel(const ConvParam
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float v = am[q >> 2][4 * (q & 3) + e] + F16S_LO_UNSCALE * ax[q >> 2][4 * (q & 3) + e] + bq[q][e];
-            x[e] = v > 0.f ? v : (p.act == ACT_RELU ? 0.f : v * slope);
+            x[e] = (v > 0.f || v != v) ? v : (p.act == ACT_RELU ? 0.f : v * slope);  // (NaN passes ReLU, as in torch)
         }
         if (col0 + 3 < p.cout) {
             *reinterpret_cast<f32x4*>(drow + col0) = x;

@@ -832,7 +832,9 @@ __global__ void k_maxpool3x3s2(const float* __restrict__ src, int N, int H, int 
             const int ix = ox * 2 - 1 + kx;
             if (ix < 0 || ix >= W) continue;
             const f32x4 v = reinterpret_cast<const f32x4*>(src)[((size_t)(n * H + iy) * W + ix) * C4 + c];
-            m[0] = fmaxf(m[0], v[0]); m[1] = fmaxf(m[1], v[1]); m[2] = fmaxf(m[2], v[2]); m[3] = fmaxf(m[3], v[3]);
+            // max_pool2d's rule (NaN propagates; fmaxf would drop it)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) m[e] = (v[e] > m[e] || v[e] != v[e]) ? v[e] : m[e];
         }
     }
     reinterpret_cast<f32x4*>(dst)[idx] = m;

@@ -58,6 +58,7 @@ struct dfvo_session {
     unsigned* h_ovf[RING] = {};   // [0] f16x3 range counter behind the flow net of the generation, [1] behind its depth net
     unsigned* d_ovf = nullptr;    // the device counter (conv_f16s_overflow_counter)
     unsigned ovf_seen[2] = {0, 0};  // its value up to which each of the two readers (flow stream, depth stream) has reported
+    bool ovf_bad[RING][2] = {};     // the generation of the slot was reported out of range to that reader: every later read is too
     float* h_depth[RING] = {};
     float *h_fwd[RING] = {}, *h_bwd[RING] = {}, *h_diff[RING] = {};
     double *h_kp_ref[RING] = {}, *h_kp_cur[RING] = {};
@@ -263,6 +264,7 @@ int dfvo_session_push_frame(dfvo_session* s, const uint8_t* h_img, const dfvo_se
     DFVO_HIP_CHECK(hipEventRecord(s->e_img, s->s_copy));
     if (s->trace) DFVO_HIP_CHECK(hipEventRecord(s->t_img, s->s_copy));
     s->have_flow = s->have_kp = s->have_h = s->have_e = false;
+    s->ovf_bad[slot][0] = s->ovf_bad[slot][1] = false;
     // ---- flow net of (g - 1, g)
     auto enqueue_flow = [&]() -> int {
         if (g >= 1 && want_flow) {
@@ -349,15 +351,23 @@ int dfvo_session_push_frame(dfvo_session* s, const uint8_t* h_img, const dfvo_se
 // The device counter of such events rides behind each net's output copy; a net that raised it fails its call here instead of
 // handing out inf / NaN silently (the exact-fp32 packing never counts).  The counter is process-wide: the two nets of a push run
 // side by side, so an event in either fails whichever of forward_depth / forward_flow reads the counter after it -- possibly
-// both; each reader keeps its own high-water mark (its reads are ordered on its stream).
-static int range_check(dfvo_session* s, int reader, unsigned now, const char* which) {
+// both; each reader keeps its own high-water mark (its reads are ordered on its stream).  A generation found out of range stays
+// so: a second read of its depth / flow fails again (the flag lives with the ring slot and is cleared by the push that reuses it).
+static int range_check(dfvo_session* s, int reader, int slot, const char* which) {
+    const unsigned now = s->h_ovf[slot][reader];
     unsigned& seen = s->ovf_seen[reader];
     if (now < seen) seen = 0;  // (someone reset the counter: dfvo_f16s_overflow_count(.., 1))
-    if (now == seen) return DFVO_OK;
+    if (now == seen && !s->ovf_bad[slot][reader]) return DFVO_OK;
     const unsigned n = now - seen;
     seen = now;
-    dfvo::set_last_error(std::string("f16 split out of range: ") + std::to_string(n) + " activation group(s) beyond +-65504 up to the " +
-                         which + " net of this frame -- its output holds inf / NaN; pack the nets in exact fp32 "
+    if (n > 0) {
+        s->ovf_bad[slot][reader] = true;
+        // (the flow net's pyramids of this frame may hold inf / NaN -- and a NaN is not counted when the next pair splits
+        // it again: the next pair runs both frames through Features instead of carrying them over)
+        s->carry_ok = false;
+    }
+    dfvo::set_last_error(std::string("f16 split out of range: ") + (n > 0 ? std::to_string(n) + " activation group(s)" : std::string("activations")) +
+                         " beyond +-65504 up to the " + which + " net of this frame -- its output holds inf / NaN; pack the nets in exact fp32 "
                          "(DFVO_CONV_PRECISION=fp32 or dfvo_hip.conv_precision: fp32)");
     return DFVO_ERR_RANGE;
 }
@@ -367,7 +377,7 @@ int dfvo_session_depth(dfvo_session* s, long long generation, const float** h_de
     DFVO_ARG_CHECK(generation == s->gen && s->gen >= 0, "dfvo_session_depth: not the newest pushed frame");
     DFVO_HIP_CHECK(hipEventSynchronize(s->e_depth));
     *h_depth = s->h_depth[s->gen % RING];
-    return range_check(s, 1, s->h_ovf[s->gen % RING][1], "depth");
+    return range_check(s, 1, (int)(s->gen % RING), "depth");
 }
 
 // the session's pinned copy of frame `generation` (the newest or the one before): uint8 [img_h, img_w, 3]
@@ -430,7 +440,7 @@ int dfvo_session_flow(dfvo_session* s, long long generation, const float** h_fwd
     *h_fwd = s->h_fwd[slot];
     *h_bwd = s->h_bwd[slot];
     *h_diff = s->h_diff[slot];
-    return range_check(s, 0, s->h_ovf[slot][0], "flow");
+    return range_check(s, 0, slot, "flow");
 }
 
 int dfvo_session_keypoints(dfvo_session* s, long long generation, const dfvo_session_kp_cfg* kp, const double** h_kp_ref,

@@ -62,7 +62,7 @@ class DeepModel:
             capi.check(lib.dfvo_set_conv_precision(before))
         if self.conv_precision != "fp32":
             # weights beyond f16's range are clamped (and counted) by the packer: refuse them here, loudly
-            self._f16_seen = capi.check_f16_range(seen, "the packed weights")
+            capi.check_f16_range(seen, "the packed weights")
         if self.cfg.deep_pose.enable:
             raise NotImplementedError("deep_pose is 'Experiment Ver. only' in the reference; out of scope")
         if opts["session"] and getattr(self, "depth", None) is not None and isinstance(self.flow, LiteFlow):
@@ -104,9 +104,8 @@ class DeepModel:
         else:
             if s is not None:
                 s.stats["flow_plain"] += 1
-            fwd, bwd, diff = self.flow.inference_flow_u8(np.ascontiguousarray(in_ref_data['img']),
-                                                         np.ascontiguousarray(in_cur_data['img']))
-            self._check_range("the flow net")
+            fwd, bwd, diff = self._in_range("the flow net", self.flow.inference_flow_u8,
+                                             np.ascontiguousarray(in_ref_data['img']), np.ascontiguousarray(in_cur_data['img']))
         src_id, tgt_id = in_ref_data['id'], in_cur_data['id']
         flows = {(src_id, tgt_id): fwd}
         if forward_backward:
@@ -120,15 +119,19 @@ class DeepModel:
         flow net of (previous frame, this frame) and the keypoint / homography stage behind it are enqueued here as well."""
         if self.session is not None and self.session.accepts(imgs[0]):
             return self.session.push(imgs[0])
-        depth = self.depth.inference_depth_image_u8(np.ascontiguousarray(imgs[0]))
-        self._check_range("the depth net")
-        return depth
+        return self._in_range("the depth net", self.depth.inference_depth_image_u8, np.ascontiguousarray(imgs[0]))
 
-    def _check_range(self, what):
+    def _in_range(self, what, net_call, *args):
         """plain entry points under an f16x3 / f16 packing: fail instead of handing out inf / NaN (the session does the same
-        from the counter it reads behind each net, libs/deep_models/session.py)"""
-        if self.conv_precision != "fp32":
-            self._f16_seen = capi.check_f16_range(getattr(self, "_f16_seen", 0), what)
+        from the counter it reads behind each net, libs/deep_models/session.py).  The process-wide counter is read right before
+        and right after the blocking call, so only events of THIS call count: an earlier overflow (here or in another model),
+        one the session reported, or a reset of the counter by anybody does not fail a later in-range call."""
+        if self.conv_precision == "fp32":
+            return net_call(*args)
+        before = capi.f16s_overflow_count()
+        out = net_call(*args)
+        capi.check_f16_range(before, what)
+        return out
 
     def initialize_deep_pose_model(self):
         raise NotImplementedError("deep_pose is 'Experiment Ver. only' in the reference; out of scope")

@@ -118,6 +118,10 @@ int dfvo_backward_warp(const float* d_src, const float* d_flow, float flow_mult,
 int dfvo_deconv_dw4x4s2(const float* d_src, int N, int H, int W, int C, int cs, const float* h_weight,
                         float* d_dst, void* stream);
 
+/* F.max_pool2d(kernel_size=3, stride=2, padding=1) on dense NHWC, C % 4 == 0 (the monodepth2 encoder's pool; NaN propagates
+ * as in torch) -- d_dst [N, (H - 1) / 2 + 1, (W - 1) / 2 + 1, C] */
+int dfvo_maxpool3x3s2(const float* d_src, int N, int H, int W, int C, float* d_dst, void* stream);
+
 /* F.interpolate(mode='bilinear') on dense NHWC, C % 4 == 0 */
 /* uint8 [H,W,3] -> uint8 [out_h,out_w,3], bit-exact with Pillow's Image.resize((out_w,out_h), Image.LANCZOS): 22-bit
  * fixed-point coefficient tables, horizontal pass then vertical pass, each rounded to uint8 (replaces the host-side
@@ -527,7 +531,7 @@ int dfvo_session_quiesce(dfvo_session* s);           /* a plain solver call is a
 int dfvo_session_push_frame(dfvo_session* s, const uint8_t* h_img, const dfvo_session_kp_cfg* kp, const dfvo_pose2d2d_cfg* pose,
                             int flags, long long* generation);
 /* float [feed_h, feed_w].  DFVO_ERR_RANGE (pointer still set) when the depth net of this frame drove an activation out of
- * f16's range under an f16x3 / f16 packing: the map holds inf / NaN. */
+ * f16's range under an f16x3 / f16 packing: the map holds inf / NaN.  Every read of such a generation returns it. */
 int dfvo_session_depth(dfvo_session* s, long long generation, const float** h_depth);
 /* flow of (generation - 1, generation): fwd / bwd float [2, img_h, img_w], diff float [img_h, img_w]; DFVO_ERR_RANGE as above */
 int dfvo_session_flow(dfvo_session* s, long long generation, const float** h_fwd, const float** h_bwd, const float** h_diff);

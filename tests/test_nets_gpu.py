@@ -66,13 +66,11 @@ def test_flownet_vs_oracle(gpu, conv_precision, h, w):
     gpu.check(lib.dfvo_flownet_forward_host(net, gpu.as_ptr(ref_img), gpu.as_ptr(cur_img), gpu.as_ptr(fwd),
                                             gpu.as_ptr(bwd), gpu.as_ptr(diff)))
     ofwd, obwd, odiff, raw = _oracle_flow(sd, ref_img, cur_img, ("vs", h, w), levels=True)
-    worst = 0.0
     for lvl in (6, 5, 4, 3, 2):
         lh, lw = nh >> (lvl - 1), nw >> (lvl - 1)
         buf = np.zeros((2, lh, lw, 2), np.float32)
         gpu.check(lib.dfvo_flownet_get_level_flow(net, lvl, gpu.as_ptr(buf), None, None))
-        e, s = report("flow level %d (%dx%d)" % (lvl, h, w), np.transpose(buf, (0, 3, 1, 2)), raw[lvl].numpy())
-        worst = max(worst, e / max(1.0, s))
+        _flow_gate("flow level %d (%dx%d) %s" % (lvl, h, w, conv_precision), np.transpose(buf, (0, 3, 1, 2)), raw[lvl].numpy())
     print("   useful GFLOP per forward: %.1f (%s)" % (lib.dfvo_flownet_last_flops(net) / 1e9, conv_precision))
     lib.dfvo_flownet_destroy(net)
     assert np.isfinite(fwd).all() and np.isfinite(bwd).all() and np.isfinite(diff).all()
