@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import depth_world as DW
 from oracle import nets_torch as O
 from synth import image_pair
 from util import report
@@ -322,6 +323,91 @@ def test_depthnet_vs_oracle(gpu, conv_precision, h, w):
     lib.dfvo_depthnet_destroy(net)
     assert np.isfinite(depth).all()
     assert e <= 1e-3 * max(1.0, s)
+    # per pixel: the bound above scales with the FARTHEST depth (0.1 m at 100 m allows 20 % at the nearest 0.5 m)
+    rel = float((np.abs(depth.astype(np.float64) - ref) / ref).max())
+    print("   max per-pixel |d - oracle| / oracle: %.2e" % rel)
+    assert rel <= 1e-4
+
+
+def _depthnet_forward(capi, h, w, sd, img):
+    lib = capi.lib()
+    net = C.c_void_p()
+    capi.check(lib.dfvo_depthnet_create(h, w, 0.1, 100.0, 5.4, None, C.byref(net)))
+    try:
+        capi.set_params(lib.dfvo_depthnet_set_param, net, {k: v.numpy() for k, v in sd.items()})
+        capi.check(lib.dfvo_depthnet_finalize(net))
+        depth = np.zeros((h, w), np.float32)
+        capi.check(lib.dfvo_depthnet_forward_host(net, capi.as_ptr(img), capi.as_ptr(depth)))
+    finally:
+        lib.dfvo_depthnet_destroy(net)
+    assert np.isfinite(depth).all()
+    return depth
+
+
+_depth_cache = {}
+
+
+def _depth_world(world, h, w):
+    """(weights, frame, oracle fp32 depth, float64 depth) of a depth-anchor world, computed once per (world, size)"""
+    key = (world, h, w)
+    if key not in _depth_cache:
+        sd = O.monodepth2_state_dict(4869) if world == "random_weights" else DW.calibrated_monodepth2_state_dict(4869, h, w)
+        img, _ = image_pair(h, w, seed=55)
+        d64 = O.depth_inference(sd, img, dtype=torch.float64)
+        if world == "calibrated":  # the precondition of the test's power (tests/test_depth_world_cpu.py)
+            frac = DW.unsaturated_fraction(DW.disparity(d64))
+            assert frac >= 0.9, "calibrated world %dx%d: only %.3f of the disparities in [0.02, 0.98]" % (h, w, frac)
+        _depth_cache[key] = sd, img, O.depth_inference(sd, img), d64
+    return _depth_cache[key]
+
+
+DEPTH_WORLDS = ["random_weights", "calibrated"]
+# 320x1024: monodepth2's high-resolution model (the feed size is read from the encoder file); larger maps move layers onto
+# other conv families
+DEPTH_SIZES = [(64, 96), (192, 640), (320, 1024)]
+
+
+@pytest.mark.parametrize("h,w", DEPTH_SIZES)
+@pytest.mark.parametrize("world", DEPTH_WORLDS)
+def test_depthnet_distance_to_the_exact_function(gpu, conv_precision, world, h, w):
+    """The depth net's float64 anchor (the flow net's test_flownet_distance_to_the_exact_function, per pixel): the device
+    depth's relative error |d - d64| / d64 against the net evaluated in DOUBLE on the same fp32 weights and frame, gated per
+    statistic (max, p99, median) at DEPTH_ANCHOR_FACTOR times the oracle fp32's own distance plus an ulp-sized floor
+    (tests/depth_world.py).  The calibrated world (trained-like batch-norm scales 1.7e-4 .. 478, 96-99 % unsaturated disparities)
+    is where the encoder, the fold and every decoder level reach the depth; tests/test_depth_world_cpu.py shows on the CPU
+    that a lost f16x3 lo plane in one decoder layer lands about 50x outside this gate, a wrong fold scale in one channel
+    about 220x."""
+    sd, img, o32, d64 = _depth_world(world, h, w)
+    depth = _depthnet_forward(gpu, h, w, sd, img)
+    d, o, x = DW.rel_err_stats(depth, d64), DW.rel_err_stats(o32, d64), DW.rel_err_stats(depth, o32.astype(np.float64))
+    print("ANCHOR depth %s_%dx%d %s: |device - exact| / exact max %.2e p99 %.2e median %.2e | |oracle fp32 - exact| max %.2e "
+          "p99 %.2e median %.2e | |device - oracle fp32| max %.2e p99 %.2e median %.2e" % ((world, h, w, conv_precision) + d + o + x))
+    gate = DW.anchor_gate(o)
+    assert all(a <= g for a, g in zip(d, gate)), "%s %dx%d %s: device %s vs gate %s" % (world, h, w, conv_precision, d, gate)
+
+
+# f16 mode (operands rounded to f16, one product per term; not fp32-class): absolute gates on (max, p99, median) of the
+# per-pixel relative depth error at 2.5x the first device measurement (printed lines "ANCHOR depth ... f16"), which was
+#   random_weights 64x96 1.76e-2 1.04e-2 1.13e-4 | 192x640 2.66e-2 5.10e-3 9.48e-6 | 320x1024 3.93e-2 5.63e-3 1.04e-5
+#   calibrated     64x96 3.53e-2 1.96e-2 2.42e-3 | 192x640 2.93e-2 1.02e-2 1.34e-3 | 320x1024 2.79e-2 9.80e-3 1.35e-3
+# (a float64 simulation of the mode on the CPU, f16-rounded operands layer by layer, lands within 1.3x of these)
+F16_DEPTH_ANCHOR_GATE = {
+    ("random_weights", 64, 96): (4.4e-2, 2.6e-2, 2.8e-4), ("random_weights", 192, 640): (6.7e-2, 1.3e-2, 2.4e-5),
+    ("random_weights", 320, 1024): (9.8e-2, 1.4e-2, 2.6e-5), ("calibrated", 64, 96): (8.8e-2, 4.9e-2, 6e-3),
+    ("calibrated", 192, 640): (7.3e-2, 2.6e-2, 3.4e-3), ("calibrated", 320, 1024): (7e-2, 2.5e-2, 3.4e-3)}
+
+
+@pytest.mark.parametrize("h,w", DEPTH_SIZES)
+@pytest.mark.parametrize("world", DEPTH_WORLDS)
+def test_depthnet_f16_distance_to_the_exact_function(gpu, f16_mode, world, h, w):
+    """the same anchor under the f16 packing: reported and gated at F16_DEPTH_ANCHOR_GATE"""
+    sd, img, o32, d64 = _depth_world(world, h, w)
+    depth = _depthnet_forward(gpu, h, w, sd, img)
+    d, o = DW.rel_err_stats(depth, d64), DW.rel_err_stats(o32, d64)
+    print("ANCHOR depth %s_%dx%d f16: |device - exact| / exact max %.2e p99 %.2e median %.2e | |oracle fp32 - exact| max %.2e "
+          "p99 %.2e median %.2e" % ((world, h, w) + d + o))
+    gate = F16_DEPTH_ANCHOR_GATE[(world, h, w)]
+    assert all(a <= g for a, g in zip(d, gate)), "%s %dx%d f16: device %s vs gate %s" % (world, h, w, d, gate)
 
 
 @pytest.mark.parametrize("h,w", [(960, 1280), (1280, 1920)])

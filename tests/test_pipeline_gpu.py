@@ -124,6 +124,7 @@ def test_pipeline_nets_equal_standalone_executors(gpu, conv_precision, pipe_mod)
     assert torch.equal(md.pred_depths[0], outs["depth"][0]) and torch.equal(md.pred_disps[0], outs["disp"][0])
     o_depth = O.depth_inference(dsd, feed)  # (the oracle's depth is the multiplied one too)
     assert np.abs(outs["depth"][0][0, 0].numpy() * 5.4 - o_depth).max() <= 1e-3 * np.abs(o_depth).max()
+    assert (np.abs(outs["depth"][0][0, 0].numpy().astype(np.float64) * 5.4 - o_depth) / o_depth).max() <= 1e-4  # per pixel
     # DeepFlow helpers of the flow mirror (deep_flow.py:107-129,171-196) on the device, against the torch restatements
     g = torch.Generator().manual_seed(3)
     fl1, fl2 = torch.randn(2, 2, 24, 40, generator=g) * 3, torch.randn(2, 2, 24, 40, generator=g) * 3
