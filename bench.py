@@ -2,9 +2,9 @@
 """bench.py -- KITTI-sized frame pairs per second through the DF-VO tracking hot path on MI355X.
 
 One step = one frame pair (1241x376): monodepth2 depth + LiteFlowNet forward/backward flow + consistency
-(HIP nets: f16x3 split products on the f16 matrix cores by default, fp32-class; `exact_fp32` in the same JSON line is the
-all-fp32-MFMA path timed in the same run), local_bestN keypoint selection, homography + 5 x five-point RANSAC + GRIC +
-recoverPose, depth-ratio scale RANSAC (PnP fallback where the reference takes it), pose out.  Inputs (the two uint8
+(HIP nets: f16x3 split products on the f16 matrix cores by default, fp32-class; with --full, `exact_fp32` in the same JSON
+line is the all-fp32-MFMA path timed in the same run), local_bestN keypoint selection, homography + 5 x five-point RANSAC +
+GRIC + recoverPose, depth-ratio scale RANSAC (PnP fallback where the reference takes it), pose out.  Inputs (the two uint8
 frames) are resident in HBM before the timed region; the Pillow-exact LANCZOS resize of the depth input runs on the
 device inside it.
 
@@ -19,8 +19,8 @@ solver stage fed a synthetic rigid-scene flow / consistency / depth triple of th
 N > 1: one process per GPU over RCCL.  Under torch.distributed.run (WORLD_SIZE set) this process is one rank; run
 directly, bench.py re-launches itself under torch.distributed.run with N ranks on 127.0.0.1.  The N ranks track ONE
 sequence of N x K pairs: contiguous chunk per rank from its 1-frame halo (df-vo_amd/sequence.py run_sequence), one
-all-gather of the relative poses, prefix composition on every rank; rank 0 then re-tracks the whole sequence alone
-(outside the timed region) and checks the gathered poses bit for bit.
+all-gather of the relative poses, prefix composition on every rank; with --full, rank 0 then re-tracks the whole sequence
+alone (outside the timed region) and checks the gathered poses bit for bit.
 
 --surface mirrors   times the drop-in class surface instead of the fused pipeline object: DeepModel / KeypointSampler /
                     EssTracker / PnpTracker built from weight FILES, host numpy arrays in and out, the frame loop of
@@ -28,7 +28,14 @@ all-gather of the relative poses, prefix composition on every rank; rank 0 then 
 --frames host       frames arrive in pinned host memory: each pair's new frame is uploaded on a copy stream inside the
                     timed region, overlapped with the nets of the pairs in flight (default: frames resident in HBM).
 
-Prints ONE JSON line on rank 0 (contract in the task description; `roofline` and `cpu_baseline` added).
+--full              also runs everything the headline does not need, after (or, for the child legs, before) the timed
+                    steps: the exact-fp32 and features-recomputed legs, the roofline pass, the CPU baseline, the child legs
+                    (dropin_surface, frames_host, other_configs) and the multi-rank single-rank re-check.  A plain run sets
+                    up, warms up, times the steps, writes --dump-outputs and prints its line; the fields of the legs it
+                    skipped are null.
+
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step, config, ...; with --full also
+`exact_fp32`, `features_recomputed`, `frames_host`, `dropin_surface`, `other_configs`, `roofline` and `cpu_baseline`.
 """
 import argparse
 import importlib
@@ -439,9 +446,9 @@ def gpu_visible():
 
 
 def other_leg(argv, timeout=300):
-    """one short leg of the default line: bench.py itself in a child process, its JSON line reduced to the figures"""
+    """one short leg of the --full line: a plain run of bench.py in a child process, its JSON line reduced to the figures"""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__)] + argv + ["--no-cpu-baseline", "--no-roofline", "--no-exact-leg", "--no-other-legs"]
+    cmd = [sys.executable, os.path.abspath(__file__)] + argv
     t0 = time.perf_counter()
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
@@ -498,7 +505,7 @@ def run_job(args, pipe, d_frames, dist, world, rank, local_rank, on_gpu, torch, 
         dt = float(tmax.item())
     status = np.concatenate([v["gathered"][:, 16] for v in res.values()]).astype(np.int64)
     check = None
-    if rank == 0 and world > 1 and on_gpu:  # outside the timed region: the same job on this rank alone, per-pair RandomState
+    if args.full and rank == 0 and world > 1 and on_gpu:  # outside the timed region: the same job on this rank alone, per-pair RandomState
         one = smod.run_sequences(pipe, seqs, 1, 0, None, rng_mode="per_pair")
         same = all(np.array_equal(one[k]["gathered"][:, 16], res[k]["gathered"][:, 16]) and
                    np.array_equal(one[k]["gathered"][one[k]["gathered"][:, 16] != 1], res[k]["gathered"][one[k]["gathered"][:, 16] != 1])
@@ -539,8 +546,12 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--height", type=int, default=376)
     ap.add_argument("--width", type=int, default=1241)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the exact-fp32 and features-recomputed legs, the roofline "
+                         "pass, the CPU baseline, the child legs (class surface, host frames, other BASELINE configs) and, on "
+                         "N ranks, the single-rank re-check (off: set up, warm up, time the steps, dump, print the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline pass")
     ap.add_argument("--conv-precision", default=os.environ.get("DFVO_CONV_PRECISION", "f16x3"), choices=["fp32", "f16x3", "f16"],
                     help="arithmetic of the conv layers: f16x3 (default: fp32-class split kernels, the whole -m gpu net / "
                          "pipeline parity suite runs green on it at the exact path's tolerances), fp32 (exact fp32 MFMA), "
@@ -555,9 +566,10 @@ def main(argv=None):
                     help="fused: the dfvo_pipeline_* object (default); mirrors: the reference's class surface over host arrays")
     ap.add_argument("--frames", default="device", choices=["device", "host"],
                     help="host: pinned host frames, H2D on a copy stream inside the timed region")
-    ap.add_argument("--no-exact-leg", action="store_true", help="skip the second timed leg in exact fp32 (exact_fp32 in the JSON line)")
+    ap.add_argument("--no-exact-leg", action="store_true",
+                    help="with --full: skip the second timed leg in exact fp32 (exact_fp32 in the JSON line)")
     ap.add_argument("--no-other-legs", action="store_true",
-                    help="skip the short extra legs of the default line: dropin_surface (the reference's class surface, 8 pairs), "
+                    help="with --full: skip the short extra legs of the line: dropin_surface (the reference's class surface, 8 pairs), "
                          "other_configs (BASELINE configs 3 / 4 / 5, a few pairs each) and features_recomputed")
     ap.add_argument("--feature-carry", default="on", choices=["on", "off"],
                     help="on: the flow net's image / feature pyramids of a pair's reference frame are the ones the previous pair "
@@ -569,7 +581,7 @@ def main(argv=None):
                          "halo per item, one all-gather, per-sequence composition; --steps / --warmup are ignored")
     ap.add_argument("--scale", type=float, default=0.02, help="--sequences: fraction of the 23 201 KITTI frames (>= 2 frames per sequence)")
     ap.add_argument("--cpu-pairs", type=int, default=3,
-                    help="pairs of the cpu_baseline leg (default 3: ~17 s on the GPU box's host cores; BASELINE.md section 4's protocol "
+                    help="pairs of the cpu_baseline leg of --full (default 3: ~17 s on the GPU box's host cores; BASELINE.md section 4's protocol "
                          "is >= 20 pairs after 3 warm-up pairs: --cpu-pairs 20 takes ~2.5 min)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
@@ -583,14 +595,14 @@ def main(argv=None):
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
 
-    # Short GPU-only legs of the default line, so that the driver's ONE command also observes (a) the surface the reference's
-    # own frame loop calls and (b) the other BASELINE configurations.  Each is this script again in a child process, run
+    # Short GPU-only legs of the --full line, so that one command also observes (a) the surface the reference's own frame
+    # loop calls and (b) the other BASELINE configurations.  Each is a plain run of this script in a child process, run
     # BEFORE this process creates its HIP context: a child that shares the GPU with a parent holding twelve hardware queues
     # measured 77 frames/s through the class surface against 132 alone (profiles/r5c_*: queue over-subscription), and none of
     # it overlaps the headline's timed region.
     dropin = others = frames_host = None
-    if (args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_other_legs and args.surface == "fused" and not args.sequences
-            and args.solver_inputs == "nets" and (args.height, args.width) == (376, 1241) and args.kp_bestn == 2000
+    if (args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_other_legs and args.surface == "fused"
+            and not args.sequences and args.solver_inputs == "nets" and (args.height, args.width) == (376, 1241) and args.kp_bestn == 2000
             and args.e_max_iters == 1000 and args.frames == "device" and gpu_visible()):
         dropin = other_leg(["--surface", "mirrors", "--steps", "30", "--warmup", "5", "--conv-precision", args.conv_precision])
         # SURVEY 8(d) defines the metric as images in -> pose out; `value` is, by the bench contract, the rate with the frames
@@ -824,7 +836,7 @@ def main(argv=None):
         status = gathered[:, 16].astype(np.int64)
         if args.dump_outputs and rank == 0:
             dump_outputs(args.dump_outputs, {"poses_gathered": gathered, "trajectory": np.asarray(traj, np.float64)})
-        if rank == 0 and on_gpu:  # outside the timed region: the same sequence tracked by this rank alone
+        if args.full and rank == 0 and on_gpu:  # outside the timed region: the same sequence tracked by this rank alone
             rel1, st1 = smod.track_chunk(pipe, frames, 0, n_total, rng_mode="per_pair", carry_features=carry[0])
             same = bool(np.array_equal(rel1.reshape(n_total, 16)[st1 != 1], gathered[:, :16][st1 != 1]) and np.array_equal(st1, status))
             seq_check = {"pairs": int(n_total), "equal_to_single_rank_run": same,
@@ -841,7 +853,7 @@ def main(argv=None):
         steady = (len(t_track) - ahead) / (t_track[-1] - t_track[ahead - 1])
     net_flops_ref = net_flops  # the reference's work per pair: Features on both frames in every model call
     recomputed = None
-    if rank == 0 and world == 1 and on_gpu and nets_mode and carry[0] and not args.no_other_legs:
+    if args.full and rank == 0 and world == 1 and on_gpu and nets_mode and carry[0] and not args.no_other_legs:
         # the same workload with both frames of every pair through Features (third timed leg, same warm-up / steps / clock)
         carry[0] = False
         run(pipe, args.warmup)
@@ -857,7 +869,7 @@ def main(argv=None):
                       "tracked_by_E": int((st_r == 0).sum()), "tracked_by_PnP": int((st_r == 3).sum())}
 
     roof = None
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if args.full and rank == 0 and world == 1 and not args.no_roofline:
         # per-launch durations of the conv kernel family, HIP events on the launch streams, graphs off
         # (one pair in flight at a time here: overlapping passes would stretch each other's launches)
         pipe.set_graph(0)
@@ -936,7 +948,7 @@ def main(argv=None):
             pass
 
     exact = None
-    if rank == 0 and world == 1 and not args.no_exact_leg and args.conv_precision != "fp32" and nets_mode and on_gpu:
+    if args.full and rank == 0 and world == 1 and not args.no_exact_leg and args.conv_precision != "fp32" and nets_mode and on_gpu:
         # the same workload with every layer on the exact fp32-MFMA kernels: a second pipeline (the precision is fixed when
         # the layers are packed), same warm-up and step count, timed the same way
         pipe.close()
@@ -955,7 +967,7 @@ def main(argv=None):
         pipe_x.close()
         capi.check(capi.lib().dfvo_set_conv_precision(args.conv_precision.encode()))
     base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         base = cpu_baseline_nets(seq["frames"], fsd, dsd, K, H, W, n_pairs=args.cpu_pairs) if nets_mode else cpu_baseline(syn, H, W, scenes)
     seen = ranks_seen(dist, world, rank, local_rank, torch)
     if pipe is not None:

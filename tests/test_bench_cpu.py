@@ -1,7 +1,8 @@
 """CPU (gloo, world_size 2): the multi-rank logic of bench.py -- world setup from the torchrun environment, ONE sequence
 of world x steps pairs tracked as contiguous chunks from each rank's halo frame (df-vo_amd/sequence.py run_sequence), the
 single pose all-gather, max-over-ranks timing, rank 0's JSON line (n_gpus, ranks_seen) -- with the device pipeline replaced
-by a stub (no GPU here), and the `--gpus N` self-launch command line."""
+by a stub (no GPU here), the `--gpus N` self-launch command line, and on one rank which extra legs a plain run and a
+--full run enter."""
 import importlib
 import io
 import json
@@ -198,6 +199,62 @@ def test_bench_gpus_flag_self_launch(monkeypatch):
     assert cmd[1:3] == ["-m", "torch.distributed.run"] and "--nproc-per-node" in cmd and cmd[cmd.index("--nproc-per-node") + 1] == "8"
     assert "--master-addr" in cmd and cmd[cmd.index("--master-addr") + 1] == "127.0.0.1"
     assert cmd[-4:] == ["--gpus", "8", "--steps", "3"] and cmd[-5].endswith("bench.py")
+
+
+class _Lib:  # the one C ABI call a single-rank run makes outside the pipeline object
+    def dfvo_set_device(self, dev):
+        return 0
+
+
+def _single_rank(monkeypatch, argv):
+    """bench.main on one rank with the device pipeline, the C ABI and the extra legs replaced on the host: the JSON line and
+    the legs that were entered (a plain run that reached the roofline pass or the exact-fp32 leg would fail on the stubs)"""
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    pmod = importlib.import_module("df-vo_amd.pipeline")
+    capi = importlib.import_module("df-vo_amd.capi")
+    monkeypatch.setattr(StubPipeline, "hybrid_pose", staticmethod(pmod.TrackingPipeline.hybrid_pose), raising=False)
+    monkeypatch.setattr(StubPipeline, "accumulate", staticmethod(pmod.TrackingPipeline.accumulate), raising=False)
+    monkeypatch.setattr(pmod, "TrackingPipeline", StubPipeline)
+    monkeypatch.setattr(capi, "lib", lambda: _Lib())
+    monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
+    monkeypatch.setattr(bench, "to_device", lambda a: torch.from_numpy(np.ascontiguousarray(a)))
+    monkeypatch.setattr(bench, "device_sync", lambda: None)
+    monkeypatch.setattr(bench, "gpu_visible", lambda: True)
+    legs = []
+    monkeypatch.setattr(bench, "other_leg", lambda a, timeout=300: legs.append(" ".join(a)) or {"value": 1.0})
+    monkeypatch.setattr(bench, "cpu_baseline_nets", lambda *a, **k: legs.append("cpu_baseline") or {"value": 1.0})
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setenv("DFVO_CONV_PRECISION", os.environ.get("DFVO_CONV_PRECISION", "f16x3"))
+    buf = io.StringIO()
+    with redirect_stdout(buf):
+        bench.main(argv)
+    return json.loads(buf.getvalue().strip().splitlines()[-1]), legs
+
+
+def test_plain_run_times_the_steps_and_nothing_else(monkeypatch):
+    """without --full a run sets up, warms up, times the steps and prints its line: no child leg, no CPU baseline, no
+    second timed leg, no roofline pass"""
+    line, legs = _single_rank(monkeypatch, ["--gpus", "1", "--steps", "6", "--warmup", "2"])
+    assert legs == []
+    assert line["steps"] == 6 and line["warmup"] == 2 and line["unit"] == "frames/s" and line["higher_is_better"] is True
+    assert line["value"] > 0 and line["ms_per_step"] > 0  # (the stub's steps take microseconds: no rate arithmetic here)
+    assert line["config"]["tracked_by_E"] == 6 and line["steady_state"] is not None
+    for k in ("exact_fp32", "features_recomputed", "frames_host", "dropin_surface", "other_configs", "roofline", "cpu_baseline"):
+        assert line[k] is None, k
+
+
+def test_full_run_keeps_the_extra_legs(monkeypatch):
+    """--full: the child legs (class surface, host frames, BASELINE configs 3 / 4 / 5), the features-recomputed leg and the
+    CPU baseline still run, and the headline is timed as in a plain run"""
+    line, legs = _single_rank(monkeypatch, ["--gpus", "1", "--steps", "6", "--warmup", "2", "--full", "--no-roofline",
+                                            "--no-exact-leg"])
+    assert legs[-1] == "cpu_baseline" and len(legs) == 7
+    assert legs[0].startswith("--surface mirrors") and legs[1].startswith("--frames host --steps 6 --warmup 2")
+    assert any(a.startswith("--sequences kitti-lengths") for a in legs) and any("--conv-precision f16" in a for a in legs)
+    assert line["steps"] == 6 and line["features_recomputed"]["tracked_by_E"] == 6
+    assert line["dropin_surface"] == line["frames_host"] == line["cpu_baseline"] == {"value": 1.0}
+    assert len(line["other_configs"]) == 4 and line["roofline"] is None and line["exact_fp32"] is None
 
 
 def test_committed_profile_feeds_the_hbm_roofline_entry():

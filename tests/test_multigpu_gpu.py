@@ -75,8 +75,8 @@ def test_rccl_allgather_of_uneven_pose_rows_equals_gloo(gpu, tmp_path, world):
 def test_bench_two_gpus_over_rccl(gpu):
     if _n_devices() < 2:
         pytest.skip("needs 2 visible GPUs; this box has %d" % _n_devices())
-    r = _launch(2, ["bench.py", "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-exact-leg", "--no-other-legs"],
-                {}, 29547)
+    r = _launch(2, ["bench.py", "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-exact-leg",
+                    "--no-other-legs"], {}, 29547)  # --full: the single-rank re-check that fills sequence_check
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     print({k: line[k] for k in ("value", "n_gpus", "ms_per_step", "scaling")}, line.get("sequence_check"), line["config"].get("ranks_seen"))
