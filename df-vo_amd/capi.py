@@ -88,7 +88,7 @@ class ConvDesc(C.Structure):
     _fields_ = [(n, C.c_int) for n in (
         "N", "H", "W", "kh", "kw", "stride", "pad_h", "pad_w", "pad_mode",
         "c0", "cs0", "co0", "up0", "c1", "cs1", "co1", "cout", "act")] + [
-        ("act_param", C.c_float)] + [(n, C.c_int) for n in ("res_cs", "res_co", "dst_cs", "dst_co")]
+        ("act_param", C.c_float)] + [(n, C.c_int) for n in ("res_cs", "res_co", "dst_cs", "dst_co", "dst_zero_to")]
 
 
 _vp, _i, _f, _d, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
@@ -136,6 +136,13 @@ SIGNATURES = {
     "dfvo_conv_profile_end_bytes": (_i, [_vp, _vp, _vp, _vp]),
     "dfvo_correlation": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "dfvo_backward_warp": (_i, [_vp, _vp, _f, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "dfvo_warp_view": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _f, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "dfvo_correlation_view": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp]),
+    "dfvo_flow_mean": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "dfvo_reg_prep": (_i, [_vp, _vp, _i, _i, _f, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "dfvo_reg_head": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _f, _vp, _f, _i, _i, _i, _vp, _i, _i, _vp]),
+    "dfvo_flow_post": (_i, [_vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp]),
+    "dfvo_img_u8_to_flow_input": (_i, [_vp, _i, _i, _vp, _i, _i, _vp]),
     "dfvo_deconv_dw4x4s2": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "dfvo_maxpool3x3s2": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "dfvo_lanczos_coeffs": (_i, [_i, _i, _vp, _vp, _i, _ip]),

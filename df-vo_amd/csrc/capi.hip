@@ -3,6 +3,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -81,6 +82,8 @@ int dfvo_conv2d(const dfvo_conv_desc* d, const float* d_src0, const float* d_src
                 const float* h_bias, const float* d_res, float* d_dst, void* stream) {
     DFVO_ARG_CHECK(d && d_src0 && h_w && d_dst, "dfvo_conv2d: null argument");
     DFVO_ARG_CHECK(d->c1 == 0 || d_src1, "dfvo_conv2d: c1 > 0 needs d_src1");
+    DFVO_ARG_CHECK(d->dst_zero_to == 0 || (d->dst_zero_to >= d->cout && d->dst_co + d->dst_zero_to <= d->dst_cs),
+                   "dfvo_conv2d: dst_zero_to outside the destination view");
     hipStream_t s = (hipStream_t)stream;
     const int Ho = (d->H + 2 * d->pad_h - d->kh) / d->stride + 1;
     const int Wo = (d->W + 2 * d->pad_w - d->kw) / d->stride + 1;
@@ -136,7 +139,8 @@ int dfvo_conv2d(const dfvo_conv_desc* d, const float* d_src0, const float* d_src
     std::lock_guard<std::mutex> conv2d_lock(conv2d_mu);
     if (!conv2d_ws.p && conv2d_ws.alloc((size_t)4 << 20) != DFVO_OK) conv2d_ws.p = nullptr;
     int rc = run_conv(L, d->N, d->H, d->W, View{d_src0, d->cs0, d->co0}, d->up0, View{d_src1, d->cs1, d->co1}, d_res,
-                      d->res_cs, d->res_co, d_dst, d->dst_cs, d->dst_co, 0, s, nullptr, conv2d_ws.p ? &conv2d_ws : nullptr);
+                      d->res_cs, d->res_co, d_dst, d->dst_cs, d->dst_co, d->dst_zero_to, s, nullptr,
+                      conv2d_ws.p ? &conv2d_ws : nullptr);
     hipError_t e = hipStreamSynchronize(s);
     (void)hipFree(dw);
     (void)hipFree(db);
@@ -201,6 +205,98 @@ int dfvo_backward_warp(const float* d_src, const float* d_flow, float mult, int 
     if (rc != DFVO_OK) return rc;
     DFVO_HIP_CHECK(e);
     return DFVO_OK;
+}
+
+// host table -> device (freed by the caller)
+static int upload_table(const float* h, int n, float** d) {
+    DFVO_ARG_CHECK(h && n > 0, "null host table");
+    DFVO_HIP_CHECK(hipMalloc((void**)d, (size_t)n * sizeof(float)));
+    DFVO_HIP_CHECK(hipMemcpy(*d, h, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    return DFVO_OK;
+}
+
+// launch, wait for the stream, free the temporaries; the launch's error wins over the stream's
+static int finish(int rc, hipStream_t s, std::initializer_list<void*> temps) {
+    hipError_t e = hipStreamSynchronize(s);
+    for (void* t : temps)
+        if (t) (void)hipFree(t);
+    if (rc != DFVO_OK) return rc;
+    DFVO_HIP_CHECK(e);
+    return DFVO_OK;
+}
+
+int dfvo_warp_view(const float* d_src, int scs, int sco, int swap, const float* d_flow, int fcs, int fco, float mult, int N,
+                   int H, int W, int C, const float* h_lin_x, const float* h_lin_y, float* d_dst, int dcs, int dco,
+                   int append_flow, int step, void* stream) {
+    DFVO_ARG_CHECK(d_src && d_flow && d_dst && N > 0 && H > 1 && W > 1 && C > 0 && step >= 1, "dfvo_warp_view: bad argument");
+    DFVO_ARG_CHECK(sco + C <= scs && fco + 2 <= fcs && dco + C + (append_flow ? 4 : 0) <= dcs, "dfvo_warp_view: view too narrow");
+    hipStream_t s = (hipStream_t)stream;
+    float *dx = nullptr, *dy = nullptr;
+    int rc = upload_table(h_lin_x, W, &dx);
+    if (rc == DFVO_OK) rc = upload_table(h_lin_y, H, &dy);
+    if (rc == DFVO_OK)
+        rc = launch_warp(d_src, scs, sco, swap, d_flow, fcs, fco, mult, N, H, W, C, dx, dy, d_dst, dcs, dco, append_flow, s, step);
+    return finish(rc, s, {dx, dy});
+}
+
+int dfvo_correlation_view(const float* d_first, int cs1, int co1, const float* d_second, int cs2, int co2, int swap2, int N,
+                          int H, int W, int C, int stride, float slope, float* d_out, int dcs, void* stream) {
+    DFVO_ARG_CHECK(d_first && d_second && d_out && N > 0 && H > 0 && W > 0 && C > 0, "dfvo_correlation_view: null argument");
+    DFVO_ARG_CHECK(stride == 1 || stride == 2, "dfvo_correlation_view: stride must be 1 or 2");
+    DFVO_ARG_CHECK(co1 + C <= cs1 && co2 + C <= cs2 && dcs >= 49, "dfvo_correlation_view: view too narrow");
+    hipStream_t s = (hipStream_t)stream;
+    return finish(launch_correlation(d_first, cs1, co1, d_second, cs2, co2, swap2, N, H, W, C, stride, d_out, dcs, slope, s),
+                  s, {});
+}
+
+int dfvo_flow_mean(const float* d_flow, int fcs, int fco, int N, int HW, float* d_mean, void* stream) {
+    DFVO_ARG_CHECK(d_flow && d_mean && N > 0 && HW > 0 && fco + 2 <= fcs, "dfvo_flow_mean: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = flow_mean_scratch_floats(N);
+    float* scratch = nullptr;
+    DFVO_HIP_CHECK(hipMalloc((void**)&scratch, n * sizeof(float)));
+    hipError_t e = hipMemsetAsync(scratch, 0, n * sizeof(float), s);
+    const int rc = e == hipSuccess ? launch_flow_mean(d_flow, fcs, fco, N, HW, scratch, d_mean, s) : DFVO_OK;
+    const int rf = finish(rc, s, {scratch});
+    DFVO_HIP_CHECK(e);
+    return rf;
+}
+
+int dfvo_reg_prep(const float* d_img, const float* d_flow, int fcs, int fco, float mult, const float* d_mean, int N, int H,
+                  int W, const float* h_lin_x, const float* h_lin_y, float* d_dst, void* stream) {
+    DFVO_ARG_CHECK(d_img && d_flow && d_mean && d_dst && N > 0 && H > 1 && W > 1 && fco + 2 <= fcs, "dfvo_reg_prep: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    float *dx = nullptr, *dy = nullptr;
+    int rc = upload_table(h_lin_x, W, &dx);
+    if (rc == DFVO_OK) rc = upload_table(h_lin_y, H, &dy);
+    if (rc == DFVO_OK) rc = launch_reg_prep(d_img, d_flow, fcs, fco, mult, d_mean, N, H, W, dx, dy, d_dst, s);
+    return finish(rc, s, {dx, dy});
+}
+
+int dfvo_reg_head(const float* d_dist, int dist_cs, int k, const float* d_flow, int fcs, int fco, const float* h_wx, float bx,
+                  const float* h_wy, float by, int N, int H, int W, float* d_dst, int dcs, int dco, void* stream) {
+    DFVO_ARG_CHECK(d_dist && d_flow && d_dst && N > 0 && H > 0 && W > 0 && (k == 3 || k == 5 || k == 7), "dfvo_reg_head: bad argument");
+    DFVO_ARG_CHECK(dist_cs >= k * k && fco + 2 <= fcs && dco + 2 <= dcs, "dfvo_reg_head: view too narrow");
+    hipStream_t s = (hipStream_t)stream;
+    float *wx = nullptr, *wy = nullptr;
+    int rc = upload_table(h_wx, k * k, &wx);
+    if (rc == DFVO_OK) rc = upload_table(h_wy, k * k, &wy);
+    if (rc == DFVO_OK) rc = launch_reg_head(d_dist, dist_cs, k, d_flow, fcs, fco, wx, bx, wy, by, N, H, W, d_dst, dcs, dco, s);
+    return finish(rc, s, {wx, wy});
+}
+
+int dfvo_flow_post(const float* d_netflow, int fcs, int fco, int h, int w, float scale, int H, int W, float* d_fwd,
+                   float* d_bwd, float* d_diff, void* stream) {
+    DFVO_ARG_CHECK(d_netflow && d_fwd && d_bwd && d_diff && h > 0 && w > 0 && H > 1 && W > 1 && fco + 2 <= fcs,
+                   "dfvo_flow_post: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    return finish(launch_flow_post(d_netflow, fcs, fco, h, w, scale, H, W, d_fwd, d_bwd, d_diff, s), s, {});
+}
+
+int dfvo_img_u8_to_flow_input(const uint8_t* d_img, int H, int W, float* d_dst, int th, int tw, void* stream) {
+    DFVO_ARG_CHECK(d_img && d_dst && H > 0 && W > 0 && th > 0 && tw > 0, "dfvo_img_u8_to_flow_input: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    return finish(launch_img_u8_to_flow_input(d_img, H, W, d_dst, th, tw, s), s, {});
 }
 
 int dfvo_maxpool3x3s2(const float* d_src, int N, int H, int W, int C, float* d_dst, void* stream) {

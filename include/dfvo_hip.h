@@ -61,6 +61,8 @@ typedef struct dfvo_conv_desc {
     float act_param;
     int res_cs, res_co;       /* residual view (used when d_res != NULL) */
     int dst_cs, dst_co;
+    int dst_zero_to;          /* != 0: the epilogue also zero-fills channels [cout, dst_zero_to) of dst (the flow net's
+                                 distance convolutions pad k*k to a multiple of 4 this way) */
 } dfvo_conv_desc;
 int dfvo_conv2d(const dfvo_conv_desc* desc, const float* d_src0, const float* d_src1, const float* h_weight_oihw,
                 const float* h_bias, const float* d_res, float* d_dst, void* stream);
@@ -113,6 +115,34 @@ int dfvo_correlation(const float* d_first, const float* d_second, int N, int H, 
  * tables (HOST; NULL = library formula). */
 int dfvo_backward_warp(const float* d_src, const float* d_flow, float flow_mult, int N, int H, int W, int C,
                        const float* h_lin_x, const float* h_lin_y, float* d_dst, void* stream);
+
+/* The flow net's non-conv launches with every argument the net passes (FlowNet::enqueue_levels), for the per-operator
+ * tests.  NHWC float views (pointer, floats per pixel, channel offset); h_lin_x / h_lin_y: torch.linspace(-1,1,W/H) on the
+ * HOST.  Each call returns after the launch has finished on `stream`.
+ * dfvo_warp_view: Backward() of source sample (swap ? N-1-n : n) at (x, y) + flow * mult into dst channels [dco, dco + C);
+ * append_flow: dst channels C, C+1 = the flow, C+2, C+3 = 0; step > 1: only the pixels y % step == 0, x % step == 0. */
+int dfvo_warp_view(const float* d_src, int scs, int sco, int swap, const float* d_flow, int fcs, int fco, float mult, int N,
+                   int H, int W, int C, const float* h_lin_x, const float* h_lin_y, float* d_dst, int dcs, int dco,
+                   int append_flow, int step, void* stream);
+/* correlation of first[n] with second[swap2 ? N-1-n : n] + leaky_relu(slope) into d_out [N, ceil(H/s), ceil(W/s), dcs] */
+int dfvo_correlation_view(const float* d_first, int cs1, int co1, const float* d_second, int cs2, int co2, int swap2, int N,
+                          int H, int W, int C, int stride, float slope, float* d_out, int dcs, void* stream);
+/* per-sample mean of a 2-channel flow view over H*W pixels -> d_mean [N][2] (lite_flow_net.py:255) */
+int dfvo_flow_mean(const float* d_flow, int fcs, int fco, int N, int HW, float* d_mean, void* stream);
+/* Regularization input, lite_flow_net.py:244-255: d_dst [N,H,W,4] = (sqrt(sum_c (img[n] - warp(img[N-1-n]))^2 + 1e-6),
+ * flow - mean[n], 0); d_img NHWC4, d_mean [N][2] on the device */
+int dfvo_reg_prep(const float* d_img, const float* d_flow, int fcs, int fco, float mult, const float* d_mean, int N, int H,
+                  int W, const float* h_lin_x, const float* h_lin_y, float* d_dst, void* stream);
+/* Regularization output head, lite_flow_net.py:256-264: softmax of -dist^2 over the k*k taps, weighted with the zero-padded
+ * k x k unfold of the flow and moduleScaleX / Y (h_wx, h_wy: k*k floats each) */
+int dfvo_reg_head(const float* d_dist, int dist_cs, int k, const float* d_flow, int fcs, int fco, const float* h_wx, float bx,
+                  const float* h_wy, float by, int N, int H, int W, float* d_dst, int dcs, int dco, void* stream);
+/* the net's output stage: level-2 flow x scale, bilinear (align_corners) to H x W, x (W/w, H/h) -> d_fwd / d_bwd [2,H,W]
+ * (samples 0 / 1), d_diff [H,W] = forward-backward consistency (deep_flow.py:107-129,171-196) */
+int dfvo_flow_post(const float* d_netflow, int fcs, int fco, int h, int w, float scale, int H, int W, float* d_fwd,
+                   float* d_bwd, float* d_diff, void* stream);
+/* uint8 [H,W,3] -> float NHWC4 [th,tw,4] = bilinear (align_corners) of u8 / 255, channel 3 = 0 (the net's input) */
+int dfvo_img_u8_to_flow_input(const uint8_t* d_img, int H, int W, float* d_dst, int th, int tw, void* stream);
 
 /* depthwise ConvTranspose2d(k=4, s=2, p=1, bias=False), lite_flow_net.py:109,117. h_weight [C,1,4,4] */
 int dfvo_deconv_dw4x4s2(const float* d_src, int N, int H, int W, int C, int cs, const float* h_weight,

@@ -3,13 +3,10 @@
 Every convolution of DepthNet::enqueue (tests/depth_world.py: DEPTH_LAYERS) runs as one dfvo_conv2d on the layer's real
 input in the calibrated world at 192x640: the float64 oracle's activations, rounded to fp32, with the batch norm folded as
 bn_fold does it in float32.  The result is compared with the float64 convolution of the same fp32 operands, per output,
-with test_f16x3_dynamic_range's bounds (sabs = sum|w x| + |bias| + |residual|):
-    fp32    2^-20 sabs
-    f16x3   (2^-22 + 2^-20) sabs + 2^-36 (sum|w| [some |x| < 2^-14] + sum|x| [some |w| < 2^-14])
-    f16     2^-20 sabs against the f16-ROUNDED operands (the one-channel head stays exact fp32 in this mode)
-ReLU, ELU and the sigmoid are 1-Lipschitz, so the bound carries through the epilogue.  The encoder's max-pool runs on the
-real stem output and must equal F.max_pool2d bit for bit.  test_inventory_runs_the_families_the_net_runs proves the
-inventory exercised the kernel families the net itself launches, profile row by profile row."""
+with test_f16x3_dynamic_range's bounds (tests/layer_bounds.py; the one-channel head stays exact fp32 in the f16 modes).
+The encoder's max-pool runs on the real stem output and must equal F.max_pool2d bit for bit.
+test_inventory_runs_the_families_the_net_runs proves the inventory exercised the kernel families the net itself launches,
+profile row by profile row."""
 import ctypes as C
 
 import numpy as np
@@ -20,6 +17,7 @@ import torch.nn.functional as F
 import depth_world as W
 from oracle import nets_torch as O
 from synth import image_pair
+from layer_bounds import conv_bound
 from test_ops_gpu import run_conv
 
 pytestmark = pytest.mark.gpu
@@ -63,21 +61,9 @@ def _run_layer(gpu, precision, L):
         gpu.check(lib.dfvo_set_conv_precision(b"fp32"))
         n_ovf = gpu.f16s_overflow_count(reset=True)
     assert n_ovf == 0, "%s %s: %d f16 range events" % (precision, L["name"], n_ovf)
-    xin = W.layer_input(L, a32).double()
-    w64, b64 = wt.double(), b.double()
     head = L["name"] == "decoder.10.conv"
-    if precision == "f16" and not head:
-        xin, w64 = xin.half().double(), wt.half().double()
-    r64 = res.double() if res is not None else 0.0
-    y = W.conv(L, xin, w64, b64) + r64
-    sabs = W.conv(L, xin.abs(), w64.abs()) + b64.abs().view(1, -1, 1, 1) + (r64.abs() if res is not None else 0.0)
-    bound = 2.0 ** -20 * sabs
-    if precision == "f16x3" and not head:
-        bound = bound + 2.0 ** -22 * sabs
-        if float(xin.abs().min()) < 2.0 ** -14:
-            bound = bound + 2.0 ** -36 * W.conv(L, torch.ones_like(xin), w64.abs())
-        if float(w64.abs().min()) < 2.0 ** -14:
-            bound = bound + 2.0 ** -36 * W.conv(L, xin.abs(), torch.ones_like(w64))
+    _, _, y, bound = conv_bound(lambda x, w, bb: W.conv(L, x, w, bb), W.layer_input(L, a32).double(), wt.double(), b.double(),
+                                res.double() if res is not None else None, precision, exact_fp32=head)
     _cache[key] = (out, W.ACT[L["act"]](y), bound, ln.copy())
     return _cache[key]
 
