@@ -130,6 +130,17 @@ SM_HD_NOINLINE double np_pairwise_sum(const double* a, int n) {
     return np_pairwise_sum(a, n2) + np_pairwise_sum(a + n2, n - n2);
 }
 
+// np.add.reduce / np.mean's sum over a contiguous float64 array as numpy evaluates it: the reduction walks the array in
+// blocks of the ufunc buffer size (np.getbufsize() = 8192 elements) and adds each block's pairwise sum to the running
+// total, so above 8192 elements it is NOT one pairwise sum (found by the 20000-keypoint cases of tests/pose_world.py:
+// the mean displacement of validity.method 'flow' was one ulp off numpy's)
+SM_HD_NOINLINE double np_add_reduce(const double* a, int n) {
+    const int kBuf = 8192;
+    double res = 0.;
+    for (int i = 0; i < n; i += kBuf) res += np_pairwise_sum(a + i, n - i < kBuf ? n - i : kBuf);
+    return res;
+}
+
 // RigidFlow layer for one pixel (geometry/{backprojection,transformation3d,projection}.py, layers.py PixToFlow) in
 // float32: every matmul row is a0*b0 rounded, then fused multiply-adds in ascending k (the order of the torch-CPU GEMM
 // that produced tests/golden/rigid_flow_kp.npz).  Ki: inverse intrinsics 3x3, T: 4x4 motion, K: intrinsics 3x3.

@@ -847,17 +847,26 @@ __device__ __forceinline__ uint32_t mt_mask_of(uint32_t v) {
 //     64-word batch + scalar compare/branch), the MT19937 block regeneration + tempering on all threads.
 //  B  the swap chains  p[i] <-> p[j_i]  of the repeats, one lane per repeat in lockstep out of LDS
 //     (the repeats are independent once their j lists are known).
+// snap (optional) [repeat + 1][MT_SNAP_STRIDE]: the stream's state before the first shuffle and behind each one -- where the
+// reference would have raised in the middle of its repeat loop, the bookkeeping kernel hands the caller the state the
+// reference left behind (mt_restore_after_raise).
 __global__ __launch_bounds__(256) void k_mt_shuffle_all(uint32_t* __restrict__ st, const int* __restrict__ n_ptr,
-                                                         int repeat, int group, int cap, int* __restrict__ perm_all) {
+                                                         int repeat, int group, int cap, int* __restrict__ perm_all,
+                                                         uint32_t* __restrict__ snap) {
     __shared__ uint32_t key[624], outw[624];
     __shared__ int s_pos, s_rep, s_i;
     extern __shared__ int s_dyn[];
     const int t = threadIdx.x;
     const int lane = t & 63;
     const int n = *n_ptr;
+    if (snap)
+        for (int i = t; i < 625; i += 256) snap[i] = st[i];
     if (n <= 1) {  // nothing is drawn
         if (t == 0 && n == 1)
             for (int r = 0; r < repeat; ++r) perm_all[(size_t)r * cap] = 0;
+        if (snap)
+            for (int r = 1; r <= repeat; ++r)
+                for (int i = t; i < 625; i += 256) snap[(size_t)r * MT_SNAP_STRIDE + i] = st[i];
         return;
     }
     int* p = s_dyn;                                                      // [group][n]
@@ -909,6 +918,11 @@ __global__ __launch_bounds__(256) void k_mt_shuffle_all(uint32_t* __restrict__ s
                     if (i == 0) {
                         ++rep;
                         i = n - 1;
+                        if (snap) {  // (wave-uniform branch) the state behind this repeat's shuffle
+                            uint32_t* d = snap + (size_t)rep * MT_SNAP_STRIDE;
+                            for (int k = lane; k < 624; k += 64) d[k] = key[k];
+                            if (lane == 0) d[624] = (uint32_t)pos;
+                        }
                     }
                 }
                 if (lane == 0) {
@@ -1247,6 +1261,26 @@ __global__ void k_pose_finish(PoseState* ps, const double* __restrict__ rp_out, 
     }
 }
 
+// Where the REFERENCE raises inside its repeat loop, the device answers with a fixed contract (include/dfvo_hip.h): identity /
+// zero pose, no valid repeat, the all-ones inlier mask, and the RandomState the reference left behind: `shuffles` draws
+// after the call's start (0: findHomography found nothing under GRIC validity, homography_residual(None) raises before the
+// loop; rep + 1: findEssentialMat returned None in repeat `rep`).  Called by every thread of the one-block bookkeeping kernel.
+__device__ void pose_after_raise(PoseState* ps, int shuffles, uint32_t* __restrict__ mt_state, const uint32_t* __restrict__ snap,
+                                 uint8_t* __restrict__ best_inliers, int repeat) {
+    const int n = ps->n;
+    __syncthreads();
+    if (mt_state && snap)
+        for (int i = threadIdx.x; i < 625; i += blockDim.x) mt_state[i] = snap[(size_t)shuffles * MT_SNAP_STRIDE + i];
+    for (int c = threadIdx.x; c < n; c += blockDim.x) best_inliers[c] = 1;
+    if (threadIdx.x == 0) {
+        ps->best_cnt = 0;
+        ps->num_valid = 0;
+        ps->have_best = 0;
+        ps->major_valid = 0;
+        for (int k = 0; k < repeat; k++) ps->rep_valid[k] = 0;
+    }
+}
+
 // the whole post-RANSAC bookkeeping of compute_pose_2d2d in one launch: H validity (k_set_h_gric), the `repeat`
 // sequential k_rep_update steps, and the major_valid decision (k_pose_finish stage 0)
 struct RepBatch {
@@ -1258,13 +1292,18 @@ __global__ __launch_bounds__(256) void k_rep_update_all(PoseState* ps, const Ran
                                                          const RepBatch B, const double* __restrict__ e_gric,
                                                          const int* __restrict__ perm, int perm_stride,
                                                          uint8_t* __restrict__ best_inliers, int repeat,
-                                                         int by_ratio, double ratio_thre) {
+                                                         int by_ratio, double ratio_thre, uint32_t* __restrict__ mt_state,
+                                                         const uint32_t* __restrict__ snap) {
     // by_ratio (validity.method 'homo_ratio', E_tracker.py:186-194,243-250): a repeat is valid while
     // H_inliers.sum() / (H_inliers.sum() + inliers.sum()) < thre (0 / 0 = nan compares false, like numpy);
     // h_gric then carries the homography's inlier count and rep_gric[] the ratios
-    __shared__ int s_take;
+    __shared__ int s_take, s_raise;
     const int n = ps->n;
     if (threadIdx.x == 0) {
+        s_raise = -1;
+        if (!by_ratio && !hst->found) s_raise = 0;
+        for (int rep = 0; rep < repeat && s_raise < 0; ++rep)
+            if (!B.st[rep]->found) s_raise = rep + 1;
         ps->h_found = hst->found;
         if (by_ratio)
             ps->h_gric = hst->found ? (double)hst->max_good : 0.0;  // no model: OpenCV returns an all-zero mask
@@ -1307,6 +1346,7 @@ __global__ __launch_bounds__(256) void k_rep_update_all(PoseState* ps, const Ran
     }
     if (threadIdx.x == 0)
         ps->major_valid = ((double)ps->num_valid > (double)repeat / 2.0 && ps->have_best) ? 1 : 0;
+    if (s_raise >= 0) pose_after_raise(ps, s_raise, mt_state, snap, best_inliers, repeat);
 }
 
 // ---- e_tracker.validity.method == "flow" (ablation_model_sel_flow.yml) ------------------------------------------
@@ -1323,7 +1363,7 @@ __global__ __launch_bounds__(256) void k_flow_gate(const int* __restrict__ kp_in
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double avg = sm::np_pairwise_sum(norms, n) / (double)n;  // n == 0: nan, compares false like numpy's
+        const double avg = sm::np_add_reduce(norms, n) / (double)n;  // n == 0: nan, compares false like numpy's
         *avg_out = avg;
         const int open = avg > thre ? 1 : 0;
         gate[0] = open ? n : 0;
@@ -1338,11 +1378,15 @@ __global__ void k_copy_double(double* __restrict__ dst, const double* __restrict
 __global__ __launch_bounds__(256) void k_rep_update_flow(PoseState* ps, const int* __restrict__ gate, const double* __restrict__ avg_flow,
                                                           const RepBatch B, const double* __restrict__ cheir,
                                                           const int* __restrict__ perm, int perm_stride,
-                                                          uint8_t* __restrict__ best_inliers, int repeat) {
-    __shared__ int s_take;
+                                                          uint8_t* __restrict__ best_inliers, int repeat,
+                                                          uint32_t* __restrict__ mt_state, const uint32_t* __restrict__ snap) {
+    __shared__ int s_take, s_raise;
     const int n = ps->n;
     const int open = gate[1];
     if (threadIdx.x == 0) {
+        s_raise = -1;  // recoverPose(None, ...) raises in the repeat whose findEssentialMat found nothing
+        for (int rep = 0; open && rep < repeat && s_raise < 0; ++rep)
+            if (!B.st[rep]->found) s_raise = rep + 1;
         ps->h_found = 0;
         ps->h_gric = *avg_flow;
     }
@@ -1375,6 +1419,7 @@ __global__ __launch_bounds__(256) void k_rep_update_flow(PoseState* ps, const in
     }
     if (threadIdx.x == 0)
         ps->major_valid = ((double)ps->num_valid > (double)repeat / 2.0 && ps->have_best) ? 1 : 0;
+    if (s_raise >= 0) pose_after_raise(ps, s_raise, mt_state, snap, best_inliers, repeat);
 }
 
 // ================================================================================================
@@ -1647,7 +1692,7 @@ void TrackerBuffers::release_kp() {
 }
 
 int TrackerBuffers::init(hipStream_t rep0, hipStream_t rep1) {
-    DFVO_HIP_CHECK(hipMalloc((void**)&mt_state, sizeof(uint32_t) * 640));
+    DFVO_HIP_CHECK(hipMalloc((void**)&mt_state, sizeof(uint32_t) * MT_SNAP_STRIDE * (MAX_REP + 2)));  // the state + its snapshots (mt_snapshots)
     DFVO_HIP_CHECK(hipMalloc((void**)&kp_info, sizeof(int) * 8));
     DFVO_HIP_CHECK(hipMalloc((void**)&kp_total, sizeof(int) * (8 + 64 + 2)));  // [0..7] counters (5, 6: the flow gate), [8..71] k_kp_cell's partial counts, [72..73] the five-point sampler's state behind its prefetched subsets
     DFVO_HIP_CHECK(hipMalloc((void**)&pose, sizeof(PoseState)));
@@ -1761,14 +1806,14 @@ int enqueue_mt_seed(TrackerBuffers& tb, uint32_t seed, hipStream_t s) {
 // `repeat` x (perm = np.arange(n); np.random.shuffle(perm)) from the device-resident numpy stream `mt_state`;
 // n = *d_n on the device (n_host bounds it), perm[r * perm_stride + i]
 int enqueue_mt_shuffle(uint32_t* mt_state, const int* d_n, int n_host, int repeat, int perm_stride, int* perm,
-                       hipStream_t s) {
+                       hipStream_t s, uint32_t* snap) {
     const size_t per_rep = 6 * (size_t)(n_host > 0 ? n_host : 1);  // int permutation + uint16 draw list
     DFVO_ARG_CHECK(per_rep <= 144 * 1024, "shuffle: too many keypoints for the LDS permutation buffer");
     int group = (int)((144 * 1024) / per_rep);
     if (group > repeat) group = repeat;
     const size_t perm_lds = per_rep * group + 16;
     if (int rc_lds = ensure_dyn_lds((const void*)k_mt_shuffle_all, perm_lds)) return rc_lds;
-    hipLaunchKernelGGL(k_mt_shuffle_all, dim3(1), dim3(256), perm_lds, s, mt_state, d_n, repeat, group, perm_stride, perm);
+    hipLaunchKernelGGL(k_mt_shuffle_all, dim3(1), dim3(256), perm_lds, s, mt_state, d_n, repeat, group, perm_stride, perm, snap);
     DFVO_HIP_CHECK(hipGetLastError());
     return DFVO_OK;
 }
@@ -1868,7 +1913,7 @@ int enqueue_pose_e_part(TrackerBuffers& tb, int n_host, const PoseConfig& cfg, h
         DFVO_HIP_CHECK(hipStreamWaitEvent(sr, by_flow ? tb.ev_h : tb.ev_start, 0));
         if (tb.ev_t[0]) DFVO_HIP_CHECK(hipEventRecord(tb.ev_t[0], sr));
         if (tb.mark(3, sr) != DFVO_OK) return DFVO_ERR_HIP;
-        int rc = enqueue_mt_shuffle(tb.mt_state, d_n, n_host, cfg.repeat, cap + 8, tb.perm, sr);
+        int rc = enqueue_mt_shuffle(tb.mt_state, d_n, n_host, cfg.repeat, cap + 8, tb.perm, sr, mt_snapshots(tb.mt_state));
         if (rc != DFVO_OK) return rc;
         hipLaunchKernelGGL(k_permute_points, dim3(nb, R), dim3(256), 0, sr, d_n, tb.perm, cap + 8, tb.kp_cur,
                            tb.kp_ref, tb.pa, tb.pb, 2 * cap);
@@ -1912,11 +1957,12 @@ int enqueue_pose_e_part(TrackerBuffers& tb, int n_host, const PoseConfig& cfg, h
             }
             if (by_flow)
                 hipLaunchKernelGGL(k_rep_update_flow, dim3(1), dim3(256), 0, s, tb.pose, tb.kp_total + 5, tb.small + 18, RB,
-                                   tb.small + 19, tb.perm, cap + 8, tb.best_inliers, cfg.repeat);
+                                   tb.small + 19, tb.perm, cap + 8, tb.best_inliers, cfg.repeat, tb.mt_state,
+                                   mt_snapshots(tb.mt_state));
             else
                 hipLaunchKernelGGL(k_rep_update_all, dim3(1), dim3(256), 0, s, tb.pose, tb.ws_h.state, tb.small + 18, RB,
                                    tb.small + 19, tb.perm, cap + 8, tb.best_inliers, cfg.repeat, by_ratio ? 1 : 0,
-                                   cfg.validity_thre);
+                                   cfg.validity_thre, tb.mt_state, mt_snapshots(tb.mt_state));
         }
         if (tb.mark(6, s) != DFVO_OK) return DFVO_ERR_HIP;
         // recoverPose(best_E, kp_cur, kp_ref): always enqueued, consumed only when major_valid; its last kernel also

@@ -292,7 +292,26 @@ __global__ void k_e_replay(const EBatch B, int it0, int it1, int count, double c
     ransac_replay(R.state, R.nmodels, R.counts, 10, it0, it1, count, 5, confidence);
 }
 
-__global__ void k_e_mask(const EBatch B, int n, float thr2) {
+// count == modelPoints (RANSACPointSetRegistrator::run, ptsetreg.cpp): nothing is drawn, the kernel runs once on the points
+// in their order (k_e_all_points writes that subset, stage 1 / polynomial / stage 3 run on it as on any other), its FIRST
+// model is accepted without scoring and every point is an inlier (k_e_mask all_inliers); no model: not found
+__global__ void k_e_all_points(const EBatch B) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    for (int i = 0; i < 5; i++) B.idx[i] = i;
+}
+__global__ void k_e_accept_first(const EBatch B) {
+    if (threadIdx.x != 0) return;
+    const ERep& R = B.r[blockIdx.x];
+    RansacState* st = R.state;
+    const int found = R.nmodels[0] > 0 ? 1 : 0;
+    st->found = found;
+    st->done = 1;
+    st->best_iter = found ? 0 : -1;
+    st->best_model = found ? 0 : -1;
+    st->max_good = found ? 5 : 0;
+}
+
+__global__ void k_e_mask(const EBatch B, int n, float thr2, int all_inliers) {
     const ERep& R = B.r[blockIdx.y];
     const RansacState* st = R.state;
     const double* models = R.models;
@@ -308,7 +327,7 @@ __global__ void k_e_mask(const EBatch B, int n, float thr2) {
     if (i < 9) E_out[i] = E[i];
     if (i >= n) return;
     const float e = sm::essential_error(E, p1[i * 2], p1[i * 2 + 1], p2[i * 2], p2[i * 2 + 1]);
-    mask[i] = e <= thr2 ? 1 : 0;
+    mask[i] = (all_inliers || e <= thr2) ? 1 : 0;
 }
 
 int RansacWorkspace::ensure(int n, int max_iters) {
@@ -384,9 +403,12 @@ int enqueue_find_essential_batch(RansacWorkspace* w, const double* const* d_pts1
     const float thr2 = (float)(threshold * threshold);
     const unsigned R = (unsigned)nrep;
     hipLaunchKernelGGL(k_e_init_normalise, dim3(cdiv(n > 0 ? n : 1, 256), R), dim3(256), 0, s, B, n, max_iters, a, bx, by, rng_pre);
-    if (n >= 5) {  // count < modelPoints: no model (state->found stays 0)
-        // count == modelPoints would run the kernel once on all points; DF-VO never gets there (N >= 10
-        // is required upstream), treat it through the generic loop with the single possible subset order.
+    if (n == 5) {  // count == modelPoints: one kernel run on the points as they are (validity 'flow' / 'homo_ratio' get here)
+        hipLaunchKernelGGL(k_e_all_points, dim3(1), dim3(1), 0, s, B);
+        hipLaunchKernelGGL(k_e_stage1, dim3(1, R), dim3(E_STAGE1_LANES), 0, s, B, 0, 1);
+        hipLaunchKernelGGL(k_e_poly_stage3, dim3(1, R), dim3(64), 0, s, B, 0, 1);
+        hipLaunchKernelGGL(k_e_accept_first, dim3(R), dim3(1), 0, s, B);
+    } else if (n > 5) {  // count < modelPoints: no model (state->found stays 0)
         int cb[4];
         chunk_bounds(max_iters, cb);
         for (int c = 0; c < 3; ++c) {
@@ -402,7 +424,7 @@ int enqueue_find_essential_batch(RansacWorkspace* w, const double* const* d_pts1
             hipLaunchKernelGGL(k_e_replay, dim3(R), dim3(1), 0, s, B, it0, it1, n, prob);
         }
     }
-    hipLaunchKernelGGL(k_e_mask, dim3(cdiv(n > 9 ? n : 9, 256), R), dim3(256), 0, s, B, n, thr2);
+    hipLaunchKernelGGL(k_e_mask, dim3(cdiv(n > 9 ? n : 9, 256), R), dim3(256), 0, s, B, n, thr2, n == 5 ? 1 : 0);
     DFVO_HIP_CHECK(hipGetLastError());
     return DFVO_OK;
 }

@@ -52,6 +52,9 @@ struct ScaleConfig {
 };
 
 constexpr int MAX_REP = 8;
+// TrackerBuffers::mt_state holds the RandomState (624 key words + position) followed by MAX_REP + 1 snapshots of it
+constexpr int MT_SNAP_STRIDE = 640;
+inline uint32_t* mt_snapshots(uint32_t* mt_state) { return mt_state + MT_SNAP_STRIDE; }
 constexpr int NUM_REP_STREAMS = 4;  // side streams created per tracker; two are used (see TrackerBuffers::init)
 static inline int rep_stream_count() { return NUM_REP_STREAMS; }
 
@@ -195,8 +198,9 @@ int enqueue_compute_pose_2d2d(TrackerBuffers& tb, int n_host, const PoseConfig& 
 int enqueue_compose_trajectory(const double* d_rows, int n, const double* d_first, double* d_poses, int* d_bad, hipStream_t s);
 int enqueue_pose_h_part(TrackerBuffers& tb, int n_bound, const PoseConfig& cfg, hipStream_t sh);
 int enqueue_pose_e_part(TrackerBuffers& tb, int n_host, const PoseConfig& cfg, hipStream_t s, double* d_T21);
+// snap (optional): mt_snapshots(tb.mt_state) -- the state before the first and behind every shuffle
 int enqueue_mt_shuffle(uint32_t* mt_state, const int* d_n, int n_host, int repeat, int perm_stride, int* perm,
-                       hipStream_t s);
+                       hipStream_t s, uint32_t* snap = nullptr);
 // depth_per_kp: d_depth holds, per keypoint, the depth map's value at that keypoint's kp1 pixel (truncated, negative indices
 // wrapped as numpy does) -- [n_host] doubles instead of the H x W map
 int enqueue_compute_pose_3d2d(PnpBuffers& pb, uint32_t* mt_state, const double* d_kp1, const double* d_kp2,

@@ -327,7 +327,14 @@ int dfvo_kp_rigid_flow(dfvo_tracker* trk, const float* h_flow, const float* h_fl
  * DFVO_VALIDITY_HOMO_RATIO (E_tracker.py:186-194,243-250): findHomography with ransacReprojThreshold 0.2; a repeat is
  * valid while H_inliers.sum() / (H_inliers.sum() + inliers.sum()) < validity_thre (out: h_gric = the homography's
  * inlier count, rep_gric[] = the ratios; fewer than 5 keypoints, where the reference raises: identity).
- * Consumes the tracker's RandomState for the shuffles. */
+ * Consumes the tracker's RandomState for the shuffles.
+ * Where the reference raises inside the call, the answer is: R = identity, t = 0, major_valid = 0, every rep_valid[] = 0,
+ * cheirality = 0, h_inliers all ones, and the RandomState advanced by exactly the shuffles the reference drew before it
+ * raised.  That is (a) GRIC validity with more than 10 keypoints and no homography found (h_found = 0;
+ * homography_residual(None) raises before the repeat loop): no shuffle; (b) any validity method, findEssentialMat
+ * returning None in repeat r (`inv(K.T) @ None`, `None.sum()`, recoverPose(None); e.g. two views equal bit for bit):
+ * r + 1 shuffles.  rep_inliers[] / rep_gric[] still report what the device computed for every repeat.
+ * findEssentialMat with exactly 5 points is OpenCV's single kernel run: first model, all five points inliers. */
 #define DFVO_VALIDITY_GRIC 0
 #define DFVO_VALIDITY_FLOW 1
 #define DFVO_VALIDITY_HOMO_RATIO 2

@@ -64,6 +64,10 @@ def lib():
     l.cv3_rng_init.argtypes = [C.POINTER(C.c_uint64), C.c_uint64]
     l.cv3_rng_uniform_int.restype = C.c_int
     l.cv3_rng_uniform_int.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int]
+    l.cv3_ransac_last_stats.restype = None
+    l.cv3_ransac_last_stats.argtypes = [C.POINTER(C.c_longlong), _i32p]
+    l.cv3_pnp_planar_count.restype = C.c_int
+    l.cv3_pnp_planar_count.argtypes = []
     if hasattr(l, "cv3_solve_pnp_ransac"):
         l.cv3_solve_pnp_ransac.restype = C.c_int
         l.cv3_solve_pnp_ransac.argtypes = [_dp, _dp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, _dp, _dp, _i32p,
@@ -81,6 +85,23 @@ def _pts(a):
     return a
 
 
+def ransac_stats():
+    """diagnostics of the LAST RANSAC run of the C oracle (findEssentialMat / findHomography / solvePnPRansac): dict(iters,
+    subset_failed, ties, attempts, best_iter, best_model, max_good, subsets [k, model points] -- the point indices of the
+    first 64 subsets the sampler accepted, in drawing order)"""
+    out = (C.c_longlong * 9)()
+    sub = np.zeros(64 * 8, np.int32)
+    lib().cv3_ransac_last_stats(out, sub)
+    k, mp = int(out[4]), int(out[5])
+    return dict(iters=int(out[0]), subset_failed=int(out[1]), ties=int(out[2]), attempts=int(out[3]), best_iter=int(out[6]),
+                best_model=int(out[7]), max_good=int(out[8]), subsets=sub[:k * mp].reshape(k, mp).copy() if mp else sub[:0])
+
+
+def pnp_planar_count():
+    """number of planar (homography) initialisations cvFindExtrinsicCameraParams2's restatement has taken so far"""
+    return int(lib().cv3_pnp_planar_count())
+
+
 def findEssentialMat(points1, points2, focal=1.0, pp=(0., 0.), method=RANSAC, prob=0.999, threshold=1.0,
                      mask=None, maxIters=1000, _stats=None):
     assert method == RANSAC
@@ -93,6 +114,8 @@ def findEssentialMat(points1, points2, focal=1.0, pp=(0., 0.), method=RANSAC, pr
                                          float(threshold), int(maxIters), E, m, C.byref(it), C.byref(bi), C.byref(bm))
     if _stats is not None:
         _stats.update(iters=it.value, best_iter=bi.value, best_model=bm.value)
+        if n >= 5:
+            _stats.update({k: v for k, v in ransac_stats().items() if k in ("subset_failed", "ties", "attempts", "subsets")})
     if not ok:
         return None, None
     return E.reshape(3, 3), m[:n].reshape(n, 1)
@@ -110,13 +133,15 @@ def recoverPose(E, points1, points2, focal=1.0, pp=(0., 0.), mask=None):
 
 
 def findHomography(srcPoints, dstPoints, method=0, ransacReprojThreshold=3.0, mask=None, maxIters=2000,
-                   confidence=0.995):
+                   confidence=0.995, _stats=None):
     assert method == RANSAC
     p1, p2 = _pts(srcPoints), _pts(dstPoints)
     n = p1.shape[0]
     H = np.zeros(9)
     m = np.zeros(max(n, 1), np.uint8)
     ok = lib().cv3_find_homography(p1, p2, n, float(ransacReprojThreshold), int(maxIters), float(confidence), H, m)
+    if _stats is not None and n > 4:
+        _stats.update(ransac_stats())
     if not ok:
         return None, m[:n].reshape(n, 1)
     return H.reshape(3, 3), m[:n].reshape(n, 1)

@@ -25,6 +25,30 @@ int cv3_ransac_update_num_iters(double p, double ep, int modelPoints, int maxIte
     return denom >= 0 || -num >= maxIters * (-denom) ? maxIters : cv3_round(num / denom);
 }
 
+/* Diagnostics of the LAST cv3_ransac_run (read by the tests through cv3_ransac_last_stats; nothing here feeds back into a
+ * result): iterations run, whether getSubset gave up, sampler attempts summed over the run (one per drawn subset,
+ * rejected ones included), later hypotheses that only TIED the best inlier count ("first wins"), the winning iteration /
+ * model / inlier count, and the point indices of the first CV3_TRACE_SUBSETS accepted subsets. */
+#define CV3_TRACE_SUBSETS 64
+static struct {
+    int iters, subset_failed, ties, model_points, nsub, best_iter, best_model, max_good;
+    long long attempts;
+    int sub[CV3_TRACE_SUBSETS * 8];
+} g_last;
+
+void cv3_ransac_last_stats(long long* out9, int* subsets) {
+    out9[0] = g_last.iters;
+    out9[1] = g_last.subset_failed;
+    out9[2] = g_last.ties;
+    out9[3] = g_last.attempts;
+    out9[4] = g_last.nsub;
+    out9[5] = g_last.model_points;
+    out9[6] = g_last.best_iter;
+    out9[7] = g_last.best_model;
+    out9[8] = g_last.max_good;
+    if (subsets) memcpy(subsets, g_last.sub, sizeof(int) * (size_t)g_last.nsub * (size_t)g_last.model_points);
+}
+
 static int ransac_get_subset(const cv3_ransac_cb* cb, const char* m1, const char* m2, int count, char* ms1, char* ms2,
                              cv3_rng* rng, int maxAttempts) {
     int idx[16];
@@ -45,6 +69,11 @@ static int ransac_get_subset(const cv3_ransac_cb* cb, const char* m1, const char
         }
         if (i == modelPoints && cb->check_subset && !cb->check_subset(cb->ctx, ms1, ms2, i)) continue;
         break;
+    }
+    g_last.attempts += iters < maxAttempts ? iters + 1 : maxAttempts;
+    if (i == modelPoints && iters < maxAttempts && g_last.nsub < CV3_TRACE_SUBSETS && modelPoints <= 8) {
+        memcpy(g_last.sub + g_last.nsub * modelPoints, idx, sizeof(int) * (size_t)modelPoints);
+        g_last.nsub++;
     }
     return i == modelPoints && iters < maxAttempts;
 }
@@ -72,6 +101,9 @@ int cv3_ransac_run(const cv3_ransac_cb* cb, const void* m1, const void* m2, int 
     cv3_rng rng;
     cv3_rng_init(&rng, (uint64_t)-1);
     if (stats) stats[0] = stats[1] = stats[2] = -1;
+    memset(&g_last, 0, sizeof(g_last));
+    g_last.iters = g_last.best_iter = g_last.best_model = -1;
+    g_last.model_points = modelPoints;
     if (count < modelPoints) return 0;
     double models[10 * 16];
     double* bestModel = (double*)malloc(sizeof(double) * (size_t)cb->model_size);
@@ -97,6 +129,7 @@ int cv3_ransac_run(const cv3_ransac_cb* cb, const void* m1, const void* m2, int 
         int found = ransac_get_subset(cb, (const char*)m1, (const char*)m2, count, ms1, ms2, &rng, 10000);
         if (!found) {
             if (iter == 0) early = 1;
+            g_last.subset_failed = 1;
             break;
         }
         nmodels = cb->run_kernel(cb->ctx, ms1, ms2, modelPoints, models);
@@ -104,12 +137,16 @@ int cv3_ransac_run(const cv3_ransac_cb* cb, const void* m1, const void* m2, int 
         for (i = 0; i < nmodels; i++) {
             const double* model_i = models + (size_t)i * cb->model_size;
             int goodCount = ransac_find_inliers(cb, m1, m2, count, model_i, err, mask, threshold);
+            if (goodCount == maxGoodCount && goodCount > modelPoints - 1) g_last.ties++;
             if (goodCount > (maxGoodCount > modelPoints - 1 ? maxGoodCount : modelPoints - 1)) {
                 unsigned char* t = mask;
                 mask = bestMask;
                 bestMask = t;
                 memcpy(bestModel, model_i, sizeof(double) * (size_t)cb->model_size);
                 maxGoodCount = goodCount;
+                g_last.best_iter = iter;
+                g_last.best_model = i;
+                g_last.max_good = goodCount;
                 niters = cv3_ransac_update_num_iters(confidence, (double)(count - goodCount) / count, modelPoints, niters);
                 if (stats) {
                     stats[1] = iter;
@@ -119,6 +156,7 @@ int cv3_ransac_run(const cv3_ransac_cb* cb, const void* m1, const void* m2, int 
         }
     }
     if (stats) stats[0] = iter;
+    g_last.iters = iter;
     if (!early && maxGoodCount > 0) {
         memcpy(mask_out, bestMask, (size_t)count);
         memcpy(model_out, bestModel, sizeof(double) * (size_t)cb->model_size);
@@ -807,6 +845,13 @@ int cv3_find_homography_lsq(const double* pts1, const double* pts2, int n, doubl
     free(dst);
     return ok;
 }
+
+/* the RANSAC callbacks of findEssentialMat / findHomography on their own (the host-lane tests compare the per-lane device
+ * functions with them subset by subset): float points [count][2] for the homography, K-normalised doubles for E */
+int cv3_homography_kernel(const float* M, const float* m, int count, double* H) { return h_run_kernel(NULL, M, m, count, H); }
+int cv3_homography_check_subset(const float* M, const float* m, int count) { return h_check_subset(NULL, M, m, count); }
+void cv3_homography_error(const float* M, const float* m, int n, const double* H, float* err) { h_compute_error(NULL, M, m, n, H, err); }
+void cv3_essential_error(const double* x1, const double* x2, int n, const double* E, float* err) { em_compute_error(NULL, x1, x2, n, E, err); }
 
 int cv3_find_homography(const double* pts1, const double* pts2, int n, double ransac_thr, int max_iters,
                         double confidence, double* H, unsigned char* mask) {

@@ -19,6 +19,12 @@ typedef struct {
     const void* ctx;
 } cv3_ransac_cb;
 
+/* diagnostics of the last cv3_ransac_run: out9 = {iterations, getSubset gave up, tied hypotheses, sampler attempts, traced
+ * subsets, model points, winning iteration, winning model, best inlier count}; subsets (optional) [traced][model points] */
+void cv3_ransac_last_stats(long long* out9, int* subsets);
+/* how many times cv3_find_extrinsic_guess has taken the planar (homography) initialisation since the library was loaded */
+int cv3_pnp_planar_count(void);
+
 /* RANSACPointSetRegistrator::run; returns 1 on success.  stats (optional): [0] iterations run,
  * [1] winning iteration, [2] winning model index */
 int cv3_ransac_run(const cv3_ransac_cb* cb, const void* m1, const void* m2, int count, double threshold,

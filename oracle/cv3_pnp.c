@@ -848,6 +848,9 @@ int cv3_find_extrinsic(const double* M, const double* m, int n, const double* K,
  * orthonormalised by a Rodrigues round trip, t = H T_transform + h3 * 2 / (|h1| + |h2|), R = H R_transform.
  * `planar_guess` is kept for callers that want the old behaviour (start the LM from a given rvec | tvec instead); NULL
  * = OpenCV's initialisation. */
+static int g_planar_count = 0; /* diagnostics only */
+int cv3_pnp_planar_count(void) { return g_planar_count; }
+
 int cv3_find_extrinsic_guess(const double* M, const double* m, int n, const double* K, const double* planar_guess,
                              double* rvec, double* tvec, int* stats) {
     const double fx = K[0], fy = K[4], cx = K[2], cy = K[5], ifx = 1. / fx, ify = 1. / fy;
@@ -868,6 +871,7 @@ int cv3_find_extrinsic_guess(const double* M, const double* m, int n, const doub
     double param[6];
     const int planar = W[2] / W[1] < 1e-3 || n < 4;
     if (planar && !planar_guess) {
+        g_planar_count++;
         /* R_transform = matV (CV_SVD_V_T: rows are the right singular vectors) */
         double Rt[9];
         memcpy(Rt, V, sizeof(Rt));

@@ -78,3 +78,21 @@ def variant_case(tag):
     ok = (ix >= 0) & (ix < w) & (iy >= 0) & (iy < h)
     depth[iy[ok], ix[ok]] = zs[ok]
     return dict(seed=seed, kp_ref=kp_ref, kp_cur=kp_cur, K=c["K"], depth_cur=depth)
+
+
+def pose_world_branches():
+    """the branch signature of the oracle on every case of tests/pose_world.py (recorded results only): {case id: signature}"""
+    import pose_world as PW
+    return {case[0]: PW.signature(case) for case in PW.CASES}
+
+
+def write_pose_world_branches(path=None):
+    """regenerates tests/golden/pose_world_branches.json (python -c "import make_golden_cases as m; m.write_pose_world_branches()"
+    with tests/ and tests/golden/ on sys.path); tests/test_pose_world_cpu.py asserts that the committed file equals it"""
+    import json
+    import os
+    path = path or os.path.join(os.path.dirname(os.path.abspath(__file__)), "pose_world_branches.json")
+    with open(path, "w") as f:
+        json.dump(pose_world_branches(), f, indent=0, sort_keys=True)
+        f.write("\n")
+    return path

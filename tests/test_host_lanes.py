@@ -188,6 +188,24 @@ def test_pairwise_sum_lane_matches_numpy(hh):
         assert got == want, (n, got, want)
 
 
+def test_add_reduce_lane_matches_numpy_above_the_buffer_size(hh):
+    """np.mean / np.add.reduce above np.getbufsize() = 8192 elements: numpy adds the pairwise sums of 8192-element blocks
+    one after the other, which one pairwise sum over the whole array does not reproduce (values of one magnitude, where
+    every rounding shows: keypoint displacements).  sm::np_add_reduce is what k_flow_gate averages with."""
+    hh.hh_np_add_reduce.restype = C.c_double
+    hh.hh_np_pairwise_sum.restype = C.c_double
+    one_sum_differs = 0
+    for seed in range(6):
+        rng = np.random.default_rng(100 + seed)
+        for n in (0, 5, 128, 2000, 8191, 8192, 8193, 10000, 16384, 16385, 20000, 24576, 30001):
+            a = np.ascontiguousarray(np.abs(rng.standard_normal(n)) * 180.0)
+            want = float(np.add.reduce(a)) if n else 0.0
+            assert hh.hh_np_add_reduce(_p(a), n) == want, (seed, n)
+            assert n == 0 or hh.hh_np_add_reduce(_p(a), n) / n == float(np.mean(a)), (seed, n)
+            one_sum_differs += hh.hh_np_pairwise_sum(_p(a), n) != want
+    assert one_sum_differs, "the inputs do not tell the block-wise reduction from a single pairwise sum"
+
+
 def test_rigid_flow_lane_matches_oracle(hh):
     """the per-pixel RigidFlow arithmetic of k_rigid_flow_diff (float32, fused multiply-add order of the fixture's GEMM)
     against the oracle restatement, which tests/test_oracle_tracker.py pins to the reference's own layers"""
@@ -284,3 +302,104 @@ def test_register_resident_jacobi_schedule_is_bit_exact(hh):
             assert np.array_equal(x.view(np.uint64), y.view(np.uint64)), "lock-step schedule differs from the sequential Jacobi"
         checked += 1
     assert checked > 1900
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the motion / scene / coordinate matrix of tests/pose_world.py through the host build, before any of it goes to a GPU
+# ------------------------------------------------------------------------------------------------------------------
+import pose_world as PW  # noqa: E402
+
+
+def _normalised(pts, K):
+    """normalise_points of oracle/cv3_calib3d.c = k_e_init_normalise: p * (1 / f) + (-c * (1 / f))"""
+    a = 1.0 / K[0, 0]
+    return np.ascontiguousarray(pts * a + np.array([-K[0, 2] * a, -K[1, 2] * a]))
+
+
+@pytest.mark.parametrize("case", PW.CASES, ids=PW.CASE_IDS)
+def test_pose_world_subsets_through_the_host_lanes(hh, cv3, case):
+    """For every case of the matrix: the first 64 five-point and the first 64 four-point subsets the oracle's samplers
+    draw go through the host build of the per-lane device functions, every bit (NaN payloads included) against the C
+    oracle -- five_point, homography_kernel / homography_check_subset, the two error functions on ALL points for the
+    first model, decompose_essential and triangulate_point on the oracle's winning E.  Every numeric loop of these
+    functions is bounded (300 solvePoly sweeps, capped Jacobi sweeps): returning at all on every input of the matrix,
+    the non-finite, collinear and identical-point sets included, is the termination check the GPU tests rely on."""
+    hh.hh_essential_error.restype = C.c_float
+    hh.hh_essential_error.argtypes = [_dp] + [C.c_double] * 4
+    hh.hh_homography_error.restype = C.c_float
+    hh.hh_homography_error.argtypes = [_dp] + [C.c_float] * 4
+    hh.hh_triangulate_point.argtypes = [_dp, _dp] + [C.c_double] * 4 + [_dp]
+    c = PW.build(case)
+    K, n = c["K"], c["kp_ref"].shape[0]
+    es, hs = {}, {}
+    with np.errstate(all="ignore"):
+        E, em = cv2_shim.findEssentialMat(c["kp_cur"], c["kp_ref"], focal=K[0, 0], pp=(K[0, 2], K[1, 2]), method=cv2_shim.RANSAC,
+                                          prob=0.99, threshold=0.2, _stats=es)
+        H, hm = cv2_shim.findHomography(c["kp_cur"], c["kp_ref"], method=cv2_shim.RANSAC, confidence=0.99, ransacReprojThreshold=1,
+                                        _stats=hs)
+    x1, x2 = _normalised(c["kp_cur"], K), _normalised(c["kp_ref"], K)
+    f1, f2 = np.ascontiguousarray(c["kp_cur"], np.float32), np.ascontiguousarray(c["kp_ref"], np.float32)
+    # ---- five-point subsets
+    first_E, checked = None, 0
+    for idx in es.get("subsets", ()):
+        q1, q2 = np.ascontiguousarray(x1[idx]), np.ascontiguousarray(x2[idx])
+        e_h, e_o = np.zeros(90), np.zeros(90)
+        n_h = hh.hh_five_point(_p(q1), _p(q2), _p(e_h))
+        n_o = cv3.cv3_five_point(_p(q1), _p(q2), _p(e_o))
+        assert n_h == n_o, (case[0], idx.tolist())
+        assert np.array_equal(e_h[:9 * n_h].view(np.uint64), e_o[:9 * n_o].view(np.uint64)), (case[0], idx.tolist())
+        checked += 1
+        if first_E is None and n_o:
+            first_E = e_o[:9].copy()
+    if n > 5:
+        assert checked == min(64, es["iters"]), "the oracle did not hand over the subsets it drew"
+    if first_E is not None:  # the error of every point under the first model
+        err_o = np.zeros(n, np.float32)
+        cv3.cv3_essential_error(_p(x1), _p(x2), n, _p(first_E), _p(err_o, C.c_float))
+        err_h = np.array([hh.hh_essential_error(_p(first_E), x1[i, 0], x1[i, 1], x2[i, 0], x2[i, 1]) for i in range(min(n, 2000))],
+                         np.float32)
+        assert np.array_equal(err_h.view(np.uint32), err_o[:len(err_h)].view(np.uint32)), case[0]
+    # ---- four-point subsets (the sampler hands over only subsets that passed checkSubset; rejected ones are checked below)
+    first_H = None
+    for idx in hs.get("subsets", ()):
+        M, m = np.ascontiguousarray(f1[idx]), np.ascontiguousarray(f2[idx])
+        assert hh.hh_homography_check_subset(_p(M, C.c_float), _p(m, C.c_float)) == 1 == \
+            cv3.cv3_homography_check_subset(_p(M, C.c_float), _p(m, C.c_float), 4), (case[0], idx.tolist())
+        h_h, h_o = np.zeros(9), np.zeros(9)
+        ok_h = hh.hh_homography_kernel(_p(M, C.c_float), _p(m, C.c_float), 4, _p(h_h))
+        ok_o = cv3.cv3_homography_kernel(_p(M, C.c_float), _p(m, C.c_float), 4, _p(h_o))
+        assert ok_h == ok_o, (case[0], idx.tolist())
+        if ok_o:
+            assert np.array_equal(h_h.view(np.uint64), h_o.view(np.uint64)), (case[0], idx.tolist())
+            if first_H is None:
+                first_H = h_o.copy()
+    rng = np.random.default_rng(case[5])
+    for _ in range(64):  # random subsets, rejected ones included: the two checkSubset restatements agree
+        idx = rng.choice(n, 4, replace=False)
+        M, m = np.ascontiguousarray(f1[idx]), np.ascontiguousarray(f2[idx])
+        assert hh.hh_homography_check_subset(_p(M, C.c_float), _p(m, C.c_float)) == \
+            cv3.cv3_homography_check_subset(_p(M, C.c_float), _p(m, C.c_float), 4), (case[0], idx.tolist())
+    if first_H is not None:
+        err_o = np.zeros(n, np.float32)
+        cv3.cv3_homography_error(_p(f1, C.c_float), _p(f2, C.c_float), n, _p(first_H), _p(err_o, C.c_float))
+        err_h = np.array([hh.hh_homography_error(_p(first_H), f1[i, 0], f1[i, 1], f2[i, 0], f2[i, 1]) for i in range(min(n, 2000))],
+                         np.float32)
+        assert np.array_equal(err_h.view(np.uint32), err_o[:len(err_h)].view(np.uint32)), case[0]
+    # ---- the winning E: decomposition and the triangulation of the first points under [I|0], [R1|t]
+    if E is not None:
+        Ef = np.ascontiguousarray(E.reshape(9))
+        out_h = [np.zeros(9), np.zeros(9), np.zeros(3)]
+        out_o = [np.zeros(9), np.zeros(9), np.zeros(3)]
+        hh.hh_decompose_essential(_p(Ef), *[_p(o) for o in out_h])
+        cv3.cv3_decompose_essential_mat(_p(Ef), *[_p(o) for o in out_o])
+        for a, b in zip(out_h, out_o):
+            assert np.array_equal(a.view(np.uint64), b.view(np.uint64)), case[0]
+        P1 = np.ascontiguousarray(np.eye(4)[:3])
+        P2 = np.ascontiguousarray(np.c_[out_o[0].reshape(3, 3), out_o[2]])
+        k = min(n, 256)
+        with np.errstate(all="ignore"):
+            Xo = cv2_shim.triangulatePoints(P1, P2, np.ascontiguousarray(x1[:k].T), np.ascontiguousarray(x2[:k].T))
+        Xh = np.zeros((k, 4))
+        for i in range(k):
+            hh.hh_triangulate_point(_p(P1), _p(P2), x1[i, 0], x1[i, 1], x2[i, 0], x2[i, 1], _p(Xh[i]))
+        assert np.array_equal(np.ascontiguousarray(Xh.T).view(np.uint64), Xo.view(np.uint64)), case[0]

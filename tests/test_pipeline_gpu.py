@@ -211,3 +211,97 @@ def test_track_begin_refuses_a_second_pending_pair(gpu, pipe_mod):
     out1 = pipe.track_end(1)
     assert out0.status in (0, 3) and out1.status in (0, 3)
     pipe.close()
+
+
+# the motions a drive also produces (tests/pose_world.py has them for the stand-alone solver entries): standing still, turning
+# on the spot, driving sideways / backward.  rigid_scene divides by the rotation angle, so "no rotation" is handed to it as
+# a rotation of 1e-150 rad, under which no point moves by a bit (x + 1e-150 * y == x), and synthetic.py keeps its bytes.  "still-exact" additionally has no flow noise: on every reliable pixel the flow is exactly zero and
+# the two keypoint sets are equal bit for bit, where the reference's findEssentialMat returns None in some repeat and
+# compute_pose_2d2d raises; the pipeline then answers with the contract of include/dfvo_hip.h (identity, RandomState as
+# the reference left it) and goes on to the PnP fallback.
+_NO_ROT = (1e-150, 0.0, 0.0)
+PIPE_MOTIONS = {"still": (_NO_ROT, (0.0, 0.0, 0.0), 0.05), "still-exact": (_NO_ROT, (0.0, 0.0, 0.0), 0.0),
+                "pure_yaw": ((0.0, 0.05, 0.0), (0.0, 0.0, 0.0), 0.05), "sideways": ((0.001, 0.002, 0.0005), (0.6, 0.0, 0.02), 0.05),
+                "backward": ((0.002, -0.005, 0.001), (0.01, 0.0, -0.8), 0.05)}
+
+
+def motion_scene(h, w, motion, seed):
+    wv, tv, noise = PIPE_MOTIONS[motion]
+    sc = rigid_scene(h, w, seed=seed, T=(np.array(wv), np.array(tv)), noise_px=noise)
+    if motion.startswith("still"):
+        v = np.array([[-20.0, 3.0, 5.0], [1.65, -0.1, 80.0]]).T
+        assert np.array_equal(sc["R"] @ v, v)
+    if noise == 0.0:  # (K @ inv(K) leaves 1e-13 px of rounding: not a flow)
+        sc["flow"][np.abs(sc["flow"]) < 1e-6] = 0.0
+        assert (sc["flow"] == 0).mean() > 0.5
+    return sc
+
+
+@pytest.mark.parametrize("motion", list(PIPE_MOTIONS))
+@pytest.mark.parametrize("h,w", [(192, 640), (376, 1241)])
+def test_pipeline_tracker_matches_oracle_chain_over_motions(gpu, conv_precision, pipe_mod, h, w, motion):
+    """test_pipeline_tracker_matches_oracle_chain's body over the motions above, every pair through prefetch_track (the E-subset
+    prefetch with the point count read on the device), three pairs with the RandomState carried and compared after each."""
+    sc = motion_scene(h, w, motion, seed=7 + h)
+    K = sc["K"]
+    pipe = pipe_mod.TrackingPipeline(h, w, 192, 640, K, O.liteflownet_state_dict(4869), O.monodepth2_state_dict(4869),
+                                     seed=4869)
+    ref, cur = image_pair(h, w, seed=11)
+    feed, _ = image_pair(192, 640, seed=12)
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    dref, dcur, dfeed = d(ref), d(cur), d(feed)
+    dflow, ddiff, ddepth = d(sc["flow"]), d(sc["diff"]), d(sc["depth_cur"])
+    np.random.seed(4869)
+    pipe.set_ref_depth(depth=d(sc["depth_ref"]))
+    ref_depth = sc["depth_ref"]
+    statuses = []
+    for frame in range(3):
+        pipe.enqueue_nets(frame % 2, dref, dcur, dfeed)
+        pipe.prefetch_track(frame % 2, dflow, ddiff)
+        out = pipe.track(frame % 2, dflow, ddiff, ddepth)
+        statuses.append(out.status)
+        kp = T.local_bestN(sc["flow"], sc["diff"][..., None])
+        assert out.good_kp_found == int(kp["good_kp_found"])
+        if not kp["good_kp_found"]:
+            assert out.status == 1  # DFVO_TRACK_CONSTANT_MOTION
+            continue
+        assert out.n_kp == kp["kp1_best"].shape[1]
+        raised = None
+        try:
+            res = T.compute_pose_2d2d(kp["kp1_best"][0], kp["kp2_best"][0], K)
+        except (ValueError, AttributeError) as e:  # None E / None H in the reference: the contract of include/dfvo_hip.h
+            raised = type(e).__name__
+            res = {"R": np.eye(3), "t": np.zeros((3, 1)), "rep_inliers": [], "rep_valid": []}
+        R = np.array(out.R[:]).reshape(3, 3)
+        t = np.array(out.t[:]).reshape(3, 1)
+        if out.status == 0:
+            assert np.array_equal(R, res["R"]) and np.array_equal(t, res["t"]), "frame %d" % frame
+        pose = np.eye(4)
+        pose[:3, :3] = res["R"]
+        pose[:3, 3:] = res["t"]
+        diag = {"n_valid": -1}
+        s_ref = -1
+        if np.linalg.norm(res["t"]) != 0:
+            s_ref = T.find_scale_from_depth(kp["kp1_best"][0], kp["kp2_best"][0], np.linalg.inv(pose), sc["depth_cur"], K,
+                                            diag=diag)
+        print("%s %dx%d frame %d: status %d kp %d inliers %d | oracle %s reps %s valid %s | scale hip %.12g oracle %.12g (valid %d/%d)" % (
+            motion, h, w, frame, out.status, out.n_kp, out.best_inlier_cnt, "RAISES " + raised if raised else "ok",
+            res["rep_inliers"], [int(v) for v in res["rep_valid"]], out.scale, s_ref, out.scale_n_valid, diag["n_valid"]))
+        if np.linalg.norm(res["t"]) == 0 or s_ref == -1:
+            assert out.status == 3  # DFVO_TRACK_PNP
+            pnp = T.compute_pose_3d2d(kp["kp1_best"][0], kp["kp2_best"][0], ref_depth, K, 0.0, 50.0, 5, 100, 1.0)
+            assert out.pnp_n_filtered == len(pnp["kp1"]) and out.pnp_inliers == pnp["best_inlier"]
+            assert np.array_equal(np.array(out.R[:]).reshape(3, 3), pnp["R"])
+            assert np.array_equal(np.array(out.t[:]).reshape(3, 1), pnp["t"])
+            rel, mode = pipe.hybrid_pose(out, np.eye(4))
+            assert mode == "PnP" and np.abs(rel - pnp["pose"]).max() <= 1e-12
+        else:
+            assert out.status == 0
+            assert out.scale_n_valid == diag["n_valid"]
+            assert abs(out.scale - s_ref) <= 1e-9 * abs(s_ref)
+        ref_depth = sc["depth_cur"]
+        st, want = pipe.get_rng_state(), np.random.get_state()
+        assert np.array_equal(st[1], want[1]) and st[2] == want[2], "RandomState diverged after frame %d" % frame
+    pipe.close()
+    if motion in ("still", "still-exact", "pure_yaw"):
+        assert 3 in statuses, "a pair without parallax must end in the PnP fallback"
