@@ -18,7 +18,7 @@
 // offset) of the four k-groups of a step come from a table built once per layer on the host and read through the scalar
 // cache (one s_load_dwordx4 per step).
 #pragma once
-// (included inside namespace dfvo, after conv_win_f16s.h)
+// (included inside namespace dfvo, after conv_pack_f16s.h and conv_win_f16s.h)
 
 // k-group table entry: ky [0,5) | kx [5,10) | valid 10 | source 11 | channel offset inside the source << 16
 static inline uint32_t f16g_entry(int ky, int kx, int valid, int src, int choff) {
@@ -362,30 +362,15 @@ static int launch_f16g_cfg(const ConvParams& p, hipStream_t stream, int cfg_id) 
     // workgroup, the only target of this library; ensure_dyn_lds reports anything the device refuses)
     const bool fast_addr = p.pad_mode != PAD_REFLECT && p.up0 == 0;
     const size_t lds = (KSP > 1 ? (size_t)WP * KSP * TC * 16 * 64 * sizeof(float) : 0) + (fast_addr ? (size_t)p.f16g_steps * 32 : 0);
-    if (lds > 48 * 1024)
-        if (int rc_lds = ensure_dyn_lds(p.f16_terms == 1 ? (const void*)conv_gemm_f16s_kernel<WP, KSP, TC, PF, RAG, 1>
-                                                         : (const void*)conv_gemm_f16s_kernel<WP, KSP, TC, PF, RAG, 3>, lds))
-            return rc_lds;
-    ConvProfEntry pe;
-    if (g_prof) {
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e0));
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e1));
-        pe.cfg = cfg_id;
-        DFVO_HIP_CHECK(hipEventRecord(pe.e0, stream));
-    }
-    if (p.f16_terms == 1)
-        hipLaunchKernelGGL((conv_gemm_f16s_kernel<WP, KSP, TC, PF, RAG, 1>), grid, dim3(64 * WP * KSP), lds, stream, p);
-    else
-        hipLaunchKernelGGL((conv_gemm_f16s_kernel<WP, KSP, TC, PF, RAG, 3>), grid, dim3(64 * WP * KSP), lds, stream, p);
-    DFVO_HIP_CHECK(hipGetLastError());
-    if (g_prof) {
-        DFVO_HIP_CHECK(hipEventRecord(pe.e1, stream));
-        pe.flops = p.useful_flops;
-        const int sh[12] = {p.N, p.H, p.W, p.Ho, p.Wo, (p.G0 + p.G1) * 4, p.cout, p.kh, p.stride, (int)grid.x, TC, KSP * 100 + 1};
-        for (int i = 0; i < 12; ++i) pe.shape[i] = sh[i];
-        g_prof->push_back(pe);
-    }
-    return DFVO_OK;
+    return with_f16_terms(p, [&](auto np) -> int {
+        const auto kernel = conv_gemm_f16s_kernel<WP, KSP, TC, PF, RAG, decltype(np)::value>;
+        if (lds > 48 * 1024)
+            if (int rc_lds = ensure_dyn_lds((const void*)kernel, lds)) return rc_lds;
+        ConvProfScope prof(p, stream, cfg_id);
+        hipLaunchKernelGGL(kernel, grid, dim3(64 * WP * KSP), lds, stream, p);
+        DFVO_HIP_CHECK(hipGetLastError());
+        return prof.done((int)grid.x, TC, KSP * 100 + 1);
+    });
 }
 
 // Shape choice.  TC = 2 (a pixel fragment, whose split costs the VALU work, feeds two cout blocks) whenever the layer has
@@ -393,29 +378,7 @@ static int launch_f16g_cfg(const ConvParams& p, hipStream_t stream, int cfg_id) 
 // Large maps (thousands of pixel blocks) run KSP = 1 with four pixel blocks per workgroup.
 // multi-tap streaming layers: conv_taps_f16s.hip (its own translation unit; bit-identical to the <4, 1, TC> shape here)
 bool conv_taps_f16s_ok(const ConvParams& p);
-int launch_taps_f16s(const ConvParams& p, hipStream_t stream, int* grid_x);
-static int launch_taps_prof(const ConvParams& p0, hipStream_t stream) {
-    ConvParams p = p0;
-    p.f16s_clamp_ctr = f16s_clamp_counter();
-    ConvProfEntry pe;
-    if (g_prof) {
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e0));
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e1));
-        pe.cfg = 20;
-        DFVO_HIP_CHECK(hipEventRecord(pe.e0, stream));
-    }
-    int gx = 0;
-    const int rc = launch_taps_f16s(p, stream, &gx);
-    if (rc != DFVO_OK) return rc;
-    if (g_prof) {
-        DFVO_HIP_CHECK(hipEventRecord(pe.e1, stream));
-        pe.flops = p.useful_flops;
-        const int sh[12] = {p.N, p.H, p.W, p.Ho, p.Wo, (p.G0 + p.G1) * 4, p.cout, p.kh, p.stride, gx, 0, 7};
-        for (int i = 0; i < 12; ++i) pe.shape[i] = sh[i];
-        g_prof->push_back(pe);
-    }
-    return DFVO_OK;
-}
+int launch_taps_f16s(const ConvParams& p, hipStream_t stream);  // (p.f16s_clamp_ctr set; profile row 20)
 
 static int launch_f16g(const ConvParams& p, hipStream_t stream) {
     const long long M = (long long)p.N * p.Ho * p.Wo;
@@ -439,8 +402,12 @@ static int launch_f16g(const ConvParams& p, hipStream_t stream) {
     // multi-tap layers among the streaming shapes: the tap-window kernel (only where this kernel would not slice K: the two
     // then sum in the same order).  DFVO_TAPS=0 (test hook, tests/test_nets_gpu.py): this file's <4, 1, TC> shape instead
     // -- the form the tap-window kernel is compared with bit for bit
-    static const bool taps_on = !(getenv("DFVO_TAPS") && atoi(getenv("DFVO_TAPS")) == 0);
-    if (taps_on && ksp == 1 && conv_taps_f16s_ok(p)) return launch_taps_prof(p, stream);
+    static const bool taps_on = env_flag("DFVO_TAPS", true);
+    if (taps_on && ksp == 1 && conv_taps_f16s_ok(p)) {
+        ConvParams pt = p;
+        pt.f16s_clamp_ctr = f16s_clamp_counter();
+        return launch_taps_f16s(pt, stream);
+    }
     // ragged cout on a streaming shape: the store-only epilogue (profiles/r4j_rag_ab.txt: the 7 x 1 / 1 x 7 distance layers
     // 80 -> 68 / 104 -> 98 us, +0.8 % pairs/s, bit-identical)
     const bool rag = ksp == 1 && (p.cout % (tc2 ? 64 : 32)) != 0 && !p.res && ((p.dst_cs | p.dst_co) & 3) == 0 &&

@@ -239,21 +239,21 @@ bool conv_f32g_ok(const ConvParams& p) {
 }
 
 template <int WP, int KSP, int TC>
-static int launch_f32g_cfg(const ConvParams& p, hipStream_t stream, int* grid_x) {
+static int launch_f32g_cfg(const ConvParams& p, hipStream_t stream) {
     const long long M = (long long)p.N * p.Ho * p.Wo;
     dim3 grid((unsigned)(((M + 32 * WP - 1) / (32 * WP)) * (p.wf16g_cout_pad / (32 * TC))), 1, 1);
     const size_t lds = KSP > 1 ? (size_t)WP * KSP * TC * 16 * 64 * sizeof(float) : 0;
     if (lds > 48 * 1024)
         if (int rc_lds = ensure_dyn_lds((const void*)conv_gemm_f32g_kernel<WP, KSP, TC>, lds)) return rc_lds;
+    ConvProfScope prof(p, stream, KSP == 1 ? 22 : 23);  // profile rows: 22 streaming (KSP = 1), 23 K-sliced small maps
     hipLaunchKernelGGL((conv_gemm_f32g_kernel<WP, KSP, TC>), grid, dim3(64 * WP * KSP), lds, stream, p);
     DFVO_HIP_CHECK(hipGetLastError());
-    if (grid_x) *grid_x = (int)grid.x;
-    return DFVO_OK;
+    return prof.done((int)grid.x, 0, KSP * 100 + 1);
 }
 
 // Shape choice: the rules of launch_f16g (conv_gemm_f16s.h) -- two cout blocks per wave while that leaves enough tiles, K
-// sliced over the waves of a workgroup until the chip holds ~2 waves per SIMD.  *ksp_out: the K slicing chosen (profile row)
-int launch_f32g(const ConvParams& p, hipStream_t stream, int* ksp_out, int* grid_x) {
+// sliced over the waves of a workgroup until the chip holds ~2 waves per SIMD
+int launch_f32g(const ConvParams& p, hipStream_t stream) {
     const long long M = (long long)p.N * p.Ho * p.Wo;
     const long long mblocks = (M + 31) / 32;
     const int nblk = p.wf16g_cout_pad / 32;
@@ -263,21 +263,20 @@ int launch_f32g(const ConvParams& p, hipStream_t stream, int* ksp_out, int* grid
     const long long tiles = mblocks * (tc2 ? nblk / 2 : nblk);
     int ksp = 1;
     while (ksp < (tc2 ? 8 : 16) && tiles * ksp * 2 <= target && p.f16g_steps >= 4 * ksp * 2) ksp *= 2;
-    if (ksp_out) *ksp_out = ksp;
     if (tc2) {
         switch (ksp) {
-            case 1: return launch_f32g_cfg<4, 1, 2>(p, stream, grid_x);
-            case 2: return launch_f32g_cfg<2, 2, 2>(p, stream, grid_x);
-            case 4: return launch_f32g_cfg<1, 4, 2>(p, stream, grid_x);
-            default: return launch_f32g_cfg<1, 8, 2>(p, stream, grid_x);
+            case 1: return launch_f32g_cfg<4, 1, 2>(p, stream);
+            case 2: return launch_f32g_cfg<2, 2, 2>(p, stream);
+            case 4: return launch_f32g_cfg<1, 4, 2>(p, stream);
+            default: return launch_f32g_cfg<1, 8, 2>(p, stream);
         }
     }
     switch (ksp) {
-        case 1: return launch_f32g_cfg<4, 1, 1>(p, stream, grid_x);
-        case 2: return launch_f32g_cfg<2, 2, 1>(p, stream, grid_x);
-        case 4: return launch_f32g_cfg<1, 4, 1>(p, stream, grid_x);
-        case 8: return launch_f32g_cfg<1, 8, 1>(p, stream, grid_x);
-        default: return launch_f32g_cfg<1, 16, 1>(p, stream, grid_x);
+        case 1: return launch_f32g_cfg<4, 1, 1>(p, stream);
+        case 2: return launch_f32g_cfg<2, 2, 1>(p, stream);
+        case 4: return launch_f32g_cfg<1, 4, 1>(p, stream);
+        case 8: return launch_f32g_cfg<1, 8, 1>(p, stream);
+        default: return launch_f32g_cfg<1, 16, 1>(p, stream);
     }
 }
 

@@ -1,5 +1,16 @@
-// Implicit-GEMM convolution on the gfx950 matrix cores, exact fp32 numerics.
+// The convolution translation unit: the exact-fp32 kernels of this file, the f16 kernel families it includes, and the
+// dispatcher launch_conv() over all of them.  In order:
+//   1. fp32 device code: split-K hand-off, conv_igemm_f32_kernel (implicit GEMM, described below), conv_win_f32_kernel
+//      (LDS window, k x k / stride 1), conv_splitk_epilogue, conv_head_f32_kernel (direct one- / two-channel heads)
+//   2. the fp32 packers conv_pick_bn, conv_pack_weights, conv_pack_head_weights (between the kernels they serve)
+//   3. the per-launch profile: ConvProfEntry, ConvProfScope (declared in dfvo_common.h: the kernels of conv_gemm_f32g.hip
+//      and conv_taps_f16s.hip, translation units of their own, are profiled through it too), conv_profile_begin / _end
+//   4. the f16 families, included: conv_pack_f16s.h (host packers; pulls in conv_f16_clamp.h, the saturation counter, and
+//      conv_f16_split.h, the plane split), conv_win_f16s.h, conv_gemm_f16s.h, conv_win_f16s2.h -- kernels and launchers each
+//   5. the fp32 launchers (conv_splitk_slices, launch_splitk, launch_cfg, launch_win3, launch_head), the tile rules, and
+//      launch_conv()
 //
+// conv_igemm_f32_kernel: implicit-GEMM convolution on the gfx950 matrix cores, exact fp32 numerics.
 // Replaces the torch.nn.Conv2d (+bias, +LeakyReLU/ReLU/ELU/sigmoid, +residual, +BatchNorm(eval),
 // +ReflectionPad2d, +nearest x2 upsample, +channel concat) call sites of the reference's nets:
 //   LiteFlowNet  /root/reference/libs/deep_models/flow/lite_flow_net/lite_flow_net.py:39-75,98-101,
@@ -776,9 +787,36 @@ struct ConvProfEntry {
     hipEvent_t e0, e1;
     int cfg;
     double flops;
-    int shape[12];  // N H W Ho Wo cin cout k stride gx gy gz
+    // N H W Ho Wo cin cout k stride gx gy gz.  gx gy gz are what the launcher passes to ConvProfScope::done(), three conventions:
+    //   fp32 kernels (cfg 0-18): the grid -- gz = split-K slices, heads gy = gz = 1
+    //   window f16 kernels (cfg 19): gx gy = the grid, gz = the skeleton (1 conv_win_f16s.h, 2 conv_win_f16s2.h, mixed heights too)
+    //   generic kernels (cfg 20-23): gx = the grid, gy = cout blocks per wave TC, gz = 100 KSP + 1 (K slices per workgroup);
+    //     the tap-window kernel: gy = 0, gz = 7; the fp32 twin conv_gemm_f32g: gy = 0
+    int shape[12];
 };
 static std::vector<ConvProfEntry>* g_prof = nullptr;
+
+ConvProfScope::ConvProfScope(const ConvParams& p, hipStream_t stream, int cfg_id) : p_(p), stream_(stream), cfg_(cfg_id) {
+    if (!g_prof) return;
+    if ((err_ = hipEventCreate(&e0_)) != hipSuccess) return;
+    if ((err_ = hipEventCreate(&e1_)) == hipSuccess) err_ = hipEventRecord(e0_, stream_);
+}
+ConvProfScope::~ConvProfScope() {
+    if (e0_) (void)hipEventDestroy(e0_);
+    if (e1_) (void)hipEventDestroy(e1_);
+}
+int ConvProfScope::done(int gx, int gy, int gz) {
+    if (err_ != hipSuccess) {  // of the constructor: reported here, where the launcher can return it
+        set_last_error(std::string("conv profile events: ") + hipGetErrorString(err_));
+        return DFVO_ERR_HIP;
+    }
+    if (!e1_ || !g_prof) return DFVO_OK;  // no profile is running
+    DFVO_HIP_CHECK(hipEventRecord(e1_, stream_));
+    g_prof->push_back({e0_, e1_, cfg_, p_.useful_flops,
+                       {p_.N, p_.H, p_.W, p_.Ho, p_.Wo, (p_.G0 + p_.G1) * 4, p_.cout, p_.kh, p_.stride, gx, gy, gz}});
+    e0_ = e1_ = nullptr;  // conv_profile_end() destroys them
+    return DFVO_OK;
+}
 
 void conv_profile_begin() {
     if (!g_prof) g_prof = new std::vector<ConvProfEntry>();
@@ -828,29 +866,37 @@ int conv_profile_end(double* ms, double* flops, int* launches, double* bytes) {
     return DFVO_OK;
 }
 
+#include "conv_pack_f16s.h"
 #include "conv_win_f16s.h"
 #include "conv_gemm_f16s.h"
 #include "conv_win_f16s2.h"
 
-// split-K when the grid cannot fill the chip: partials to p.ws, ordered reduction in a second launch
-static int conv_pick_splits(const ConvParams& p, long long blocks) {
+// Split-K when the grid cannot fill the chip (fewer than 600 workgroups): the number of K slices for `units` units of K
+// (K-steps, or channel chunks) with at least `min_per_slice` units each, at most `cap`, partials [slices][M][cout_pad] inside p.ws
+static int conv_splitk_slices(const ConvParams& p, long long blocks, int units, int min_per_slice, int cap) {
+    if (!p.ws || blocks >= 600 || units < 2 * min_per_slice) return 1;
     const long long M = (long long)p.N * p.Ho * p.Wo;
-    int splits = 1;
-    if (!p.ws) return 1;
-    if (p.force_splits > 0)
-        splits = p.force_splits;
-    else if (blocks < 600 && p.ksteps >= 16)
-        splits = (int)((1024 + blocks - 1) / blocks);
-    if (splits > 1) {
-        if (splits > p.ksteps / 8) splits = p.ksteps / 8;
-        if (splits > 32) splits = 32;
-        while (splits > 1 && (size_t)splits * M * p.cout_pad > p.ws_floats) --splits;
-        if (splits < 1) splits = 1;
-        // no empty z-slices
-        const int per = (p.ksteps + splits - 1) / splits;
-        splits = (p.ksteps + per - 1) / per;
+    int splits = std::min({(int)((1024 + blocks - 1) / blocks), units / min_per_slice, cap});
+    while (splits > 1 && (size_t)splits * M * p.cout_pad > p.ws_floats) --splits;
+    const int per = (units + splits - 1) / splits;  // no empty slice
+    return (units + per - 1) / per;
+}
+
+// grid.z K slices of a contracting kernel: finished inside the kernel when the tiles have tickets (splitk_last_arriver),
+// else by the ordered reduction of conv_splitk_epilogue in a second launch
+static int launch_splitk(void (*kernel)(const ConvParams), dim3 grid, const ConvParams& p, hipStream_t stream) {
+    ConvParams pk = p;
+    const bool fused = grid.z > 1 && pk.tile_flags && (long long)grid.x * grid.y <= pk.tile_flags_n;
+    if (!fused) pk.tile_flags = nullptr;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, pk);
+    DFVO_HIP_CHECK(hipGetLastError());
+    if (grid.z > 1 && !fused) {
+        const int cols = p.dst_zero_to > p.cout ? p.dst_zero_to : p.cout;
+        const long long total = (long long)p.N * p.Ho * p.Wo * cols;
+        hipLaunchKernelGGL(conv_splitk_epilogue, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p, (int)grid.z);
+        DFVO_HIP_CHECK(hipGetLastError());
     }
-    return splits;
+    return DFVO_OK;
 }
 
 template <int WM, int WN, int TM, int TN>
@@ -859,44 +905,12 @@ static int launch_cfg(const ConvParams& p, hipStream_t stream, int cfg_id) {
     const long long M = (long long)p.N * p.Ho * p.Wo;
     dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)(p.cout_pad / BN), 1);
     DFVO_ARG_CHECK((p.G0 + p.G1) * p.kh * p.kw + 4 <= MAX_KGROUPS, "launch_conv: too many k-groups for the LDS table");
-    const int splits = conv_pick_splits(p, (long long)grid.x * grid.y);
-    grid.z = (unsigned)splits;
-    ConvProfEntry pe;
-    if (g_prof) {
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e0));
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e1));
-        pe.cfg = cfg_id;
-        const int cin = (p.G0 + p.G1) * 4;  // padded channels; the caller's useful-FLOP count is kept separately
-        (void)cin;
-        pe.flops = 0;
-        DFVO_HIP_CHECK(hipEventRecord(pe.e0, stream));
-    }
-    ConvParams pk = p;  // in-kernel split-K finish when the tiles have tickets (else: second launch below)
-    const bool fused = splits > 1 && pk.tile_flags && (long long)grid.x * grid.y <= pk.tile_flags_n;
-    if (!fused) pk.tile_flags = nullptr;
-    hipLaunchKernelGGL((conv_igemm_f32_kernel<WM, WN, TM, TN>), grid, dim3(256), 0, stream, pk);
-    DFVO_HIP_CHECK(hipGetLastError());
-    if (splits > 1 && !fused) {
-        const int cols = p.dst_zero_to > p.cout ? p.dst_zero_to : p.cout;
-        const long long total = M * cols;
-        hipLaunchKernelGGL(conv_splitk_epilogue, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p, splits);
-        DFVO_HIP_CHECK(hipGetLastError());
-    }
-    if (g_prof) {
-        DFVO_HIP_CHECK(hipEventRecord(pe.e1, stream));
-        pe.flops = p.useful_flops;
-        const int sh[12] = {p.N, p.H, p.W, p.Ho, p.Wo, (p.G0 + p.G1) * 4, p.cout, p.kh, p.stride, (int)grid.x, (int)grid.y, (int)grid.z};
-        for (int i = 0; i < 12; ++i) pe.shape[i] = sh[i];
-        g_prof->push_back(pe);
-    }
-    return DFVO_OK;
+    grid.z = (unsigned)conv_splitk_slices(p, (long long)grid.x * grid.y, p.ksteps, 8, 32);
+    ConvProfScope prof(p, stream, cfg_id);
+    if (int rc = launch_splitk(conv_igemm_f32_kernel<WM, WN, TM, TN>, grid, p, stream)) return rc;
+    return prof.done((int)grid.x, (int)grid.y, (int)grid.z);
 }
 
-// Tile choice: the widest N tile the layer's cout allows (conv_pick_bn); the M tile from a sweep on MI355X
-// (tools/sweep_conv.sh): 64-row tiles win or tie on every layer with BN <= 64 and on BN = 128 below ~1200
-// workgroups (more resident workgroups hide the global -> LDS staging latency; the per-tap gather is served by
-// L2 either way); 128 x 128 keeps the largest maps.  Small grids additionally split K inside launch_cfg.
-// DFVO_CONV_FORCE_BM=<rows> overrides the M tile (tuning aid).
 template <int WM, int WN, int TM, int TN, int KS = 3>
 static int launch_win3(const ConvParams& p, hipStream_t stream, int cfg_id) {
     constexpr int TH = WM * TM, BN = WN * TN * 16;
@@ -904,73 +918,26 @@ static int launch_win3(const ConvParams& p, hipStream_t stream, int cfg_id) {
     dim3 grid((unsigned)tiles, (unsigned)(p.cout_pad / BN), 1);
     // split the channel chunks when the tile grid cannot fill the chip
     const int nchunks = ((p.G0 + 3) >> 2) + ((p.G1 + 3) >> 2);
-    const long long M = (long long)p.N * p.Ho * p.Wo;
-    int splits = 1;
-    const long long blocks = (long long)grid.x * grid.y;
-    if (p.ws && blocks < 600 && nchunks >= 4) {
-        splits = (int)((1024 + blocks - 1) / blocks);
-        if (splits > nchunks / 2) splits = nchunks / 2;
-        while (splits > 1 && (size_t)splits * M * p.cout_pad > p.ws_floats) --splits;
-        if (splits < 1) splits = 1;
-        const int per = (nchunks + splits - 1) / splits;
-        splits = (nchunks + per - 1) / per;
-    }
-    grid.z = (unsigned)splits;
-    ConvProfEntry pe;
-    if (g_prof) {
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e0));
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e1));
-        pe.cfg = cfg_id;
-        DFVO_HIP_CHECK(hipEventRecord(pe.e0, stream));
-    }
-    ConvParams pk = p;  // in-kernel split-K finish (exact fp32 kernel) when the tiles have tickets
-    const bool fused = splits > 1 && pk.tile_flags && blocks <= pk.tile_flags_n;
-    if (!fused) pk.tile_flags = nullptr;
-    hipLaunchKernelGGL((conv_win_f32_kernel<WM, WN, TM, TN, KS>), grid, dim3(256), 0, stream, pk);
-    DFVO_HIP_CHECK(hipGetLastError());
-    if (splits > 1 && !fused) {
-        const int cols = p.dst_zero_to > p.cout ? p.dst_zero_to : p.cout;
-        const long long total = M * cols;
-        hipLaunchKernelGGL(conv_splitk_epilogue, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p, splits);
-        DFVO_HIP_CHECK(hipGetLastError());
-    }
-    if (g_prof) {
-        DFVO_HIP_CHECK(hipEventRecord(pe.e1, stream));
-        pe.flops = p.useful_flops;
-        const int sh[12] = {p.N, p.H, p.W, p.Ho, p.Wo, (p.G0 + p.G1) * 4, p.cout, p.kh, p.stride, (int)grid.x, (int)grid.y, (int)grid.z};
-        for (int i = 0; i < 12; ++i) pe.shape[i] = sh[i];
-        g_prof->push_back(pe);
-    }
-    return DFVO_OK;
+    grid.z = (unsigned)conv_splitk_slices(p, (long long)grid.x * grid.y, nchunks, 2, nchunks);
+    ConvProfScope prof(p, stream, cfg_id);
+    if (int rc = launch_splitk(conv_win_f32_kernel<WM, WN, TM, TN, KS>, grid, p, stream)) return rc;
+    return prof.done((int)grid.x, (int)grid.y, (int)grid.z);
 }
 
 template <int KS, int CO>
 static int launch_head(const ConvParams& p, hipStream_t stream, int cfg_id) {
-    static const bool py1_ok = !(getenv("DFVO_HEAD_PY1") && atoi(getenv("DFVO_HEAD_PY1")) == 0);
+    static const bool py1_ok = env_flag("DFVO_HEAD_PY1", true);
     const int tiles2 = p.N * ((p.Ho + 31) / 32) * ((p.Wo + 15) / 16);
     const bool py1 = py1_ok && tiles2 < 256;  // (one workgroup per CU is the first round; below that the chain per thread is the launch)
     const int tiles = py1 ? p.N * ((p.Ho + 15) / 16) * ((p.Wo + 15) / 16) : tiles2;
     dim3 grid((unsigned)tiles, 1, 1);
-    ConvProfEntry pe;
-    if (g_prof) {
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e0));
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e1));
-        pe.cfg = cfg_id;
-        DFVO_HIP_CHECK(hipEventRecord(pe.e0, stream));
-    }
+    ConvProfScope prof(p, stream, cfg_id);
     if (py1)
         hipLaunchKernelGGL((conv_head_f32_kernel<KS, CO, 1>), grid, dim3(256), 0, stream, p);
     else
         hipLaunchKernelGGL((conv_head_f32_kernel<KS, CO, 2>), grid, dim3(256), 0, stream, p);
     DFVO_HIP_CHECK(hipGetLastError());
-    if (g_prof) {
-        DFVO_HIP_CHECK(hipEventRecord(pe.e1, stream));
-        pe.flops = p.useful_flops;
-        const int sh[12] = {p.N, p.H, p.W, p.Ho, p.Wo, (p.G0 + p.G1) * 4, p.cout, p.kh, p.stride, (int)grid.x, 1, 1};
-        for (int i = 0; i < 12; ++i) pe.shape[i] = sh[i];
-        g_prof->push_back(pe);
-    }
-    return DFVO_OK;
+    return prof.done((int)grid.x, 1, 1);
 }
 
 // the direct kernel serves the square, stride-1, "same"-padded heads with one or two output channels
@@ -990,20 +957,20 @@ static bool conv_use_window(const ConvParams& p, int bn) {
     return (p.kh == 5 || p.kh == 7) && bn == 16 && (p.G0 + p.G1) >= 4 && M >= 8000;
 }
 
+// Tile choice: the widest N tile the layer's cout allows (conv_pick_bn); the M tile from a sweep on MI355X
+// (tools/sweep_conv.sh): 64-row tiles win or tie on every layer with BN <= 64 and on BN = 128 below ~1200
+// workgroups (more resident workgroups hide the global -> LDS staging latency; the per-tap gather is served by
+// L2 either way); 128 x 128 keeps the largest maps.  Small grids additionally split K (conv_splitk_slices).
 static int conv_pick_bm(const ConvParams& p, int bn) {
     const long long M = (long long)p.N * p.Ho * p.Wo;
-    const int force_bm = p.force_bm;  // (0: the rule below)
     const long long ntiles_n = p.cout_pad / bn;
     auto blocks = [&](int bm) { return ((M + bm - 1) / bm) * ntiles_n; };
     if (bn == 128) {
         int bm = blocks(128) >= 1200 ? 128 : 64;
         if (M <= 4096) bm = 32;
-        if (force_bm == 128 || force_bm == 64 || force_bm == 32) bm = force_bm;
         return bm;
     }
-    int bm = M >= 400000 ? 128 : 64;
-    if (force_bm == 256 || force_bm == 128 || force_bm == 64) bm = force_bm;
-    return bm;
+    return M >= 400000 ? 128 : 64;
 }
 
 // exact-fp32 mode: which layers leave conv_igemm_f32_kernel for the register-ring kernel (conv_gemm_f32g.hip).  Not the
@@ -1015,26 +982,6 @@ static bool conv_f32g_takes(const ConvParams& p, int bn) {
     if (conv_use_window(p, bn)) return false;
     const long long M = (long long)p.N * p.Ho * p.Wo;
     return M <= 8192;  // pyramid levels 5 / 6 (2 x 11 x 38 .. 2 x 44 x 152) and the depth net's 6 x 20 .. 48 x 160 maps
-}
-static int launch_f32g_prof(const ConvParams& p, hipStream_t stream) {
-    ConvProfEntry pe;
-    if (g_prof) {
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e0));
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e1));
-        DFVO_HIP_CHECK(hipEventRecord(pe.e0, stream));
-    }
-    int ksp = 1, gx = 0;
-    const int rc = launch_f32g(p, stream, &ksp, &gx);
-    if (rc != DFVO_OK) return rc;
-    if (g_prof) {
-        pe.cfg = ksp == 1 ? 22 : 23;  // profile rows: 22 streaming (KSP = 1), 23 K-sliced small maps
-        DFVO_HIP_CHECK(hipEventRecord(pe.e1, stream));
-        pe.flops = p.useful_flops;
-        const int sh[12] = {p.N, p.H, p.W, p.Ho, p.Wo, (p.G0 + p.G1) * 4, p.cout, p.kh, p.stride, gx, 0, ksp * 100 + 1};
-        for (int i = 0; i < 12; ++i) pe.shape[i] = sh[i];
-        g_prof->push_back(pe);
-    }
-    return DFVO_OK;
 }
 
 int launch_conv(const ConvParams& p, hipStream_t stream) {
@@ -1053,7 +1000,7 @@ int launch_conv(const ConvParams& p, hipStream_t stream) {
         return rc2 != F16S2_NOT_APPLICABLE ? rc2 : launch_f16s(p, stream, 19);  // errors (negative) propagate
     }
     if (conv_f16g_ok(p)) return launch_f16g(p, stream);  // f16x3: everything else (small maps, 1x1, k x 1, stride 2, 7x7)
-    if (conv_f32g_ok(p) && conv_f32g_takes(p, bn)) return launch_f32g_prof(p, stream);  // exact fp32: the same skeleton on fp32 MFMAs
+    if (conv_f32g_ok(p) && conv_f32g_takes(p, bn)) return launch_f32g(p, stream);  // exact fp32: the same skeleton on fp32 MFMAs
     if (conv_use_window(p, bn) && p.kh == 7) return launch_win3<4, 1, 2, 1, 7>(p, stream, 16);
     if (conv_use_window(p, bn) && p.kh == 5) return launch_win3<4, 1, 2, 1, 5>(p, stream, 17);
     if (conv_use_window(p, bn)) {
@@ -1067,7 +1014,7 @@ int launch_conv(const ConvParams& p, hipStream_t stream) {
         if (bn == 64) return launch_win3<2, 2, 4, 2>(p, stream, 13);
         return launch_win3<4, 1, 2, 2>(p, stream, 14);
     }
-    const int bm = conv_pick_bm(p, bn);
+    const int bm = conv_pick_bm(p, bn);  // (never 256 today: those tiles stay instantiated and selectable by the rule)
     if (bn == 128) {
         if (bm == 128) return launch_cfg<2, 2, 4, 4>(p, stream, 0);
         if (bm == 64) return launch_cfg<1, 4, 4, 2>(p, stream, 8);

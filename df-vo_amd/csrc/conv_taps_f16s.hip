@@ -240,6 +240,13 @@ bool taps_geom(const ConvParams& p, TapsGeom* g) {
     }
     return false;
 }
+template <int TH, int TC>
+void taps_launch(const ConvParams& p, hipStream_t stream, int tiles, const TapsGeom& g) {
+    with_f16_terms(p, [&](auto np) {
+        hipLaunchKernelGGL((conv_taps_f16s_kernel<TH, TC, decltype(np)::value>), dim3(tiles), dim3(64 * TH), g.lds, stream, p, g.G,
+                           g.pxd, g.wcols, g.wrows);
+    });
+}
 }  // namespace
 
 bool conv_taps_f16s_ok(const ConvParams& p) {
@@ -255,36 +262,19 @@ bool conv_taps_f16s_ok(const ConvParams& p) {
     return taps_geom(p, &g);
 }
 
-int launch_taps_f16s(const ConvParams& p, hipStream_t stream, int* grid_x) {
+int launch_taps_f16s(const ConvParams& p, hipStream_t stream) {
     DFVO_ARG_CHECK(p.f16s_clamp_ctr, "conv_taps_f16s: clamp counter not set");
     TapsGeom g;
     DFVO_ARG_CHECK(taps_geom(p, &g), "conv_taps_f16s: window does not fit");
     const int tiles = p.N * ((p.Ho + g.th - 1) / g.th) * ((p.Wo + 31) / 32);
     const bool tc2 = p.wf16g_cout_pad == 64;
-#define DFVO_TAPS_LAUNCH(TH_, TC_)                                                                                          \
-    do {                                                                                                                   \
-        if (p.f16_terms == 1)                                                                                              \
-            hipLaunchKernelGGL((conv_taps_f16s_kernel<TH_, TC_, 1>), dim3(tiles), dim3(64 * TH_), g.lds, stream, p, g.G,    \
-                               g.pxd, g.wcols, g.wrows);                                                                   \
-        else                                                                                                               \
-            hipLaunchKernelGGL((conv_taps_f16s_kernel<TH_, TC_, 3>), dim3(tiles), dim3(64 * TH_), g.lds, stream, p, g.G,    \
-                               g.pxd, g.wcols, g.wrows);                                                                   \
-    } while (0)
-    if (g.th == 4) {
-        if (tc2)
-            DFVO_TAPS_LAUNCH(4, 2);
-        else
-            DFVO_TAPS_LAUNCH(4, 1);
-    } else {
-        if (tc2)
-            DFVO_TAPS_LAUNCH(2, 2);
-        else
-            DFVO_TAPS_LAUNCH(2, 1);
-    }
-#undef DFVO_TAPS_LAUNCH
+    ConvProfScope prof(p, stream, 20);
+    if (g.th == 4)
+        tc2 ? taps_launch<4, 2>(p, stream, tiles, g) : taps_launch<4, 1>(p, stream, tiles, g);
+    else
+        tc2 ? taps_launch<2, 2>(p, stream, tiles, g) : taps_launch<2, 1>(p, stream, tiles, g);
     DFVO_HIP_CHECK(hipGetLastError());
-    if (grid_x) *grid_x = tiles;
-    return DFVO_OK;
+    return prof.done(tiles, 0, 7);
 }
 
 }  // namespace dfvo

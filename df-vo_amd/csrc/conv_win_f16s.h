@@ -1,5 +1,5 @@
 // 3x3 / stride-1 convolution with fp32-class accuracy on the f16 matrix cores (opt-in: DFVO_CONV_PRECISION=f16x3).
-// Included by conv_igemm_f32.hip (same translation unit: shares the epilogue and the per-launch profiling hooks).
+// Included by conv_igemm_f32.hip (same translation unit: shares the epilogue and the saturation counter of conv_f16_clamp.h).
 //
 // Every fp32 operand x is split into two f16 planes  x = hi + 2^-11 lo,  hi = f16(x),  lo = f16((x - hi) * 2^11):
 // 22 mantissa bits, the scaled low plane never leaves f16's normal range (an unscaled residue would be subnormal for
@@ -9,7 +9,7 @@
 // sets ("main" and "cross") that the epilogue combines as main + 2^-11 cross.  Against the exact fp32-MFMA path this
 // trades 16 K-passes of 64 FLOP/clk/SIMD for 3 passes of 1024 FLOP/clk/SIMD: 5.3x less matrix-pipe time.
 //
-// Tiling (wave64, 4 or 8 waves per workgroup): a workgroup owns TH rows x 32 columns of output pixels x BN output channels.
+// Tiling (wave64, 4 waves per workgroup): a workgroup owns TH rows x 32 columns of output pixels x BN output channels.
 // The (TH+2) x 34 input window of one 16-channel chunk is split into planes ONCE, when it is written to LDS
 // (padding / reflection / x2-upsample / two-source concat resolved at that load), pixel stride 80 bytes = 5 sixteen-byte
 // slots: the 16 lanes of every ds_read_b128 service group hit 16 distinct slots.  One MFMA contracts a whole chunk for a
@@ -22,32 +22,17 @@
 #pragma once
 // (included inside namespace dfvo)
 
-#include "conv_f16_split.h"
+#include "conv_f16_clamp.h"
 
-// |x| > 65504 does not fit the hi plane.  It is neither clamped (a silently wrong product) nor ignored: the conversion
-// yields +-inf, which propagates as inf / NaN into the layer's output, and every kernel that splits activations keeps the
-// running max |x| of what it split (one v_max3_f32 per two elements -- cheaper than the clamp it replaces) and bumps
-// g_f16s_clamped once per thread that saw such a value; dfvo_f16s_overflow_count() reads it (the -m gpu tests assert
-// zero after every f16x3 test).
-__device__ unsigned int g_f16s_clamped = 0;
-__device__ __forceinline__ void f16s_report_clamp(float amax) {
-    if (amax > F16S_MAX) atomicAdd(&g_f16s_clamped, 1u);
-}
-// the counter's device address, for the f16x3 kernels that live in other translation units (device symbols do not cross TUs)
-static unsigned* f16s_clamp_counter() {
-    static unsigned* ptr = nullptr;
-    if (!ptr && hipGetSymbolAddress((void**)&ptr, HIP_SYMBOL(g_f16s_clamped)) != hipSuccess) ptr = nullptr;
-    return ptr;
-}
 template <int WC, int WR, int TC, int TR, int NP = 3>  // NP: products per term (3 = f16x3, 1 = "f16" mode: hi planes only)
 __global__ __launch_bounds__(64 * WC * WR, 2) void conv_win_f16s_kernel(const ConvParams p) {
-    constexpr int NT = 64 * WC * WR;  // 4 or 8 waves per workgroup
+    constexpr int NT = 64 * WC * WR;  // 4 waves per workgroup
     constexpr int TH = WR * TR, TW = 32, WH = TH + 2, WW = TW + 2, PS = 20;  // pixel stride in dwords (80 bytes)
     constexpr int BN = WC * TC * 32;
     constexpr int WIN = WH * WW * PS;  // dwords per window buffer
     constexpr int W_ITEMS = WH * WW * 4;
     constexpr int W_CNT = (W_ITEMS + NT - 1) / NT;
-    static_assert(WC * WR == 4 || WC * WR == 8, "4 or 8 waves per block");
+    static_assert(WC * WR == 4 && TC == 1 && W_CNT <= 6, "the one shape left on this skeleton: 4 waves, one cout block per wave");
     __shared__ __attribute__((aligned(16))) float lds[2 * WIN];
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -130,14 +115,12 @@ __global__ __launch_bounds__(64 * WC * WR, 2) void conv_win_f16s_kernel(const Co
     // [register stage][cout block][plane].  Memory operations retire in order (one vmcnt): waiting for a weight fragment also
     // waits for every older load, so the window loads of the next chunk -- HBM latency -- get exactly as many taps of slack
     // as the fragments are fetched ahead.  One cout block per wave (TC == 1) leaves room for a ring of three = two taps ahead
-    // (9 taps = 3 turns of the ring: the stage of a tap is a compile-time constant and nothing is copied at the chunk end);
-    // TC == 2 keeps two stages, one tap ahead (a third would spill: 128 accumulator + 48 ring + 16 pixel-fragment +
-    // window staging registers)
+    // (9 taps = 3 turns of the ring: the stage of a tap is a compile-time constant and nothing is copied at the chunk end)
     // (Round 6: a ring of NINE for the one shape left on this skeleton -- a whole chunk of fragments in registers, tap t of chunk
     // c + 1 requested behind the MFMAs of tap t of chunk c; 183 VGPRs, no scratch -- measured SLOWER on every small-map layer it
     // serves: level-4 128 -> 128 29.4 -> 33.6 us, 96+98 -> 128 42.0 -> 48.1, 128 -> 64 25.4 -> 29.1 (profiles/r6q_heads_ring.txt
     // against r6l_small_map_tiles.txt).  Those launches are not waiting for their weight fragments; reverted.)
-    constexpr int R = TC == 1 ? 3 : 2;
+    constexpr int R = 3;
     h16x8 wa[R][TC][2];
     auto load_w = [&](int stage, int tap, int c) {
         const unsigned short* g = wbase + ((size_t)tap * nchunks + c) * w_chunk_stride;
@@ -161,7 +144,7 @@ __global__ __launch_bounds__(64 * WC * WR, 2) void conv_win_f16s_kernel(const Co
 
     load_window(0);
     load_w(0, 0, 0);
-    if (R == 3) load_w(1, 1, 0);
+    load_w(1, 1, 0);
     store_window(lds);
     __syncthreads();
     for (int c = 0; c < nchunks; ++c) {
@@ -169,22 +152,15 @@ __global__ __launch_bounds__(64 * WC * WR, 2) void conv_win_f16s_kernel(const Co
         float* Wn = lds + ((c + 1) & 1) * WIN;
         const bool next_chunk = c + 1 < nchunks;
         const int c_next = c + 1;
-        constexpr bool SPREAD = W_CNT <= 6;  // (always, with the tiles instantiated below)
-        if (next_chunk && !SPREAD) load_window(c_next);
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int ky = tap / 3, kx = tap - ky * 3;
-            const int cur = R == 3 ? tap % 3 : (tap & 1);  // compile-time register stage (the loop is fully unrolled)
-            if (R == 3) {
-                if (tap < 7)
-                    load_w((tap + 2) % 3, tap + 2, c);
-                else if (next_chunk)
-                    load_w((tap + 2) % 3, tap - 7, c_next);
-            } else if (tap < 8)
-                load_w(cur ^ 1, tap + 1, c);
+            const int cur = tap % 3;  // compile-time register stage (the loop is fully unrolled)
+            if (tap < 7)
+                load_w((tap + 2) % 3, tap + 2, c);
             else if (next_chunk)
-                load_w(1, 0, c_next);  // tap 8 runs from stage 0: the next chunk's first fragments land in stage 1 ...
-            if (SPREAD && next_chunk && tap < W_CNT) load_window_item(c_next, tap);
+                load_w((tap + 2) % 3, tap - 7, c_next);
+            if (next_chunk && tap < W_CNT) load_window_item(c_next, tap);
             // keep the fetch HERE: left alone, the scheduler sinks these loads below the tap's last MFMA (it then needs one
             // register set instead of two) and the L2 round trip is exposed at every tap -- measured 30 % matrix-pipe busy
             __builtin_amdgcn_sched_barrier(0);
@@ -213,18 +189,8 @@ __global__ __launch_bounds__(64 * WC * WR, 2) void conv_win_f16s_kernel(const Co
 #pragma unroll
                 for (int j = 0; j < TR; ++j)
                     am[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa[cur][i][0], xb[j][0], am[i][j], 0, 0, 0);
-            if (SPREAD) {
-                if (next_chunk && tap >= 9 - W_CNT) store_window_item(Wn, tap - (9 - W_CNT));
-            } else if (tap == 4 && next_chunk) {
-                store_window(Wn);
-            }
+            if (next_chunk && tap >= 9 - W_CNT) store_window_item(Wn, tap - (9 - W_CNT));
         }
-        if (R == 2)
-#pragma unroll
-            for (int i = 0; i < TC; ++i) {  // ... and move to stage 0, where tap 0 expects them (2 TC register-quad copies per chunk)
-                wa[0][i][0] = wa[1][i][0];
-                if constexpr (NP == 3) wa[0][i][1] = wa[1][i][1];
-            }
         __syncthreads();
     }
 
@@ -263,6 +229,7 @@ static bool conv_f16s_ok(const ConvParams& p) {
     return e >= 200;
 }
 
+// workgroups of a launch with this tile shape, either window skeleton (0: the shape does not divide the layer's couts)
 template <int WC, int WR, int TC, int TR>
 static long long f16s_blocks(const ConvParams& p) {
     constexpr int TH = WR * TR, BN = WC * TC * 32;
@@ -275,26 +242,12 @@ static int launch_f16s_cfg(const ConvParams& p, hipStream_t stream, int cfg_id) 
     constexpr int TH = WR * TR, BN = WC * TC * 32;
     const int tiles = p.N * ((p.Ho + TH - 1) / TH) * ((p.Wo + 31) / 32);
     dim3 grid((unsigned)tiles, (unsigned)(p.wf16_cout_pad / BN), 1);
-    ConvProfEntry pe;
-    if (g_prof) {
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e0));
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e1));
-        pe.cfg = cfg_id;
-        DFVO_HIP_CHECK(hipEventRecord(pe.e0, stream));
-    }
-    if (p.f16_terms == 1)
-        hipLaunchKernelGGL((conv_win_f16s_kernel<WC, WR, TC, TR, 1>), grid, dim3(64 * WC * WR), 0, stream, p);
-    else
-        hipLaunchKernelGGL((conv_win_f16s_kernel<WC, WR, TC, TR, 3>), grid, dim3(64 * WC * WR), 0, stream, p);
+    ConvProfScope prof(p, stream, cfg_id);
+    with_f16_terms(p, [&](auto np) {
+        hipLaunchKernelGGL((conv_win_f16s_kernel<WC, WR, TC, TR, decltype(np)::value>), grid, dim3(64 * WC * WR), 0, stream, p);
+    });
     DFVO_HIP_CHECK(hipGetLastError());
-    if (g_prof) {
-        DFVO_HIP_CHECK(hipEventRecord(pe.e1, stream));
-        pe.flops = p.useful_flops;
-        const int sh[12] = {p.N, p.H, p.W, p.Ho, p.Wo, (p.G0 + p.G1) * 4, p.cout, p.kh, p.stride, (int)grid.x, (int)grid.y, 1};
-        for (int i = 0; i < 12; ++i) pe.shape[i] = sh[i];
-        g_prof->push_back(pe);
-    }
-    return DFVO_OK;
+    return prof.done((int)grid.x, (int)grid.y, 1);
 }
 
 // The first skeleton (two waves per SIMD) takes what the one-wave-per-SIMD skeleton of conv_win_f16s2.h leaves: layers with
@@ -304,54 +257,3 @@ static int launch_f16s_cfg(const ConvParams& p, hipStream_t stream, int cfg_id) 
 static int launch_f16s(const ConvParams& p, hipStream_t stream, int cfg_id) {
     return launch_f16s_cfg<1, 4, 1, 1>(p, stream, cfg_id);
 }
-
-// host side: f32 -> (hi, lo) exactly as split_f16_planes does on the device
-static unsigned long long g_f16s_clamped_host = 0;  // weights beyond f16's range at pack time (same report as the device counter)
-static inline void f16s_split_host(float x, unsigned short* hi, unsigned short* lo) {
-    float v = x < -F16S_MAX ? -F16S_MAX : (x > F16S_MAX ? F16S_MAX : x);
-    if (v != x && x == x) ++g_f16s_clamped_host;
-    const _Float16 h = (_Float16)v;
-    const _Float16 l = (_Float16)((v - (float)h) * F16S_LO_SCALE);
-    memcpy(hi, &h, 2);
-    memcpy(lo, &l, 2);
-}
-
-unsigned* conv_f16s_overflow_counter() { return f16s_clamp_counter(); }
-
-// number of threads (activations) + weights (pack time) that hit the +-65504 saturation of the hi plane since the last reset
-int conv_f16s_overflow_count(unsigned long long* n, int reset) {
-    unsigned int dev = 0;
-    DFVO_HIP_CHECK(hipMemcpyFromSymbol(&dev, HIP_SYMBOL(g_f16s_clamped), sizeof(dev)));
-    if (n) *n = (unsigned long long)dev + g_f16s_clamped_host;
-    if (reset) {
-        const unsigned int zero = 0;
-        DFVO_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_f16s_clamped), &zero, sizeof(zero)));
-        g_f16s_clamped_host = 0;
-    }
-    return DFVO_OK;
-}
-
-size_t conv_pack_weights_f16s(const float* w, int cout, int c0, int c1, const float* fold_scale, unsigned short* out) {
-    const int nch0 = (c0 + 15) / 16, nch1 = (c1 + 15) / 16, nch = nch0 + nch1;
-    const int cp = round_up(cout, 32);
-    const size_t total = (size_t)9 * nch * cp * 32;
-    if (!out) return total;
-    memset(out, 0, total * sizeof(unsigned short));
-    const int cin = c0 + c1;
-    for (int tap = 0; tap < 9; ++tap)
-        for (int c = 0; c < nch; ++c)
-            for (int co = 0; co < cout; ++co)
-                for (int k = 0; k < 16; ++k) {
-                    const bool s1 = c >= nch0;
-                    const int ch = s1 ? (c - nch0) * 16 + k : c * 16 + k;
-                    if (ch >= (s1 ? c1 : c0)) continue;
-                    const int ci = s1 ? c0 + ch : ch;
-                    float v = w[((size_t)co * cin + ci) * 9 + tap];
-                    if (fold_scale) v *= fold_scale[co];
-                    // [tap][chunk][cout / 32][plane][k / 8][cout % 32][k % 8]
-                    unsigned short* o = out + (((size_t)tap * nch + c) * cp + (co & ~31)) * 32 + ((k >> 3) * 32 + (co & 31)) * 8 + (k & 7);
-                    f16s_split_host(v, o, o + 512);
-                }
-    return total;
-}
-

@@ -317,37 +317,16 @@ __global__ __launch_bounds__(64 * WC * WR, 1) void conv_win_f16s2_mix_kernel(con
 }
 
 template <int WC, int WR, int TC, int TR>
-static long long f16s2_blocks(const ConvParams& p) {
-    constexpr int TH = WR * TR, BN = WC * TC * 32;
-    if (p.wf16_cout_pad % BN != 0) return 0;
-    return (long long)p.N * ((p.Ho + TH - 1) / TH) * ((p.Wo + 31) / 32) * (p.wf16_cout_pad / BN);
-}
-
-template <int WC, int WR, int TC, int TR>
 static int launch_f16s2_cfg(const ConvParams& p, hipStream_t stream, int cfg_id) {
     constexpr int TH = WR * TR, BN = WC * TC * 32;
     const int tiles = p.N * ((p.Ho + TH - 1) / TH) * ((p.Wo + 31) / 32);
     dim3 grid((unsigned)tiles, (unsigned)(p.wf16_cout_pad / BN), 1);
-    ConvProfEntry pe;
-    if (g_prof) {
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e0));
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e1));
-        pe.cfg = cfg_id;
-        DFVO_HIP_CHECK(hipEventRecord(pe.e0, stream));
-    }
-    if (p.f16_terms == 1)
-        hipLaunchKernelGGL((conv_win_f16s2_kernel<WC, WR, TC, TR, 1>), grid, dim3(64 * WC * WR), 0, stream, p);
-    else
-        hipLaunchKernelGGL((conv_win_f16s2_kernel<WC, WR, TC, TR, 3>), grid, dim3(64 * WC * WR), 0, stream, p);
+    ConvProfScope prof(p, stream, cfg_id);
+    with_f16_terms(p, [&](auto np) {
+        hipLaunchKernelGGL((conv_win_f16s2_kernel<WC, WR, TC, TR, decltype(np)::value>), grid, dim3(64 * WC * WR), 0, stream, p);
+    });
     DFVO_HIP_CHECK(hipGetLastError());
-    if (g_prof) {
-        DFVO_HIP_CHECK(hipEventRecord(pe.e1, stream));
-        pe.flops = p.useful_flops;
-        const int sh[12] = {p.N, p.H, p.W, p.Ho, p.Wo, (p.G0 + p.G1) * 4, p.cout, p.kh, p.stride, (int)grid.x, (int)grid.y, 2};
-        for (int i = 0; i < 12; ++i) pe.shape[i] = sh[i];
-        g_prof->push_back(pe);
-    }
-    return DFVO_OK;
+    return prof.done((int)grid.x, (int)grid.y, 2);
 }
 
 template <int WC, int WR, int TC, int TRA, int TRB>
@@ -357,26 +336,13 @@ static int launch_f16s2_mix(const ConvParams& p, hipStream_t stream, int cfg_id,
     const int na = p.N * (rows_a / THA) * tiles_x, na_pad = (na + 7) & ~7;
     const int nb = p.N * ((p.Ho - rows_a + THB - 1) / THB) * tiles_x;
     dim3 grid((unsigned)(na_pad + nb), (unsigned)(p.wf16_cout_pad / BN), 1);
-    ConvProfEntry pe;
-    if (g_prof) {
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e0));
-        DFVO_HIP_CHECK(hipEventCreate(&pe.e1));
-        pe.cfg = cfg_id;
-        DFVO_HIP_CHECK(hipEventRecord(pe.e0, stream));
-    }
-    if (p.f16_terms == 1)
-        hipLaunchKernelGGL((conv_win_f16s2_mix_kernel<WC, WR, TC, TRA, TRB, 1>), grid, dim3(64 * WC * WR), 0, stream, p, rows_a, na, na_pad, nb);
-    else
-        hipLaunchKernelGGL((conv_win_f16s2_mix_kernel<WC, WR, TC, TRA, TRB, 3>), grid, dim3(64 * WC * WR), 0, stream, p, rows_a, na, na_pad, nb);
+    ConvProfScope prof(p, stream, cfg_id);
+    with_f16_terms(p, [&](auto np) {
+        hipLaunchKernelGGL((conv_win_f16s2_mix_kernel<WC, WR, TC, TRA, TRB, decltype(np)::value>), grid, dim3(64 * WC * WR), 0, stream, p,
+                           rows_a, na, na_pad, nb);
+    });
     DFVO_HIP_CHECK(hipGetLastError());
-    if (g_prof) {
-        DFVO_HIP_CHECK(hipEventRecord(pe.e1, stream));
-        pe.flops = p.useful_flops;
-        const int sh[12] = {p.N, p.H, p.W, p.Ho, p.Wo, (p.G0 + p.G1) * 4, p.cout, p.kh, p.stride, (int)grid.x, (int)grid.y, 2};
-        for (int i = 0; i < 12; ++i) pe.shape[i] = sh[i];
-        g_prof->push_back(pe);
-    }
-    return DFVO_OK;
+    return prof.done((int)grid.x, (int)grid.y, 2);
 }
 
 // Greedy dispatch of `ca` tiles of cost `wa` followed by `cb` tiles of cost `wb` onto 256 CUs (one workgroup per CU): the time
@@ -442,7 +408,7 @@ static int launch_f16s2(const ConvParams& p, hipStream_t stream, int cfg_id) {
     // (per layer the two skeletons are within 2 % of each other; inside the pipeline this one gives +3 % pairs/s: half the
     // resident net waves next to the solver's kernels -- round 3)
     // DFVO_WIN_MIX=0: single-height launches only (the round 3-5 rule: the height that minimises rounds x rows)
-    static const bool mix_env = !(getenv("DFVO_WIN_MIX") && atoi(getenv("DFVO_WIN_MIX")) == 0);
+    static const bool mix_env = env_flag("DFVO_WIN_MIX", true);
     static const int force_tr = getenv("DFVO_WIN_FORCE_TR") ? atoi(getenv("DFVO_WIN_FORCE_TR")) : 0;  // (calibration hook: 2 / 3)
     if (force_tr == 2 || force_tr == 3) {
         if (p.wf16_cout_pad % 128 == 0) return force_tr == 3 ? launch_f16s2_cfg<2, 2, 2, 3>(p, stream, cfg_id) : launch_f16s2_cfg<2, 2, 2, 2>(p, stream, cfg_id);
@@ -453,14 +419,14 @@ static int launch_f16s2(const ConvParams& p, hipStream_t stream, int cfg_id) {
     const bool mix_ok = mix_env && p.f16_terms != 1;
     if (p.wf16_cout_pad % 128 == 0) {
         // (an 8-row tile -- 256 accumulator registers -- does not fit: the allocator spills inside the tap loop)
-        if (f16s2_blocks<2, 2, 2, 2>(p) < 200) return F16S2_NOT_APPLICABLE;
+        if (f16s_blocks<2, 2, 2, 2>(p) < 200) return F16S2_NOT_APPLICABLE;
         const int ra = f16s2_pick_rows_a(p, 6, 4, p.wf16_cout_pad / 128, mix_ok);
         if (ra >= p.Ho) return launch_f16s2_cfg<2, 2, 2, 3>(p, stream, cfg_id);
         if (ra <= 0) return launch_f16s2_cfg<2, 2, 2, 2>(p, stream, cfg_id);
         return launch_f16s2_mix<2, 2, 2, 3, 2>(p, stream, cfg_id, ra);
     }
     if (p.wf16_cout_pad % 64 == 0) {
-        if (f16s2_blocks<1, 4, 2, 2>(p) < 200) return F16S2_NOT_APPLICABLE;
+        if (f16s_blocks<1, 4, 2, 2>(p) < 200) return F16S2_NOT_APPLICABLE;
         const int ra = f16s2_pick_rows_a(p, 12, 8, p.wf16_cout_pad / 64, mix_ok);
         if (ra >= p.Ho) return launch_f16s2_cfg<1, 4, 2, 3>(p, stream, cfg_id);
         if (ra <= 0) return launch_f16s2_cfg<1, 4, 2, 2>(p, stream, cfg_id);
@@ -469,7 +435,7 @@ static int launch_f16s2(const ConvParams& p, hipStream_t stream, int cfg_id) {
     // 32-cout layers: single heights only.  Their 8-row shape needs 198 registers and runs TWO workgroups per CU; inside a mixed
     // launch it would carry the 12-row shape's 262 and run one (measured: 64 -> 32 44 -> 52 us, 32 -> 32 31 -> 34,
     // profiles/r6u_window_mixed_tiles.txt).
-    const long long b3 = f16s2_blocks<1, 4, 1, 3>(p), b2 = f16s2_blocks<1, 4, 1, 2>(p);
+    const long long b3 = f16s_blocks<1, 4, 1, 3>(p), b2 = f16s_blocks<1, 4, 1, 2>(p);
     if (b2 < 200) return F16S2_NOT_APPLICABLE;
     auto cost = [&](long long blocks, int rows) { return blocks <= 0 ? (1LL << 60) : ((blocks + 255) / 256) * rows; };
     if (cost(b3, 12) <= cost(b2, 8)) return launch_f16s2_cfg<1, 4, 1, 3>(p, stream, cfg_id);

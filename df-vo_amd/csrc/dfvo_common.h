@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/dfvo_hip.h"
@@ -35,6 +36,13 @@ const char* last_error();
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device function attribute: remembered per (device, kernel) so that a
 // process that drives several GPUs (dfvo_set_device) or several pipelines from different threads configures each one
 int ensure_dyn_lds(const void* kernel, size_t bytes);
+
+// a DFVO_* on / off switch of the environment: unset = dflt, else whether its integer value is non-zero.  The callers
+// read their switch once, into a function-local static.
+static inline bool env_flag(const char* name, bool dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) != 0 : dflt;
+}
 
 enum Act { ACT_NONE = 0, ACT_LEAKY = 1, ACT_RELU = 2, ACT_ELU = 3, ACT_SIGMOID = 4 };
 enum PadMode { PAD_ZERO = 0, PAD_REFLECT = 1 };
@@ -92,9 +100,9 @@ struct ConvParams {
     int tile_flags_n;
     // 2 * MACs of the unpadded convolution (bookkeeping for the bench's roofline leg; not read on device)
     double useful_flops;
-    // launch overrides chosen by the per-layer autotuner (0 = heuristic): M tile rows, split-K factor
+    // unused: padding of the kernel ABI (ConvParams is a kernel argument; no host or device code reads these)
     int force_bm, force_splits;
-    // the device counter of activations beyond f16's range (g_f16s_clamped of conv_win_f16s.h) for the f16 kernels that
+    // the device counter of activations beyond f16's range (g_f16s_clamped of conv_f16_clamp.h) for the f16 kernels that
     // live in their own translation units (conv_taps_f16s.hip: device symbols do not cross TUs)
     unsigned* f16s_clamp_ctr;
 };
@@ -140,13 +148,13 @@ int conv_split_mode();  // 0 exact fp32 (default), 4 = f16x3 (f16 hi/lo planes, 
 // (out may be null to query the size): [tap][chunk][cout_pad32][2][16], chunks = ceil(c0/16) + ceil(c1/16)
 size_t conv_pack_weights_f16s(const float* w_oihw, int cout, int c0, int c1, const float* fold_scale, unsigned short* out);
 unsigned* conv_f16s_overflow_counter();  // device address of the counter behind it (session.hip reads it behind each net)
-int conv_f16s_overflow_count(unsigned long long* n, int reset);  // saturation report of the f16x3 split (conv_win_f16s.h)
+int conv_f16s_overflow_count(unsigned long long* n, int reset);  // saturation report of the f16x3 split (conv_f16_clamp.h)
 void conv_build_f16g_table(int c0, int c1, int kh, int kw, std::vector<uint32_t>* tab);
 size_t conv_pack_weights_f16g(const float* w_oihw, int cout, int c0, int c1, int kh, int kw, const float* fold_scale,
                               unsigned short* out);
 size_t conv_pack_weights_f32g(const float* w_oihw, int cout, int c0, int c1, int kh, int kw, const float* fold_scale, float* out);
 bool conv_f32g_ok(const ConvParams& p);
-int launch_f32g(const ConvParams& p, hipStream_t stream, int* ksp_out, int* grid_x);
+int launch_f32g(const ConvParams& p, hipStream_t stream);
 size_t conv_head_weight_floats(int cout, int c0, int c1, int k);
 void conv_pack_head_weights(const float* w_oihw, int cout, int c0, int c1, int k, const float* fold_scale, float* out);
 void conv_pack_weights(const float* w_oihw, const float* bias, int cout, int c0, int c1, int kh, int kw,
@@ -157,5 +165,32 @@ constexpr int CONV_NUM_CFGS = 24;  // tile configurations of the implicit-GEMM k
 int launch_conv(const ConvParams& p, hipStream_t stream);
 void conv_profile_begin();
 int conv_profile_end(double* ms, double* flops, int* launches, double* bytes = nullptr);
+
+// One profiled launch (conv_igemm_f32.hip).  Between conv_profile_begin() and conv_profile_end() the constructor creates two
+// events and records the first on the stream, done() records the second and files the entry; a scope that is left without
+// done() -- an error return of the launcher -- destroys its events.  Outside a profile both do nothing.
+class ConvProfScope {
+  public:
+    ConvProfScope(const ConvParams& p, hipStream_t stream, int cfg_id);
+    ~ConvProfScope();
+    ConvProfScope(const ConvProfScope&) = delete;
+    ConvProfScope& operator=(const ConvProfScope&) = delete;
+    // after the launch(es): DFVO_OK, or DFVO_ERR_HIP if an event call failed.  gx gy gz: see ConvProfEntry
+    int done(int gx, int gy, int gz);
+
+  private:
+    const ConvParams& p_;
+    hipStream_t stream_;
+    int cfg_;
+    hipEvent_t e0_ = nullptr, e1_ = nullptr;
+    hipError_t err_ = hipSuccess;
+};
+
+// f(std::integral_constant<int, NP>) for the NP (products per term) of p.f16_terms: 1 = "f16" mode, 3 = f16x3.  An f16
+// launcher names its kernel once, as kernel<..., decltype(np)::value>, and both instantiations exist.
+template <class F>
+static inline auto with_f16_terms(const ConvParams& p, F&& f) {
+    return p.f16_terms == 1 ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 3>{});
+}
 
 }  // namespace dfvo

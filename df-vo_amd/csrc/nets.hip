@@ -236,7 +236,7 @@ int run_conv(const ConvLayer& L, int N, int H, int W, View s0, int up0, View s1,
     if (splitk_ws && splitk_ws->n > (size_t)(2 * SPLITK_TICKETS)) {  // the tail of the (zero-filled) workspace holds the tickets
         // DFVO_SPLITK_FUSED=0 (test hook, tests/test_nets_gpu.py): the separate ordered-reduction launch instead of the
         // in-kernel finish -- the reference form the fused one is compared with bit for bit
-        static const bool fused = !(getenv("DFVO_SPLITK_FUSED") && atoi(getenv("DFVO_SPLITK_FUSED")) == 0);
+        static const bool fused = env_flag("DFVO_SPLITK_FUSED", true);
         p.ws_floats = splitk_ws->n - SPLITK_TICKETS;
         if (fused) {
             p.tile_flags = reinterpret_cast<unsigned*>(splitk_ws->p + p.ws_floats);

@@ -449,7 +449,7 @@ int launch_deconv_dw(const float* src, int scs, int sco, int N, int H, int W, in
                      int dcs, int dco, hipStream_t s) {
     const int C4 = (C + 3) >> 2;
     if (((scs | sco | dcs | dco) & 3) == 0 && C4 * 4 <= scs - sco && C4 * 4 <= dcs - dco) {  // 16-byte views with room for the quad
-        static const bool blk = !(getenv("DFVO_DECONV_BLK") && atoi(getenv("DFVO_DECONV_BLK")) == 0);
+        static const bool blk = env_flag("DFVO_DECONV_BLK", true);
         if (blk && C4 * 4 * 16 * sizeof(float) <= 32 * 1024) {
             const long long totalb = (long long)N * H * W * C4;
             hipLaunchKernelGGL(k_deconv_dw4_blk, dim3(grid1d(totalb, 256)), dim3(256), (size_t)C4 * 4 * 16 * sizeof(float), s, src, scs, sco,
@@ -672,7 +672,7 @@ int launch_correlation(const float* f1, int cs1, int co1, const float* f2, int c
                        int H, int W, int C, int stride, float* dst, int dcs, float slope, hipStream_t s) {
     DFVO_ARG_CHECK(C % 4 == 0 && cs1 % 4 == 0 && cs2 % 4 == 0 && co1 % 4 == 0 && co2 % 4 == 0,
                    "correlation: alignment");
-    static const bool rt = !(getenv("DFVO_CORR_RT") && atoi(getenv("DFVO_CORR_RT")) == 0);
+    static const bool rt = env_flag("DFVO_CORR_RT", true);
     if (rt && C % 32 == 0 && C >= 32 && C <= 192) {
         switch (C / 32) {
             case 1: return launch_correlation_rt<1>(f1, cs1, co1, f2, cs2, co2, swap2, N, H, W, stride, dst, dcs, slope, s);
@@ -790,7 +790,7 @@ __global__ __launch_bounds__(256) void k_reg_head_v(const float* __restrict__ di
 int launch_reg_head(const float* dist, int dist_cs, int k, const float* flow, int fcs, int fco, const float* wx,
                     float bx, const float* wy, float by, int N, int H, int W, float* dst, int dcs, int dco,
                     hipStream_t s) {
-    static const bool vec = !(getenv("DFVO_REG_HEAD_V") && atoi(getenv("DFVO_REG_HEAD_V")) == 0);
+    static const bool vec = env_flag("DFVO_REG_HEAD_V", true);
     const dim3 grid(grid1d((long long)N * H * W, 256));
     const bool aligned = dist_cs % 4 == 0 && ((uintptr_t)dist & 15) == 0 && dist_cs >= ((k * k + 3) & ~3) && fcs % 2 == 0 &&
                          fco % 2 == 0 && ((uintptr_t)flow & 7) == 0 && dcs % 2 == 0 && dco % 2 == 0 && ((uintptr_t)dst & 7) == 0;

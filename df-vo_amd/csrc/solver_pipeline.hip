@@ -1859,7 +1859,7 @@ int enqueue_pose_h_part(TrackerBuffers& tb, int n_bound, const PoseConfig& cfg, 
     // the five-point sampler's first chunk of subsets depends on the keypoint COUNT only: drawn here, beside the homography
     // chain, instead of inside the RandomState-ordered chain (round 6; consumed by enqueue_pose_e_part through tb.e_pre_*)
     tb.e_pre_iters = 0;
-    static const bool subsets_ahead = !(getenv("DFVO_E_SUBSETS_AHEAD") && atoi(getenv("DFVO_E_SUBSETS_AHEAD")) == 0);  // (0: A/B hook)
+    static const bool subsets_ahead = env_flag("DFVO_E_SUBSETS_AHEAD", true);  // (0: A/B hook)
     if (subsets_ahead && cfg.max_iters >= 1) {
         int rc_pre = enqueue_e_subsets_prefetch(tb.ws_rep[0], tb.kp_info, n_bound, cfg.max_iters,
                                                 reinterpret_cast<unsigned long long*>(tb.kp_total + 72), sh);
