@@ -127,6 +127,19 @@ SIGNATURES = {
     "dfvo_session_keypoints": (_i, [_vp, C.c_longlong, _vp, C.POINTER(_vp), C.POINTER(_vp), _ip, _ip]),
     "dfvo_session_pose_ahead": (_i, [_vp, C.c_longlong, _vp, _vp, _ip]),
     "dfvo_session_pose_2d2d": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _ip]),
+    "dfvo_vis_create": (_i, [_i, _i, C.POINTER(_vp)]),
+    "dfvo_vis_destroy": (None, [_vp]),
+    "dfvo_vis_cell_rect": (_i, [_vp, _i, _ip]),
+    "dfvo_vis_draw_flow": (_i, [_vp, _i, _vp, _i, _i, C.POINTER(C.c_longlong)]),
+    "dfvo_vis_draw_map": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _d, C.POINTER(_d)]),
+    "dfvo_vis_draw_session": (_i, [_vp, _vp, C.c_longlong, _i, _d, _i, _d, C.POINTER(C.c_longlong), C.POINTER(_d)]),
+    "dfvo_vis_session_cells": (_i, [_vp, C.c_longlong, _ip]),
+    "dfvo_vis_clear_cell": (_i, [_vp, _i]),
+    "dfvo_vis_fetch": (_i, [_vp, _i, _vp]),
+    "dfvo_vis_counters": (_i, [_vp, C.POINTER(C.c_longlong)]),
+    "dfvo_vis_device_ms": (_i, [_vp, C.POINTER(_f)]),
+    "dfvo_vis_flow_rgb": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_longlong)]),
+    "dfvo_vis_disparity_percentile90": (_i, [_vp, _vp, _i, _i, C.POINTER(_d)]),
     "dfvo_set_conv_precision": (_i, [C.c_char_p]),
     "dfvo_get_conv_precision": (C.c_char_p, []),
     "dfvo_set_sklearn_compat": (_i, [C.c_char_p]),

@@ -95,6 +95,10 @@ struct FlowNet {
     DevBuf u8_ref, u8_cur;  // staging for the host-pointer entry point
     DevBuf splitk;          // split-K partial sums of the small-grid convs (own buffer: the nets run on separate streams)
     DevBuf out_fwd, out_bwd, out_diff;
+    // counts the forward() calls: every one overwrites the output buffers it is handed (out_fwd / out_bwd / out_diff for the
+    // host-array entry points and the frame session).  A holder of device-resident outputs remembers the count of ITS pass
+    // and knows them overwritten when it has moved on (session.hip: dfvo_session_vis_sources)
+    unsigned long long out_epoch = 0;
     double flops_last = 0.0;  // useful conv+corr FLOPs of the last forward (2*MAC)
     // ... of its parts: Features on both frames / on the current frame alone (carried mode) / everything behind them
     double flops_feat2 = 0.0, flops_feat1 = 0.0, flops_levels = 0.0;
@@ -141,6 +145,7 @@ struct DepthNet {
     DevBuf x0, f0, pool, tmp[4], feat[5], blk_t, blk_ds, blk_o[2], du[5], dx[5], disp, depth;
     DevBuf u8_in;
     DevBuf splitk;
+    unsigned long long out_epoch = 0;  // forward() calls so far (see FlowNet::out_epoch)
     double flops_last = 0.0;
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;

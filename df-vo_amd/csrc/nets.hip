@@ -696,6 +696,7 @@ int FlowNet::forward(const uint8_t* d_ref, const uint8_t* d_cur, float* d_fwd, f
         return DFVO_ERR_STATE;
     }
     DFVO_ARG_CHECK(d_cur && (d_ref || carry_from), "FlowNet::forward: null frame");
+    ++out_epoch;
     if (!e_feat) DFVO_HIP_CHECK(hipEventCreateWithFlags(&e_feat, hipEventDisableTiming));
     if (!tuned_once) {  // first call: one eager run before any graph capture (lazy allocations, dynamic-LDS attributes)
         DFVO_TRY(enqueue_input(d_ref, d_cur));
@@ -984,6 +985,7 @@ int DepthNet::forward(const uint8_t* d_img, float* d_depth) {
         set_last_error("DepthNet::forward before finalize");
         return DFVO_ERR_STATE;
     }
+    ++out_epoch;
     if (!tuned_once) {  // one eager run before any graph capture
         int rc = enqueue(d_img, d_depth);
         if (rc != DFVO_OK) return rc;

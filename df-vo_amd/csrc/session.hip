@@ -33,6 +33,7 @@
 
 #include "capi_types.h"
 #include "ops.h"
+#include "vis.h"
 
 using namespace dfvo;
 
@@ -51,6 +52,10 @@ struct dfvo_session {
     bool carry_ok = false;       // the flow net's current-frame pyramids are those of frame `gen`
     bool have_flow = false;      // a flow pass of (gen - 1, gen) is enqueued / done
     bool have_kp = false, have_h = false;
+    // FlowNet / DepthNet::out_epoch right after this generation's passes: while they still stand, the nets' output buffers hold
+    // this generation (a plain pass on the same net -- forward_flow on another pair, forward_depth on a frame the session does
+    // not take -- overwrites them without touching gen or the host ring)
+    unsigned long long flow_epoch = 0, depth_epoch = 0;
     bool have_e = false;         // the RandomState-consuming half of compute_pose_2d2d is enqueued (dfvo_session_pose_ahead)
     uint32_t rng_ahead[625] = {};            // ... under this RandomState
     unsigned char ahead_cfg[sizeof(dfvo_pose2d2d_cfg)] = {};  // ... and this configuration (bytes)
@@ -127,6 +132,24 @@ static int place_streams(dfvo_session* s) {
         }
     }
     pool.release();
+    return DFVO_OK;
+}
+
+// the drawer's view of the newest generation (vis.hip: dfvo_vis_draw_session): the nets' own output buffers, which the next
+// push overwrites, and the events recorded behind the nets.  Read-only: no flag, counter or buffer of the session changes.
+int dfvo_session_vis_sources(dfvo_session* s, long long generation, dfvo::VisSessionSources* out) {
+    DFVO_ARG_CHECK(s && out, "dfvo_session_vis_sources: bad argument");
+    DFVO_ARG_CHECK(generation == s->gen && s->gen >= 0, "dfvo_session_vis_sources: not the newest pushed frame");
+    out->fwd = s->f->net.out_fwd.p;
+    out->bwd = s->f->net.out_bwd.p;
+    out->diff = s->f->net.out_diff.p;
+    out->depth = s->d->net.depth.p;
+    out->H = s->H, out->W = s->W;
+    out->depth_h = s->d->net.H, out->depth_w = s->d->net.W;
+    out->e_net = s->e_net, out->e_depth = s->e_depth;
+    // the nets' output buffers still hold this generation only if no other pass ran on the nets since the push
+    out->have_flow = s->have_flow && s->f->net.out_epoch == s->flow_epoch;
+    out->have_depth = s->d->net.out_epoch == s->depth_epoch;
     return DFVO_OK;
 }
 
@@ -273,6 +296,7 @@ int dfvo_session_push_frame(dfvo_session* s, const uint8_t* h_img, const dfvo_se
                 S_TRY(fn.forward(nullptr, img, fn.out_fwd.p, fn.out_bwd.p, fn.out_diff.p, &fn));
             else
                 S_TRY(fn.forward(s->d_img[(g - 1) & 1], img, fn.out_fwd.p, fn.out_bwd.p, fn.out_diff.p));
+            s->flow_epoch = fn.out_epoch;
             DFVO_HIP_CHECK(hipEventRecord(s->e_net, fn.stream));
             if (s->trace) DFVO_HIP_CHECK(hipEventRecord(s->t_flow, fn.stream));
             DFVO_HIP_CHECK(hipMemcpyAsync(&s->h_ovf[slot][0], s->d_ovf, sizeof(unsigned), hipMemcpyDeviceToHost, fn.stream));
@@ -297,6 +321,7 @@ int dfvo_session_push_frame(dfvo_session* s, const uint8_t* h_img, const dfvo_se
         DFVO_HIP_CHECK(hipStreamWaitEvent(dn.stream, s->e_img, 0));
         S_TRY(s->d->resize.enqueue(img, (uint8_t*)dn.u8_in.p, dn.stream));
         S_TRY(dn.forward((const uint8_t*)dn.u8_in.p, dn.depth.p));
+        s->depth_epoch = dn.out_epoch;
         DFVO_HIP_CHECK(hipMemcpyAsync(s->h_depth[slot], dn.depth.p, dpx * sizeof(float), hipMemcpyDeviceToHost, dn.stream));
         DFVO_HIP_CHECK(hipMemcpyAsync(&s->h_ovf[slot][1], s->d_ovf, sizeof(unsigned), hipMemcpyDeviceToHost, dn.stream));
         DFVO_HIP_CHECK(hipEventRecord(s->e_depth, dn.stream));

@@ -291,6 +291,31 @@ class FrameSession:
         # (owned copies: no view of the keypoint ring leaves the session)
         return np.array(_pinned(pr, C.c_double, (nn, 2))), np.array(_pinned(pc, C.c_double, (nn, 2))), nn, int(good.value)
 
+    # -- the drawer's dense panels (libs/general/frame_drawer.py) ---------------------------------------------------------
+    def vis_is_buffer(self, arr, name):
+        """_is_buffer for the drawer: the consistency map arrives as a [H,W] view of the [H,W,1] copy (kp_selection reshapes
+        it: np.asarray(copy).reshape(h, w) is a plain view of a plain view of the copy), which keeps no token of its own --
+        the token of the array that owns its memory is accepted; the whole contents are compared either way"""
+        tok, owner = getattr(arr, "_dfvo_tok", None), arr
+        while tok is None and isinstance(getattr(owner, "base", None), np.ndarray):
+            owner = owner.base
+            tok = getattr(owner, "_dfvo_tok", None)
+        if tok != (self.sid, self.gen, name) or self.flow_views is None or self.flow_views[0] != self.gen:
+            return False
+        mine = np.asarray(self.flow_views[1 + ("fwd", "bwd", "diff").index(name)])
+        a = np.asarray(arr)
+        return a.dtype == mine.dtype and a.size == mine.size and a.flags["C_CONTIGUOUS"] and same_bytes(a.reshape(mine.shape), mine)
+
+    def vis_is_depth(self, arr):
+        """is `arr` the raw depth of the newest generation, byte for byte?  (It is when the caller's image size is the depth
+        net's feed size: dfvo.py:314-317 resizes it otherwise, and the resized map is uploaded.)"""
+        if not (isinstance(arr, np.ndarray) and arr.dtype == np.float32 and arr.shape == (self.fh, self.fw) and self.gen >= 0):
+            return False
+        p = C.c_void_p()
+        if self.lib.dfvo_session_depth(self.handle, self.gen, C.byref(p)) != 0:
+            return False
+        return same_bytes(np.ascontiguousarray(arr), _pinned(p, C.c_float, (self.fh, self.fw)))
+
     # -- EssTracker.compute_pose_2d2d ------------------------------------------------------------------------------
     def pose_2d2d(self, kp_ref, kp_cur, n, cfg, out, inliers, rng_words):
         """rng_words: np.random's state at this call (625 uint32); the advanced state is left on the device"""

@@ -594,6 +594,65 @@ int dfvo_session_pose_ahead(dfvo_session* s, long long generation, const uint32_
 int dfvo_session_pose_2d2d(dfvo_session* s, const double* h_kp_ref, const double* h_kp_cur, int n, const dfvo_pose2d2d_cfg* cfg,
                            dfvo_pose2d2d_out* out, uint8_t* h_inliers, const uint32_t* h_rng625, int* used_resident);
 
+/* ---- the dense panels of the frame drawer (libs/general/frame_drawer.py:410-512) ----
+ * FrameDrawer.main draws, per frame, the depth / disparity map (matplotlib magma), the forward and backward flow
+ * (flowlib.flow_to_image: the Middlebury wheel) and the consistency maps (jet), each cvtColor'ed to BGR and cv2.resize'd into
+ * a cell of the window.  dfvo_vis owns the window canvas (uint8 BGR [window_h, window_w, 3], zero at creation) in HBM and the
+ * reference's quarter-grid rectangles int(h / 4 * r), int(w / 4 * c):
+ *     DFVO_VIS_CELL_DEPTH rows 2-3 cols 2-3 | DFVO_VIS_CELL_FLOW1 rows 2-3 cols 3-4
+ *     DFVO_VIS_CELL_FLOW2 rows 3-4 cols 2-3 ('flow2', 'rigid_flow_diff' and 'warp_diff' share it) | DFVO_VIS_CELL_OPT_FLOW_DIFF rows 3-4 cols 3-4
+ * A draw call colours only the <= 4 source pixels a cell pixel samples and blends them with dfvo_resize_linear_u8's
+ * arithmetic (the exact-half area path included); what needs the whole map -- the maximum flow radius, the exact 90th
+ * percentile of the disparity -- runs in front of it on the device.  Results equal the reference's numpy (NEP 50) /
+ * matplotlib arithmetic; maps of up to 1280 x 1920.  Every draw call returns when the cell is drawn. */
+typedef struct dfvo_vis dfvo_vis;
+#define DFVO_VIS_CELLS 4
+#define DFVO_VIS_CELL_DEPTH 0
+#define DFVO_VIS_CELL_FLOW1 1
+#define DFVO_VIS_CELL_FLOW2 2
+#define DFVO_VIS_CELL_OPT_FLOW_DIFF 3
+#define DFVO_VIS_MAP_VALUE 0     /* colour the map itself: Normalize(0, vmax) */
+#define DFVO_VIS_MAP_DISPARITY 1 /* colour 1 / (map + 1e-3), map == 0 -> 0; vmax = np.percentile(.., 90) */
+#define DFVO_VIS_MAGMA 0
+#define DFVO_VIS_JET 1
+#define DFVO_VIS_COUNTERS 8
+int dfvo_vis_create(int window_h, int window_w, dfvo_vis** out);
+void dfvo_vis_destroy(dfvo_vis* v);
+int dfvo_vis_cell_rect(const dfvo_vis* v, int cell, int* y0x0y1x1);
+/* draw_flow (frame_drawer.py:446-459): h_flow float [2, H, W].  *n_unknown = pixels with |u| or |v| > 1e7: flow_to_image
+ * zeroes those in the CALLER's array (flowlib.py:203-205); a caller that mirrors it applies that write when the count is not 0. */
+int dfvo_vis_draw_flow(dfvo_vis* v, int cell, const float* h_flow, int H, int W, long long* n_unknown);
+/* draw_depth / draw_flow_consistency / draw_rigid_flow_consistency (:410-444, 461-512): h_map float32 / float64 [H, W].
+ * kind DFVO_VIS_MAP_VALUE uses vmax_in; DFVO_VIS_MAP_DISPARITY computes it.  *vmax_out = the vmax used; when it is negative
+ * matplotlib's Normalize raises and the cell is left as it was. */
+int dfvo_vis_draw_map(dfvo_vis* v, int cell, const void* h_map, int is_f64, int H, int W, int kind, int cmap, double vmax_in,
+                      double* vmax_out);
+/* The panels of the session's newest generation from its device-resident buffers, behind the events that guard them, in ONE
+ * panel launch: cells = bit mask (1 << DFVO_VIS_CELL_*): FLOW1 forward flow, FLOW2 backward flow, OPT_FLOW_DIFF the
+ * consistency map (jet, diff_vmax), DEPTH the raw depth [feed_h, feed_w] (magma; depth_kind / depth_vmax as in
+ * dfvo_vis_draw_map).  n_unknown2[2]: unknown pixels of the forward / backward flow.  Reads the session, changes nothing in it.
+ * DFVO_ERR_STATE when a requested buffer no longer holds that generation (dfvo_vis_session_cells). */
+int dfvo_vis_draw_session(dfvo_vis* v, dfvo_session* s, long long generation, int cells, double diff_vmax, int depth_kind,
+                          double depth_vmax, long long* n_unknown2, double* depth_vmax_out);
+/* Which cells dfvo_vis_draw_session can serve now (bit mask): the session's device buffers are the nets' own output buffers,
+ * and any other pass on the same net (dfvo_flownet_forward_host on another pair, dfvo_depthnet_forward* on another frame)
+ * overwrites them while the session's generation and pinned host copies stay.  A cell whose bit is clear must be drawn from
+ * the host array (dfvo_vis_draw_flow / _map); dfvo_vis_draw_session returns DFVO_ERR_STATE for it. */
+int dfvo_vis_session_cells(dfvo_session* s, long long generation, int* cells);
+int dfvo_vis_clear_cell(dfvo_vis* v, int cell);
+/* cell >= 0: that cell, uint8 BGR [cell_h, cell_w, 3]; cell = -1: the whole canvas */
+int dfvo_vis_fetch(dfvo_vis* v, int cell, uint8_t* h_dst);
+/* counters since creation: [0] panels drawn from session buffers, [1] panels drawn from uploaded arrays, [2] panel launches,
+ * [3] percentile selects, [4] cells cleared, [5] bytes uploaded, [6] bytes fetched, [7] 0 */
+int dfvo_vis_counters(const dfvo_vis* v, long long* out);
+/* device time of the last draw call (reductions + panel launch), from HIP events */
+int dfvo_vis_device_ms(const dfvo_vis* v, float* ms);
+/* flowlib.flow_to_image at full resolution: h_rgb uint8 RGB [H, W, 3] */
+int dfvo_vis_flow_rgb(dfvo_vis* v, const float* h_flow, int H, int W, uint8_t* h_rgb, long long* n_unknown);
+/* np.percentile(disparity, 90) of h_depth[n] (float32 / float64), exact: the two neighbouring order statistics by a radix
+ * select, numpy's _lerp; *out = the value widened to double */
+int dfvo_vis_disparity_percentile90(dfvo_vis* v, const void* h_depth, int is_f64, int n, double* out);
+
 /* DFVO.update_global_pose (dfvo.py:109-119: t_w += R_w t, then R_w = R_w R) over a whole gathered sequence in ONE launch,
  * constant-motion rows included (dfvo.py:157-161: a row with status 1 reuses the previous pair's relative motion).
  * rows [n][17] = relative pose cur -> ref (4x4 row major) | status (the layout of dist.allgather_poses); first [16] = pose
