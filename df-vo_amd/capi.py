@@ -144,6 +144,9 @@ SIGNATURES = {
     "dfvo_get_conv_precision": (C.c_char_p, []),
     "dfvo_set_sklearn_compat": (_i, [C.c_char_p]),
     "dfvo_f16s_overflow_count": (_i, [C.POINTER(C.c_ulonglong), _i]),
+    "dfvo_set_fp32_winograd": (_i, [_i]),
+    "dfvo_get_fp32_winograd": (_i, []),
+    "dfvo_fp32_winograd_launches": (_i, [C.POINTER(C.c_ulonglong), _i]),
     "dfvo_conv_profile_begin": (_i, []),
     "dfvo_conv_profile_end": (_i, [_vp, _vp, _vp]),
     "dfvo_conv_profile_end_bytes": (_i, [_vp, _vp, _vp, _vp]),

@@ -93,33 +93,25 @@ int dfvo_conv2d(const dfvo_conv_desc* d, const float* d_src0, const float* d_src
     std::vector<float> pw((size_t)(ksteps * 4 + 8) * cout_pad * 4), pb(cout_pad);  // slack: see make_conv
     conv_pack_weights(h_w, h_bias, d->cout, d->c0, d->c1, d->kh, d->kw, cout_pad, nullptr, nullptr, pw.data(),
                       pb.data());
-    float *dw = nullptr, *db = nullptr;
-    DFVO_HIP_CHECK(hipMalloc((void**)&dw, pw.size() * sizeof(float)));
-    DFVO_HIP_CHECK(hipMalloc((void**)&db, pb.size() * sizeof(float)));
-    DFVO_HIP_CHECK(hipMemcpy(dw, pw.data(), pw.size() * sizeof(float), hipMemcpyHostToDevice));
-    DFVO_HIP_CHECK(hipMemcpy(db, pb.data(), pb.size() * sizeof(float), hipMemcpyHostToDevice));
-    ConvLayer L;
-    L.wp = dw;
-    if (make_f16s_weights(h_w, d->cout, d->c0, d->c1, d->kh, d->kw, nullptr, &L) != DFVO_OK) {
-        (void)hipFree(dw);
-        (void)hipFree(db);
-        return DFVO_ERR_HIP;
-    }
-    if (make_f16g_weights(h_w, d->cout, d->c0, d->c1, d->kh, d->kw, nullptr, &L) != DFVO_OK) {
-        (void)hipFree(dw);
-        (void)hipFree(db);
-        if (L.wf) (void)hipFree(L.wf);
-        return DFVO_ERR_HIP;
-    }
-    {
-        const int hrc = make_head_weights(h_w, d->cout, d->c0, d->c1, d->kh, d->kw, nullptr, &L.wh);
-        if (hrc != DFVO_OK) {
-            (void)hipFree(dw);
-            (void)hipFree(db);
-            return hrc;
-        }
-    }
-    L.bias = db;
+    ConvLayer L;  // every packing of the layer is released by free_conv, on every path
+    struct Release {
+        ConvLayer* l;
+        ~Release() { free_conv(l); }
+    } release{&L};
+    DFVO_HIP_CHECK(hipMalloc((void**)&L.wp, pw.size() * sizeof(float)));
+    DFVO_HIP_CHECK(hipMalloc((void**)&L.bias, pb.size() * sizeof(float)));
+    DFVO_HIP_CHECK(hipMemcpy(L.wp, pw.data(), pw.size() * sizeof(float), hipMemcpyHostToDevice));
+    DFVO_HIP_CHECK(hipMemcpy(L.bias, pb.data(), pb.size() * sizeof(float), hipMemcpyHostToDevice));
+    API_TRY(make_f16s_weights(h_w, d->cout, d->c0, d->c1, d->kh, d->kw, nullptr, &L));
+    API_TRY(make_f16g_weights(h_w, d->cout, d->c0, d->c1, d->kh, d->kw, nullptr, &L));
+    L.stride = d->stride;
+    L.pad_h = d->pad_h;
+    L.pad_w = d->pad_w;
+    L.pad_mode = d->pad_mode;
+    L.m_hint = M;
+    API_TRY(make_wino_weights(h_w, d->cout, d->c0, d->c1, d->kh, d->kw, nullptr,
+                              d->stride == 1 && d->pad_h == 1 && d->pad_w == 1 && d->pad_mode == PAD_ZERO && d->up0 == 0, &L));
+    API_TRY(make_head_weights(h_w, d->cout, d->c0, d->c1, d->kh, d->kw, nullptr, &L.wh));
     L.cout = d->cout;
     L.cout_pad = cout_pad;
     L.c0 = d->c0;
@@ -127,10 +119,6 @@ int dfvo_conv2d(const dfvo_conv_desc* d, const float* d_src0, const float* d_src
     L.kh = d->kh;
     L.kw = d->kw;
     L.ksteps = ksteps;
-    L.stride = d->stride;
-    L.pad_h = d->pad_h;
-    L.pad_w = d->pad_w;
-    L.pad_mode = d->pad_mode;
     L.act = d->act;
     L.act_param = d->act_param;
     // split-K workspace + tile tickets (as the nets own one each): process-wide, calls are serialised by the sync below
@@ -141,14 +129,7 @@ int dfvo_conv2d(const dfvo_conv_desc* d, const float* d_src0, const float* d_src
     int rc = run_conv(L, d->N, d->H, d->W, View{d_src0, d->cs0, d->co0}, d->up0, View{d_src1, d->cs1, d->co1}, d_res,
                       d->res_cs, d->res_co, d_dst, d->dst_cs, d->dst_co, d->dst_zero_to, s, nullptr,
                       conv2d_ws.p ? &conv2d_ws : nullptr);
-    hipError_t e = hipStreamSynchronize(s);
-    (void)hipFree(dw);
-    (void)hipFree(db);
-    if (L.wh) (void)hipFree(L.wh);
-    if (L.wf) (void)hipFree(L.wf);
-    if (L.wg) (void)hipFree(L.wg);
-    if (L.wg32) (void)hipFree(L.wg32);
-    if (L.gtab) (void)hipFree(L.gtab);
+    hipError_t e = hipStreamSynchronize(s);  // (before the weights are released)
     if (rc != DFVO_OK) return rc;
     DFVO_HIP_CHECK(e);
     return DFVO_OK;
@@ -157,6 +138,9 @@ int dfvo_conv2d(const dfvo_conv_desc* d, const float* d_src0, const float* d_src
 int dfvo_set_conv_precision(const char* name) { return conv_set_precision(name); }
 const char* dfvo_get_conv_precision(void) { return conv_get_precision(); }
 int dfvo_f16s_overflow_count(unsigned long long* h_count, int reset) { return conv_f16s_overflow_count(h_count, reset); }
+int dfvo_set_fp32_winograd(int mode) { return conv_set_fp32_winograd(mode); }
+int dfvo_get_fp32_winograd(void) { return conv_fp32_winograd_mode(); }
+int dfvo_fp32_winograd_launches(unsigned long long* h_count, int reset) { return conv_fp32_winograd_launches(h_count, reset); }
 
 int dfvo_conv_profile_begin(void) {
     conv_profile_begin();

@@ -6,7 +6,8 @@
 //   3. the per-launch profile: ConvProfEntry, ConvProfScope (declared in dfvo_common.h: the kernels of conv_gemm_f32g.hip
 //      and conv_taps_f16s.hip, translation units of their own, are profiled through it too), conv_profile_begin / _end
 //   4. the f16 families, included: conv_pack_f16s.h (host packers; pulls in conv_f16_clamp.h, the saturation counter, and
-//      conv_f16_split.h, the plane split), conv_win_f16s.h, conv_gemm_f16s.h, conv_win_f16s2.h -- kernels and launchers each
+//      conv_f16_split.h, the plane split), conv_win_f16s.h, conv_gemm_f16s.h, conv_win_f16s2.h -- kernels and launchers each;
+//      conv_wino_f32.h: the opt-in fp32 Winograd F(2x2,3x3) kernel, its switch and launcher (conv_pack_wino_f32.h: its packer)
 //   5. the fp32 launchers (conv_splitk_slices, launch_splitk, launch_cfg, launch_win3, launch_head), the tile rules, and
 //      launch_conv()
 //
@@ -870,6 +871,7 @@ int conv_profile_end(double* ms, double* flops, int* launches, double* bytes) {
 #include "conv_win_f16s.h"
 #include "conv_gemm_f16s.h"
 #include "conv_win_f16s2.h"
+#include "conv_wino_f32.h"
 
 // Split-K when the grid cannot fill the chip (fewer than 600 workgroups): the number of K slices for `units` units of K
 // (K-steps, or channel chunks) with at least `min_per_slice` units each, at most `cap`, partials [slices][M][cout_pad] inside p.ws
@@ -957,6 +959,27 @@ static bool conv_use_window(const ConvParams& p, int bn) {
     return (p.kh == 5 || p.kh == 7) && bn == 16 && (p.G0 + p.G1) >= 4 && M >= 8000;
 }
 
+// the profile row (12-15) of the window kernel's tile class for a 3x3 layer: launch_conv's window branch and the Winograd
+// launcher (which files its launches under the row of the class they replace) both go by it.  Under
+// dfvo_set_fp32_winograd(2), the unit-test mode, layers that never were window layers (bn 16, small maps) land on a row too.
+static int conv_window_cfg(const ConvParams& p, int bn) {
+    const long long tiles8 = (long long)p.N * ((p.Ho + 7) / 8) * ((p.Wo + 15) / 16) * (p.cout_pad / bn);
+    // 128-wide layers on the largest maps run as two 64-wide column blocks: 2x the workgroups at 4 (instead of 3) per CU
+    // shortens the under-filled last round of the grid (+5 % measured at 2 x 192 x 624)
+    if (bn == 128) return tiles8 >= 1200 ? 13 : (tiles8 >= 400 ? 12 : 15);
+    return bn == 64 ? 13 : 14;
+}
+// fp32 Winograd under dfvo_set_fp32_winograd(1), EXPERIMENTAL: the window kernel's own size rule without the 32-wide class,
+// whose Winograd workgroup is two waves (half of a CU's SIMDs).  A class stays here only where tools/wino_bench.py shows
+// Winograd at <= 0.90 x the direct kernel's time (DESIGN.md section 5d holds the table this rule goes by)
+constexpr long long WINO_MIN_PIXELS = 30000;  // conv_use_window's
+bool conv_wino_rule_may_accept(int cout, long long max_pixels) {
+    return conv_pick_bn(cout, max_pixels) >= 64 && (max_pixels <= 0 || max_pixels >= WINO_MIN_PIXELS);
+}
+static bool conv_wino_size_rule(const ConvParams& p, int bn) {
+    return conv_use_window(p, bn) && conv_wino_rule_may_accept(p.cout, (long long)p.N * p.Ho * p.Wo);
+}
+
 // Tile choice: the widest N tile the layer's cout allows (conv_pick_bn); the M tile from a sweep on MI355X
 // (tools/sweep_conv.sh): 64-row tiles win or tie on every layer with BN <= 64 and on BN = 128 below ~1200
 // workgroups (more resident workgroups hide the global -> LDS staging latency; the per-tap gather is served by
@@ -984,7 +1007,7 @@ static bool conv_f32g_takes(const ConvParams& p, int bn) {
     return M <= 8192;  // pyramid levels 5 / 6 (2 x 11 x 38 .. 2 x 44 x 152) and the depth net's 6 x 20 .. 48 x 160 maps
 }
 
-int launch_conv(const ConvParams& p, hipStream_t stream) {
+int launch_conv(const ConvParams& p, hipStream_t stream, bool wino_all) {
     const long long M = (long long)p.N * p.Ho * p.Wo;
     const int bn = conv_pick_bn(p.cout, M);
     DFVO_ARG_CHECK(p.cout_pad % bn == 0, "launch_conv: cout_pad not a multiple of the N tile");
@@ -1000,19 +1023,19 @@ int launch_conv(const ConvParams& p, hipStream_t stream) {
         return rc2 != F16S2_NOT_APPLICABLE ? rc2 : launch_f16s(p, stream, 19);  // errors (negative) propagate
     }
     if (conv_f16g_ok(p)) return launch_f16g(p, stream);  // f16x3: everything else (small maps, 1x1, k x 1, stride 2, 7x7)
+    // fp32 Winograd (opt-in, decided when the layer was packed): ahead of every direct fp32 kernel.  Its launches are filed
+    // under the window row of the tile class they replace, with the direct convolution's FLOP count
+    if (conv_wino_applicable(p) && (wino_all || conv_wino_size_rule(p, bn))) return launch_wino(p, stream, conv_window_cfg(p, bn));
     if (conv_f32g_ok(p) && conv_f32g_takes(p, bn)) return launch_f32g(p, stream);  // exact fp32: the same skeleton on fp32 MFMAs
     if (conv_use_window(p, bn) && p.kh == 7) return launch_win3<4, 1, 2, 1, 7>(p, stream, 16);
     if (conv_use_window(p, bn) && p.kh == 5) return launch_win3<4, 1, 2, 1, 5>(p, stream, 17);
     if (conv_use_window(p, bn)) {
-        const long long tiles8 = (long long)p.N * ((p.Ho + 7) / 8) * ((p.Wo + 15) / 16) * (p.cout_pad / bn);
-        if (bn == 128) {
-            // 128-wide layers on the largest maps run as two 64-wide column blocks: 2x the workgroups at 4 (instead
-            // of 3) per CU shortens the under-filled last round of the grid (+5 % measured at 2 x 192 x 624)
-            if (tiles8 >= 1200) return launch_win3<2, 2, 4, 2>(p, stream, 13);
-            return tiles8 >= 400 ? launch_win3<2, 2, 4, 4>(p, stream, 12) : launch_win3<1, 4, 4, 2>(p, stream, 15);
+        switch (conv_window_cfg(p, bn)) {
+            case 12: return launch_win3<2, 2, 4, 4>(p, stream, 12);
+            case 13: return launch_win3<2, 2, 4, 2>(p, stream, 13);
+            case 15: return launch_win3<1, 4, 4, 2>(p, stream, 15);
+            default: return launch_win3<4, 1, 2, 2>(p, stream, 14);
         }
-        if (bn == 64) return launch_win3<2, 2, 4, 2>(p, stream, 13);
-        return launch_win3<4, 1, 2, 2>(p, stream, 14);
     }
     const int bm = conv_pick_bm(p, bn);  // (never 256 today: those tiles stay instantiated and selectable by the rule)
     if (bn == 128) {

@@ -100,8 +100,10 @@ struct ConvParams {
     int tile_flags_n;
     // 2 * MACs of the unpadded convolution (bookkeeping for the bench's roofline leg; not read on device)
     double useful_flops;
-    // unused: padding of the kernel ABI (ConvParams is a kernel argument; no host or device code reads these)
-    int force_bm, force_splits;
+    // Winograd F(2x2,3x3) weights U = G g G^T of a layer packed in "fp32" with dfvo_set_fp32_winograd on (else null):
+    // [8-channel chunk][pos 16][h 2][round_up(cout, 32)][4], see conv_pack_wino_f32.h.  (These eight bytes were padding of the
+    // kernel ABI: ConvParams is a kernel argument, the layout of every other field is what it was.)
+    const float* wu32;
     // the device counter of activations beyond f16's range (g_f16s_clamped of conv_f16_clamp.h) for the f16 kernels that
     // live in their own translation units (conv_taps_f16s.hip: device symbols do not cross TUs)
     unsigned* f16s_clamp_ctr;
@@ -155,6 +157,15 @@ size_t conv_pack_weights_f16g(const float* w_oihw, int cout, int c0, int c1, int
 size_t conv_pack_weights_f32g(const float* w_oihw, int cout, int c0, int c1, int kh, int kw, const float* fold_scale, float* out);
 bool conv_f32g_ok(const ConvParams& p);
 int launch_f32g(const ConvParams& p, hipStream_t stream);
+// fp32 Winograd (conv_wino_f32.h): the process-wide switch (0 off, 1 by the size rule, 2 every applicable layer; read once
+// from DFVO_FP32_WINOGRAD), the host-side count of launches of its kernel, and the packer of a 3x3 layer's U
+int conv_fp32_winograd_mode();
+int conv_set_fp32_winograd(int mode);
+int conv_fp32_winograd_launches(unsigned long long* n, int reset);
+// mode 1: can launch_conv's size rule accept a launch of this layer, of at most max_pixels output pixels (0: unknown)?
+bool conv_wino_rule_may_accept(int cout, long long max_pixels);
+size_t conv_wino_f32_weight_floats(int cout, int c0, int c1);
+void conv_pack_weights_wino_f32(const float* w_oihw, int cout, int c0, int c1, const float* fold_scale, float* out);
 size_t conv_head_weight_floats(int cout, int c0, int c1, int k);
 void conv_pack_head_weights(const float* w_oihw, int cout, int c0, int c1, int k, const float* fold_scale, float* out);
 void conv_pack_weights(const float* w_oihw, const float* bias, int cout, int c0, int c1, int kh, int kw,
@@ -162,7 +173,8 @@ void conv_pack_weights(const float* w_oihw, const float* bias, int cout, int c0,
                        float* out_b);
 
 constexpr int CONV_NUM_CFGS = 24;  // tile configurations of the implicit-GEMM kernel (profile arrays have this size)
-int launch_conv(const ConvParams& p, hipStream_t stream);
+// wino_all: a layer with Winograd weights (p.wu32) takes that kernel whatever its size (dfvo_set_fp32_winograd(2))
+int launch_conv(const ConvParams& p, hipStream_t stream, bool wino_all = false);
 void conv_profile_begin();
 int conv_profile_end(double* ms, double* flops, int* launches, double* bytes = nullptr);
 

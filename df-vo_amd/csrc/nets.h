@@ -33,6 +33,8 @@ struct ConvLayer {
     int wg_cout_pad = 0, g_steps = 0;
     long long m_hint = 0;          // output pixels the layer was built for (0: unknown, dfvo_conv2d) -- gates optional packings
     int f16_terms = 3;             // 1: packed in "f16" mode (one product per term; the kernels never read the lo planes)
+    int wino_mode = 0;    // dfvo_set_fp32_winograd's value when wu was packed: 1 the size rule decides per launch, 2 every applicable launch
+    float* wu = nullptr;  // Winograd U (fp32 mode with dfvo_set_fp32_winograd on, applicable 3x3 layers), see conv_pack_wino_f32.h
     float* wh = nullptr;  // head layout (cout <= 2, square 3/5/7 kernels), see conv_pack_head_weights
     int cout = 0, cout_pad = 0, c0 = 0, c1 = 0, kh = 0, kw = 0, ksteps = 0;
     int stride = 1, pad_h = 0, pad_w = 0, pad_mode = PAD_ZERO, act = ACT_NONE;
@@ -45,13 +47,16 @@ struct ParamStore {
     const HostTensor* get(const std::string& name) const;
 };
 
-// builds + uploads a conv layer from OIHW weights; scale/shift fold an eval BatchNorm
+// builds + uploads a conv layer from OIHW weights; scale/shift fold an eval BatchNorm.  wino_geometry false: the layer will
+// run with a stride, reflection padding or an upsampled source -- no Winograd weights are packed for it
 int make_conv(const ParamStore& ps, const std::string& wname, const std::string& bname, int c0, int c1,
-              long long M_hint, const float* scale, const float* shift, ConvLayer* out);
+              long long M_hint, const float* scale, const float* shift, ConvLayer* out, bool wino_geometry = true);
 void free_conv(ConvLayer* l);
 // uploads the head-layout copy of the weights when the layer qualifies for the direct head kernel (else leaves wh null)
 int make_f16s_weights(const float* w_oihw, int cout, int c0, int c1, int kh, int kw, const float* scale, ConvLayer* L);
 int make_f16g_weights(const float* w_oihw, int cout, int c0, int c1, int kh, int kw, const float* scale, ConvLayer* L);
+int make_wino_weights(const float* w_oihw, int cout, int c0, int c1, int kh, int kw, const float* scale, bool geometry_ok,
+                      ConvLayer* L);
 int conv_set_precision(const char* name);  // fp32 | f16x3 | f16: applies to layers packed afterwards
 const char* conv_get_precision();
 int make_head_weights(const float* w_oihw, int cout, int c0, int c1, int kh, int kw, const float* scale, float** wh);

@@ -47,7 +47,7 @@ static int upload(const std::vector<float>& h, DevBuf* d) {
 }
 
 int make_conv(const ParamStore& ps, const std::string& wname, const std::string& bname, int c0, int c1,
-              long long M_hint, const float* scale, const float* shift, ConvLayer* L) {
+              long long M_hint, const float* scale, const float* shift, ConvLayer* L, bool wino_geometry) {
     const HostTensor* w = ps.get(wname);
     if (!w) {
         set_last_error("missing parameter " + wname);
@@ -77,6 +77,7 @@ int make_conv(const ParamStore& ps, const std::string& wname, const std::string&
     DFVO_HIP_CHECK(hipMemcpy(L->bias, pb.data(), pb.size() * sizeof(float), hipMemcpyHostToDevice));
     DFVO_TRY(make_f16s_weights(w->data.data(), L->cout, c0, c1, L->kh, L->kw, scale, L));
     DFVO_TRY(make_f16g_weights(w->data.data(), L->cout, c0, c1, L->kh, L->kw, scale, L));
+    DFVO_TRY(make_wino_weights(w->data.data(), L->cout, c0, c1, L->kh, L->kw, scale, wino_geometry, L));
     return make_head_weights(w->data.data(), L->cout, c0, c1, L->kh, L->kw, scale, &L->wh);
 }
 
@@ -150,6 +151,24 @@ int make_f16g_weights(const float* w_oihw, int cout, int c0, int c1, int kh, int
     return DFVO_OK;
 }
 
+// fp32 Winograd: U of the 3x3 layers packed in "fp32" while the switch is on.  The decision is the layer's from here on
+// (launch_conv looks at the pointer, never at the switch), so a captured graph replays what was packed.  U is 16 / 9 of the
+// weight bytes: it is not packed for a layer that no launch can hand to the kernel -- geometry_ok false (the builder knows
+// the layer runs with a stride, reflection padding or the upsampled source), or, in mode 1, a width or a map (m_hint pixels
+// at the most) that the size rule never accepts.  launch_conv still declines per launch what the kernel does not compute.
+int make_wino_weights(const float* w_oihw, int cout, int c0, int c1, int kh, int kw, const float* scale, bool geometry_ok,
+                      ConvLayer* L) {
+    L->wino_mode = 0;
+    const int mode = conv_fp32_winograd_mode();
+    if (conv_split_mode() != 0 || mode == 0 || kh != 3 || kw != 3 || cout <= 2 || !geometry_ok) return DFVO_OK;
+    if (mode == 1 && !conv_wino_rule_may_accept(cout, L->m_hint)) return DFVO_OK;
+    std::vector<float> wu(conv_wino_f32_weight_floats(cout, c0, c1));
+    conv_pack_weights_wino_f32(w_oihw, cout, c0, c1, scale, wu.data());
+    DFVO_HIP_CHECK(hipMalloc((void**)&L->wu, wu.size() * sizeof(float)));
+    DFVO_HIP_CHECK(hipMemcpy(L->wu, wu.data(), wu.size() * sizeof(float), hipMemcpyHostToDevice));
+    L->wino_mode = mode;
+    return DFVO_OK;
+}
 
 int make_head_weights(const float* w, int cout, int c0, int c1, int kh, int kw, const float* scale, float** wh) {
     *wh = nullptr;
@@ -169,6 +188,8 @@ void free_conv(ConvLayer* l) {
     if (l->wg) (void)hipFree(l->wg);
     if (l->wg32) (void)hipFree(l->wg32);
     l->wg32 = nullptr;
+    if (l->wu) (void)hipFree(l->wu);
+    l->wu = nullptr;
     if (l->gtab) (void)hipFree(l->gtab);
     l->wf = nullptr;
     l->wg = nullptr;
@@ -212,6 +233,7 @@ int run_conv(const ConvLayer& L, int N, int H, int W, View s0, int up0, View s1,
     p.wf16_cout_pad = L.wf_cout_pad;
     p.wf16g = L.wg;
     p.wf32g = L.wg32;
+    p.wu32 = L.wu;
     p.wf16g_cout_pad = L.wg_cout_pad;
     p.f16g_tab = L.gtab;
     p.f16g_steps = L.g_steps;
@@ -245,7 +267,7 @@ int run_conv(const ConvLayer& L, int N, int H, int W, View s0, int up0, View s1,
     }
     p.useful_flops = 2.0 * (double)N * p.Ho * p.Wo * L.macs_per_pixel();
     if (flops) *flops += p.useful_flops;
-    return launch_conv(p, s);
+    return launch_conv(p, s, L.wino_mode == 2);
 }
 
 // torch.linspace(-1, 1, n) fallback (the Python host normally uploads torch's own table, see capi)
@@ -331,7 +353,7 @@ int FlowNet::finalize() {
         const std::string base = std::string("moduleFeatures.") + fcs[i].name;
         const long long M = (long long)N * lh[fcs[i].level_in] * lw[fcs[i].level_in];
         DFVO_TRY(make_conv(params, base + ".weight", base + ".bias", fcs[i].cin, 0, M, nullptr, nullptr,
-                           &feat_convs[i]));
+                           &feat_convs[i], fcs[i].stride == 1 && fcs[i].pad == 1));
         feat_convs[i].stride = fcs[i].stride;
         feat_convs[i].pad_h = feat_convs[i].pad_w = fcs[i].pad;
         feat_convs[i].act = ACT_LEAKY;
@@ -860,7 +882,7 @@ int DepthNet::finalize() {
             }
             const long long M = (long long)hh * ww;
             DFVO_TRY(bn_fold(params, base + ".bn1", cout, &sc, &sh));
-            DFVO_TRY(make_conv(params, base + ".conv1.weight", "", c_in, 0, M, sc.data(), sh.data(), &B.c1));
+            DFVO_TRY(make_conv(params, base + ".conv1.weight", "", c_in, 0, M, sc.data(), sh.data(), &B.c1, s == 1));
             B.c1.stride = s;
             B.c1.pad_h = B.c1.pad_w = 1;
             B.c1.act = ACT_RELU;
@@ -888,8 +910,8 @@ int DepthNet::finalize() {
         const long long M0 = (long long)(H >> (i + 1)) * (W >> (i + 1)), M1 = (long long)(H >> i) * (W >> i);
         const std::string b0 = "decoder." + std::to_string(idx0) + ".conv.conv";
         const std::string b1 = "decoder." + std::to_string(idx1) + ".conv.conv";
-        DFVO_TRY(make_conv(params, b0 + ".weight", b0 + ".bias", cin0, 0, M0, nullptr, nullptr, &up[i][0]));
-        DFVO_TRY(make_conv(params, b1 + ".weight", b1 + ".bias", dec[i], skip, M1, nullptr, nullptr, &up[i][1]));
+        DFVO_TRY(make_conv(params, b0 + ".weight", b0 + ".bias", cin0, 0, M0, nullptr, nullptr, &up[i][0], false));  // reflection padding
+        DFVO_TRY(make_conv(params, b1 + ".weight", b1 + ".bias", dec[i], skip, M1, nullptr, nullptr, &up[i][1], false));
         for (int j = 0; j < 2; ++j) {
             up[i][j].stride = 1;
             up[i][j].pad_h = up[i][j].pad_w = 1;

@@ -19,6 +19,9 @@ def hip_options(cfg):
       conv_precision  "f16x3" (default here: fp32-class split products, the arithmetic bench.py's headline runs), "fp32"
                       (exact fp32 MFMA, the C library's own default) or "f16" (one product per term: not fp32-class);
                       DFVO_CONV_PRECISION overrides
+      fp32_winograd   True / False: dfvo_set_fp32_winograd(1 / 0) while these nets are packed -- the opt-in Winograd path of
+                      the 3x3 layers, "fp32" packing only; absent (default, and then absent from the returned options): the
+                      process-wide setting stands, which DFVO_FP32_WINOGRAD initialises
       session         True (default): the frame session of libs/deep_models/session.py; DFVO_SESSION=0 turns it off"""
     o = {"conv_precision": "f16x3", "session": True}
     try:
@@ -26,7 +29,7 @@ def hip_options(cfg):
     except Exception:  # (config objects without the key)
         extra = None
     if extra:
-        o.update({k: extra[k] for k in o if k in extra})
+        o.update({k: extra[k] for k in list(o) + ["fp32_winograd"] if k in extra})
     if os.environ.get("DFVO_CONV_PRECISION"):
         o["conv_precision"] = os.environ["DFVO_CONV_PRECISION"]
     if os.environ.get("DFVO_SESSION") is not None:
@@ -49,6 +52,9 @@ class DeepModel:
         lib = capi.lib()
         before = lib.dfvo_get_conv_precision()  # the process-wide setting is restored once these nets are packed
         capi.check(lib.dfvo_set_conv_precision(self.conv_precision.encode()))
+        wino_before = lib.dfvo_get_fp32_winograd()  # restored with the precision
+        if opts.get("fp32_winograd") is not None:
+            capi.check(lib.dfvo_set_fp32_winograd(1 if opts["fp32_winograd"] else 0))
         self.session = None
         seen = capi.f16s_overflow_count() if self.conv_precision != "fp32" else 0
         try:
@@ -60,6 +66,7 @@ class DeepModel:
                     assert False, "No precomputed depths nor pretrained depth model"
         finally:
             capi.check(lib.dfvo_set_conv_precision(before))
+            capi.check(lib.dfvo_set_fp32_winograd(wino_before))
         if self.conv_precision != "fp32":
             # weights beyond f16's range are clamped (and counted) by the packer: refuse them here, loudly
             capi.check_f16_range(seen, "the packed weights")

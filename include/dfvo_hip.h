@@ -99,6 +99,19 @@ int dfvo_set_sklearn_compat(const char* version);
  * *h_count = events since the last reset (0 = the f16x3 result is the 22-bit split of the true operands everywhere).
  * reset != 0 clears the counter. */
 int dfvo_f16s_overflow_count(unsigned long long* h_count, int reset);
+/* Opt-in Winograd F(2x2,3x3) for the layers packed in "fp32" (df-vo_amd/csrc/conv_wino_f32.h): all-fp32 arithmetic, 16
+ * instead of 36 multiplications per 2x2 output tile, NOT bit-identical to the direct fp32 kernels (its error bound is the
+ * fp32 row's constant on the magnitudes of the transformed products: tests/wino_bounds.py).
+ * 0 off (default); 1 on (experimental): 3x3 / stride-1 / zero-pad-1 layers with cout > 2 that the size rule accepts run as
+ * Winograd (64- and 128-wide layers on maps of at least 30000 pixels: DESIGN.md section 5d);
+ * 2 on for every such layer whatever its size (unit tests).  Reflection padding and the x2-upsampled source stay on the
+ * direct kernels.  No effect on layers packed as f16x3 / f16.
+ * Read when a layer is packed (nets: *_finalize; dfvo_conv2d: per call); also from DFVO_FP32_WINOGRAD once. */
+int dfvo_set_fp32_winograd(int mode);
+int dfvo_get_fp32_winograd(void);
+/* launches of the Winograd kernel since the last reset (counted on the host when the launch is enqueued; a replayed
+ * hipGraph does not count again).  reset != 0 clears the counter. */
+int dfvo_fp32_winograd_launches(unsigned long long* h_count, int reset);
 int dfvo_conv_profile_begin(void);
 int dfvo_conv_profile_end(double* h_ms24, double* h_flops24, int* h_launches24);
 /* the same, plus the ALGORITHMIC HBM bytes of each configuration's launches (fp32 input map + output map + weights, each
