@@ -188,7 +188,7 @@ SM_HD int kp_median_of_median5_cp(float* key, IdxT* tosort, int num, int depth) 
 }
 
 // main loop of the selection from an intermediate state (low, high, depth_limit): lets a caller run the first,
-// long partition passes some other way (k_kp_cell does them with the whole workgroup) and finish here
+// long partition passes some other way (kp_introselect_block, solver_kp.hip, does them with the whole workgroup) and finish here
 template <typename IdxT>
 SM_HD_NOINLINE void kp_introselect_cp_from(float* key, IdxT* tosort, int kth, int depth, int low, int high,
                                            int depth_limit);

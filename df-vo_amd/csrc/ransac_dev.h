@@ -1,4 +1,4 @@
-// Device helpers shared by the RANSAC kernels (solver_ransac.hip, solver_pnp.hip).
+// Device helpers shared by the solver kernels (solver_ransac.hip, solver_pnp.hip, solver_kp.hip, solver_scale.hip).
 #pragma once
 #include "dfvo_common.h"
 #include "solver.h"
@@ -17,6 +17,12 @@ __device__ __forceinline__ int wave_sum(int v) {
     v += __builtin_amdgcn_ds_swizzle(v, 0x201F);
     v += __builtin_amdgcn_ds_swizzle(v, 0x401F);
     v += __shfl_xor(v, 32, 64);
+    return v;
+}
+
+// wave64 double sum, the same butterfly order
+__device__ __forceinline__ double wave_sum_d(double v) {
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
     return v;
 }
 

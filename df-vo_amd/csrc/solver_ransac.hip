@@ -61,14 +61,6 @@ __global__ void k_replay(RansacState* st, const int* __restrict__ nmodels, const
 // call and the five-point sampler has no data-dependent subset check, so the subset indices depend
 // only on the point count: they are drawn once and shared by the batch.
 // ================================================================================================
-__global__ void k_e_normalise(const double* __restrict__ pts, int n, double a, double bx, double by,
-                              double* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    out[i * 2] = pts[i * 2] * a + bx;
-    out[i * 2 + 1] = pts[i * 2 + 1] * a + by;
-}
-
 struct ERep {
     RansacState* state;
     const double *pts1, *pts2;  // inputs
@@ -449,11 +441,6 @@ int enqueue_e_subsets_prefetch(RansacWorkspace& w0, const int* d_n, int n_bound,
 // ================================================================================================
 // homography
 // ================================================================================================
-__global__ void k_to_float(const double* __restrict__ a, int n, float* __restrict__ o) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) o[i] = (float)a[i];
-}
-
 // findHomography prologue in one launch: RANSAC state reset + both point sets converted to float (blockIdx.y)
 // d_n (optional): the point count lives on the device (fused pipeline, chain enqueued before the host knows it);
 // then n_arg is only the launch bound.  Fewer than 5 points: no model (state done, found = 0).

@@ -1,4 +1,13 @@
-// Device buffers and small state blocks of the tracker pipeline (solver_pipeline.hip).
+// Device buffers, small state blocks and enqueue functions of the tracker stages around the RANSAC solvers:
+//   solver_kp.hip               keypoint selection (local_bestN, bestN_flow_kp, rigid-flow and sampled keypoints)
+//   solver_rng.hip              numpy's MT19937 seeding and shuffle on the device
+//   solver_pose2d2d.hip         EssTracker.compute_pose_2d2d: GRIC, the repeated shuffled five-point RANSAC, bookkeeping
+//   solver_scale.hip            depth-ratio scale recovery (find_scale_from_depth)
+//   solver_trajectory.hip       update_global_pose over a gathered sequence
+//   solver_tracker_buffers.hip  lifetime of TrackerBuffers (host only)
+// Sequential semantics that leak into the results (argpartition order, python-loop summation order, the global
+// np.random stream, last-writer-wins scatter) are kept by giving each sequential chain to one lane and spreading
+// independent chains over lanes / workgroups.  All solver_*.hip units are built with -ffp-contract=off.
 #pragma once
 #include <stddef.h>
 
@@ -55,6 +64,20 @@ constexpr int MAX_REP = 8;
 // TrackerBuffers::mt_state holds the RandomState (624 key words + position) followed by MAX_REP + 1 snapshots of it
 constexpr int MT_SNAP_STRIDE = 640;
 inline uint32_t* mt_snapshots(uint32_t* mt_state) { return mt_state + MT_SNAP_STRIDE; }
+// TrackerBuffers::kp_total, ints: small device counters of the stages
+constexpr int KP_CNT_BLOCKS = 64;     // counting blocks of k_kp_cell (solver_kp.hip)
+constexpr int KPT_GOOD = 0;           // k_kp_gather's count when it is given no partial counts ([1..3] unused)
+constexpr int KPT_SCALE_VALID = 4;    // number of valid depth ratios of the scale stage
+constexpr int KPT_FLOW_GATE = 5;      // "flow" validity: [5] the keypoint count the shuffles see, [6] valid_case ([7] unused)
+constexpr int KPT_CELL_PARTIAL = 8;   // [8..71] the counting blocks' partial counts
+constexpr int KPT_E_RNG = KPT_CELL_PARTIAL + KP_CNT_BLOCKS;  // [72..73] the five-point sampler's 64-bit state behind its prefetched subsets
+constexpr int KPT_SIZE = KPT_E_RNG + 2;
+// TrackerBuffers::small, doubles
+constexpr int SMALL_KINVT = 0;    // [0..8] K^-T
+constexpr int SMALL_KINV = 9;     // [9..17] K^-1
+constexpr int SMALL_H_GRIC = 18;  // GRIC of the homography ("flow" validity: the mean keypoint displacement)
+constexpr int SMALL_E_GRIC = 19;  // [19 .. 19 + MAX_REP) GRIC of each repeat's E ("flow" validity: its cheirality count)
+constexpr int SMALL_SIZE = 128;
 constexpr int NUM_REP_STREAMS = 4;  // side streams created per tracker; two are used (see TrackerBuffers::init)
 static inline int rep_stream_count() { return NUM_REP_STREAMS; }
 
@@ -123,10 +146,10 @@ struct TrackerBuffers {
     bool shared = false;  // streams / events / RandomState borrowed from another TrackerBuffers (see share_from)
     uint32_t* mt_state = nullptr;  // numpy RandomState: key[624], pos
     int* kp_info = nullptr;        // [n, good_kp_found, regions]
-    int* kp_total = nullptr;
+    int* kp_total = nullptr;       // [KPT_SIZE], layout: KPT_* above
     int e_pre_iters = 0;  // > 0: enqueue_pose_h_part drew the five-point sampler's first chunk ahead, for this iteration budget
     PoseState* pose = nullptr;
-    double* small = nullptr;
+    double* small = nullptr;       // [SMALL_SIZE], layout: SMALL_* above
     double h_small[18] = {};       // host copy of the 18 intrinsics doubles held in `small` (uploaded only when they change)
     bool small_valid = false;
     ScaleResult* scale_out = nullptr;
@@ -153,6 +176,9 @@ struct TrackerBuffers {
     int ensure_kp(int cap, int cells, int n_best);
     void release_kp();
     void release();
+
+private:
+    int init_own();  // the buffers and events every set owns, shared or not
 };
 
 // score_method: 0 'flow' (the consistency map itself), 1 'flow_ratio' (map / |flow|), kp_selection.py:137-141,151-156

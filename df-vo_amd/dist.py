@@ -130,7 +130,7 @@ def allgather_poses(rel, status, world, rank, dist=None, counts=None, comm=None,
 
 
 def compose_trajectory_device(gathered, first_pose=None):
-    """compose_trajectory in ONE device launch (dfvo_compose_trajectory[_device], csrc/solver_pipeline.hip): `gathered` is
+    """compose_trajectory in ONE device launch (dfvo_compose_trajectory[_device], csrc/solver_trajectory.hip): `gathered` is
     the [n,17] pose | status array -- a numpy array, or a CUDA tensor (the RCCL all-gather's output: nothing but the
     composed poses then crosses PCIe).  Same recurrence, same order of operations as the host loop below; numpy's 3x3
     products may fuse multiply-adds where the kernel does not, so the two agree to rounding (<= 1e-12), not bit for bit."""
