@@ -13,10 +13,14 @@ Sub-modules
 """
 import os
 
-# The fused pipeline keeps eight HIP streams busy (two flow-net instances, depth net, solver chain and its two side
-# streams, two prefetch streams).  ROCm maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4); streams that share a queue
-# serialise, which costs ~20 % of the pair rate.  Must be in the environment before the HIP runtime initialises, so
-# it is set (without overriding the user's choice) when the package is imported.
+# The fused pipeline's wide layout keeps eight HIP streams busy (two flow-net instances, depth net, solver chain and its two
+# side streams, two prefetch streams).  ROCm maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), read once when
+# the HIP runtime initialises; streams that share a queue execute in host enqueue order, which cost the wide layout ~20 % of
+# the pair rate.  So twelve are asked for when the package is imported -- but only asked: a value that is already in the
+# environment wins (setdefault), and a caller that initialised HIP before this import (torch.cuda, as bench.py does) has
+# fixed the count whatever is set here.  The pipeline therefore adapts to the queues it finds: dfvo_pipeline_create measures
+# which of its candidate streams share a hardware queue and, with four to seven queues, runs its roles on one stream per
+# queue instead (csrc/stream_layout.h; dfvo_pipeline_stream_layout reports the layout in use).
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "12")
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))

@@ -223,6 +223,7 @@ SIGNATURES = {
     "dfvo_pipeline_get_rng_state": (_i, [_vp, _vp]),
     "dfvo_pipeline_set_rng_state": (_i, [_vp, _vp]),
     "dfvo_pipeline_sync": (_i, [_vp]),
+    "dfvo_pipeline_stream_layout": (_i, [_vp, _vp, _i]),
     "dfvo_pipeline_net_flops": (_d, [_vp]),
     "dfvo_find_scale_from_depth": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, C.POINTER(ScaleCfg), C.POINTER(_d), _vp]),
     "dfvo_find_scale_from_depth_at_kp": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, C.POINTER(ScaleCfg), _vp, C.POINTER(_d), _vp]),

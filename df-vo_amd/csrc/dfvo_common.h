@@ -123,8 +123,13 @@ struct StreamPool {
     std::vector<hipStream_t> s;
     std::vector<int> group;  // pipe group of s[i] (streams of one group slow each other's dispatch), -1 unknown
     int ngroups = 0;         // 0: the probe failed, use creation order
+    // hardware queue of s[i]: streams of one queue execute in host enqueue order, whatever their events say (-1 unknown).
+    // Streams of one queue are of one pipe group; with fewer hardware queues than candidates several share a queue.
+    std::vector<int> queue_group;
+    int nqueues = 0;         // 0: the probe failed
     int create(int n);
     hipStream_t take(int group);  // removes a stream of that group from the pool (nullptr when none is left)
+    hipStream_t take_index(int i);  // removes candidate i from the pool (nullptr when it was taken before)
     int count(int group) const;
     void release();               // destroys what was not taken
 };

@@ -14,6 +14,7 @@
 #include "nets.h"
 #include "ops.h"
 #include "resize_lanczos.h"
+#include "stream_layout.h"
 #include "tracker.h"
 
 using namespace dfvo;
@@ -64,6 +65,12 @@ struct dfvo_pipeline {
     dfvo_pipeline_cfg cfg;
     bool nets_ready = false;
     const FlowNet* last_flow = nullptr;  // the instance that ran the previous pair (carry source of a d_ref == NULL call)
+    // Stream layout (stream_layout.h).  LAYOUT_LANES: lane[0 .. 3] are the pipeline's only streams, one per hardware queue,
+    // and every role's stream above is one of them (s_flow, s_flow_x[0], s_depth = s_pre[0] = s_pre[1], s_trk = both side
+    // streams of the chain); otherwise every role owns its stream and lane[] is null.
+    StreamPlan plan;
+    int pool_groups = 0, pool_queues = 0;  // what the pool measured (0: no measurement)
+    hipStream_t lane[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 #define P_TRY(expr)                     \
@@ -86,31 +93,68 @@ int dfvo_pipeline_create(const dfvo_pipeline_cfg* cfg, dfvo_pipeline** out) {
         delete p;
         return rc;
     };
-    // Streams by dispatch pipe (stream_pool.hip): twelve candidates, classified by measurement; pipe A / B: one flow-net
-    // instance each, pipe C: the depth net + the two run-ahead homography chains, pipe D: the RandomState-ordered chain and
-    // its two side streams, alone.  Falls back to creation order when the probe does not find four groups of three.
+    // Streams by measurement (stream_pool.hip, stream_layout.h): twelve candidates, classified by dispatch pipe and by
+    // hardware queue.  Eight or more queues: the wide layout, a stream per role -- pipe A / B: one flow-net instance each, pipe
+    // C: the depth net + the two run-ahead homography chains, pipe D: the RandomState-ordered chain and its two side streams,
+    // alone.  Four to seven queues (GPU_MAX_HW_QUEUES at the runtime's default of 4): eight busy streams would share queues,
+    // and streams of one queue execute in host enqueue order -- a wait enqueued for one of them holds up the others' work;
+    // the lane layout takes one stream from each of four queues and puts the roles of a lane on that one stream (flow |
+    // flow_x | depth + pre-parts | chain + side streams), so which roles share a queue is decided here and not by the runtime.
+    // DFVO_STREAM_LAYOUT=auto|wide|lanes forces one (A/B runs, tests).  Falls back to creation order when the probe does
+    // not settle or finds too few groups / queues for the layout.
     hipStream_t pool_rep[2] = {nullptr, nullptr}, pool_pre[2] = {nullptr, nullptr}, pool_fx = nullptr;
     {
+        int choice = LAYOUT_CHOICE_AUTO;
+        if (const char* e = getenv("DFVO_STREAM_LAYOUT")) {
+            if (!strcmp(e, "wide"))
+                choice = LAYOUT_CHOICE_WIDE;
+            else if (!strcmp(e, "lanes"))
+                choice = LAYOUT_CHOICE_LANES;
+            else if (strcmp(e, "auto")) {
+                dfvo::set_last_error("dfvo_pipeline_create: DFVO_STREAM_LAYOUT is auto, wide or lanes");
+                return fail(DFVO_ERR_ARG);
+            }
+        }
         StreamPool pool;
-        if (pool.create(12) == DFVO_OK && pool.ngroups >= 4) {
+        if (pool.create(12) == DFVO_OK && pool.ngroups > 0) {
+            p->pool_groups = pool.ngroups;
+            p->pool_queues = pool.nqueues;
+        }
+        StreamPlan plan = plan_stream_layout(p->pool_groups, p->pool_queues, choice);
+        if (plan.layout == LAYOUT_LANES) {
+            PoolClasses c;
+            c.group = pool.group;
+            c.queue_group = pool.queue_group;
+            c.ngroups = pool.ngroups;
+            c.nqueues = pool.nqueues;
+            int pick[4];
+            if (pick_lane_candidates(c, pick)) {
+                for (int l = 0; l < 4; ++l) p->lane[l] = pool.take_index(pick[l]);
+                p->s_trk = p->lane[plan.lane[ROLE_TRK]];
+                p->s_depth = p->lane[plan.lane[ROLE_DEPTH]];
+                p->s_flow = p->lane[plan.lane[ROLE_FLOW]];
+                p->plan = plan;
+            }
+        } else if (plan.layout == LAYOUT_WIDE) {
             int g[4] = {-1, -1, -1, -1}, ng = 0;  // the four largest groups, largest first
             std::vector<int> order;
             for (int i = 0; i < pool.ngroups; ++i) order.push_back(i);
             std::sort(order.begin(), order.end(), [&](int a, int b) { return pool.count(a) > pool.count(b); });
             for (int i = 0; i < 4; ++i) g[ng++] = order[i];
-            // role -> pipe: trk rep0 rep1 | depth pre0 pre1 | flow | flow_x.  Other placements were measured
+            // role -> pipe: trk rep0 rep1 | depth pre0 pre1 | flow | flow_x (plan.lane).  Other placements were measured
             // (profiles/r3k_layouts.txt): a run-ahead homography chain on a flow net's pipe 178-194 pairs/s against 266 -- its
             // long single-workgroup kernels hold up the dispatch of the flow net's hundred short launches per pass.
-            static const int R[8] = {0, 0, 0, 1, 1, 1, 2, 3};
-            if (pool.count(g[0]) >= 3 && pool.count(g[1]) >= 3 && pool.count(g[2]) >= 3 && pool.count(g[3]) >= 3) {
-                p->s_trk = pool.take(g[R[0]]);
-                pool_rep[0] = pool.take(g[R[1]]);
-                pool_rep[1] = pool.take(g[R[2]]);
-                p->s_depth = pool.take(g[R[3]]);
-                pool_pre[0] = pool.take(g[R[4]]);
-                pool_pre[1] = pool.take(g[R[5]]);
-                p->s_flow = pool.take(g[R[6]]);
-                pool_fx = pool.take(g[R[7]]);
+            const int* rank = plan.lane;  // wide: per role, the rank (0 = largest) of the pipe group its stream comes from
+            const bool full = pool.count(g[0]) >= 3 && pool.count(g[1]) >= 3 && pool.count(g[2]) >= 3 && pool.count(g[3]) >= 3;
+            if (full) {
+                p->s_trk = pool.take(g[rank[ROLE_TRK]]);
+                pool_rep[0] = pool.take(g[rank[ROLE_REP0]]);
+                pool_rep[1] = pool.take(g[rank[ROLE_REP1]]);
+                p->s_depth = pool.take(g[rank[ROLE_DEPTH]]);
+                pool_pre[0] = pool.take(g[rank[ROLE_PRE0]]);
+                pool_pre[1] = pool.take(g[rank[ROLE_PRE1]]);
+                p->s_flow = pool.take(g[rank[ROLE_FLOW]]);
+                pool_fx = pool.take(g[rank[ROLE_FLOW_X]]);
             } else if (pool.count(g[0]) >= 3 && pool.count(g[1]) >= 3 && pool.count(g[2]) >= 1 && pool.count(g[3]) >= 1) {
                 p->s_trk = pool.take(g[0]);
                 pool_rep[0] = pool.take(g[0]);
@@ -121,9 +165,11 @@ int dfvo_pipeline_create(const dfvo_pipeline_cfg* cfg, dfvo_pipeline** out) {
                 p->s_flow = pool.take(g[2]);
                 pool_fx = pool.take(g[3]);
             }
+            if (p->s_trk) p->plan = plan;
         }
         pool.release();
     }
+    const bool lanes = p->plan.layout == LAYOUT_LANES;
     if (!p->s_trk && (create_net_stream(&p->s_flow) != hipSuccess || create_net_stream(&p->s_depth) != hipSuccess ||
                       create_solver_stream(&p->s_trk) != hipSuccess)) {
         dfvo::set_last_error("dfvo_pipeline_create: hipStreamCreate failed (no GPU?)");
@@ -142,7 +188,9 @@ int dfvo_pipeline_create(const dfvo_pipeline_cfg* cfg, dfvo_pipeline** out) {
     // r3ag_flow_instances_ab.txt).  DFVO_FLOW_INSTANCES=1 is a test hook: the carry-over from a pass of the SAME instance
     p->flow_instances = getenv("DFVO_FLOW_INSTANCES") && atoi(getenv("DFVO_FLOW_INSTANCES")) == 1 ? 1 : 2;
     for (int i = 0; i + 1 < p->flow_instances; ++i) {
-        if (i == 0 && pool_fx) {
+        if (i == 0 && lanes) {
+            p->s_flow_x[0] = p->lane[p->plan.lane[ROLE_FLOW_X]];
+        } else if (i == 0 && pool_fx) {
             p->s_flow_x[0] = pool_fx;
             pool_fx = nullptr;
         } else if (create_net_stream(&p->s_flow_x[i]) != hipSuccess) {
@@ -157,7 +205,9 @@ int dfvo_pipeline_create(const dfvo_pipeline_cfg* cfg, dfvo_pipeline** out) {
     p->depth.max_depth = cfg->net_max_depth;
     p->depth.baseline_mult = cfg->baseline_mult;
     if (pool_fx) (void)hipStreamDestroy(pool_fx);
-    rc = p->tbs[0].init(pool_rep[0], pool_rep[1]);
+    // (lanes: the chain's side streams are the chain's own stream, borrowed -- the pipeline destroys its lanes)
+    rc = lanes ? p->tbs[0].init(p->lane[p->plan.lane[ROLE_REP0]], p->lane[p->plan.lane[ROLE_REP1]], true)
+               : p->tbs[0].init(pool_rep[0], pool_rep[1]);
     if (rc != DFVO_OK) return fail(rc);
     for (int i = 1; i < DFVO_PIPELINE_SLOTS; i++) {
         rc = p->tbs[i].init_shared(p->tbs[0]);
@@ -170,7 +220,9 @@ int dfvo_pipeline_create(const dfvo_pipeline_cfg* cfg, dfvo_pipeline** out) {
         if (rc != DFVO_OK) return fail(rc);
     }
     for (int i = 0; i < 2; i++) {
-        if (pool_pre[i])
+        if (lanes)
+            p->s_pre[i] = p->lane[p->plan.lane[ROLE_PRE0 + i]];
+        else if (pool_pre[i])
             p->s_pre[i] = pool_pre[i];
         else if (create_solver_stream(&p->s_pre[i], 4) != hipSuccess)
             return fail(DFVO_ERR_HIP);
@@ -208,6 +260,10 @@ int dfvo_pipeline_create(const dfvo_pipeline_cfg* cfg, dfvo_pipeline** out) {
     if (p->feed_resize.init(p->H, p->W, p->feedH, p->feedW) != DFVO_OK) return fail(DFVO_ERR_HIP);
     enqueue_mt_seed(p->tbs[0], cfg->seed, p->s_trk);
     (void)hipStreamSynchronize(p->s_trk);
+    if (getenv("DFVO_STREAM_PROBE_VERBOSE")) {
+        char line[256];
+        if (dfvo_pipeline_stream_layout(p, line, sizeof(line)) == DFVO_OK) fprintf(stderr, "dfvo pipeline streams: %s\n", line);
+    }
     *out = p;
     return DFVO_OK;
 }
@@ -215,15 +271,16 @@ int dfvo_pipeline_create(const dfvo_pipeline_cfg* cfg, dfvo_pipeline** out) {
 void dfvo_pipeline_destroy(dfvo_pipeline* p) {
     if (!p) return;
     (void)hipDeviceSynchronize();
+    const bool lanes = p->plan.layout == LAYOUT_LANES;  // every role's stream is one of lane[]
     p->flow.destroy();
     for (int i = 0; i + 1 < p->flow_instances; ++i) {
         p->flow_x[i].destroy();
-        if (p->s_flow_x[i]) (void)hipStreamDestroy(p->s_flow_x[i]);
+        if (p->s_flow_x[i] && !lanes) (void)hipStreamDestroy(p->s_flow_x[i]);
     }
     p->depth.destroy();
     for (int i = DFVO_PIPELINE_SLOTS - 1; i >= 0; i--) p->tbs[i].release();
     for (int i = 0; i < 2; i++)
-        if (p->s_pre[i]) (void)hipStreamDestroy(p->s_pre[i]);
+        if (p->s_pre[i] && !lanes) (void)hipStreamDestroy(p->s_pre[i]);
     for (int i = 0; i < DFVO_PIPELINE_SLOTS; i++) {
         if (p->e_pre[i]) (void)hipEventDestroy(p->e_pre[i]);
         if (p->e_res[i]) (void)hipEventDestroy(p->e_res[i]);
@@ -246,9 +303,14 @@ void dfvo_pipeline_destroy(dfvo_pipeline* p) {
     if (p->ref_raw) (void)hipFree(p->ref_raw);
     p->pnp.release();
     if (p->d_T21) (void)hipFree(p->d_T21);
-    if (p->s_flow) (void)hipStreamDestroy(p->s_flow);
-    if (p->s_depth) (void)hipStreamDestroy(p->s_depth);
-    if (p->s_trk) (void)hipStreamDestroy(p->s_trk);
+    if (lanes) {
+        for (hipStream_t l : p->lane)
+            if (l) (void)hipStreamDestroy(l);
+    } else {
+        if (p->s_flow) (void)hipStreamDestroy(p->s_flow);
+        if (p->s_depth) (void)hipStreamDestroy(p->s_depth);
+        if (p->s_trk) (void)hipStreamDestroy(p->s_trk);
+    }
     delete p;
 }
 
@@ -443,7 +505,10 @@ int dfvo_pipeline_track_begin(dfvo_pipeline* p, int slot, const float* d_flow_ov
     if (trace && !tb.ev_t[0])
         for (int i = 0; i < 4; i++) DFVO_HIP_CHECK(hipEventCreate(&tb.ev_t[i]));
     P_TRY(enqueue_scale_prepare(tb, p->H, p->W));  // side stream: the scale stage's fills leave the dependent chain
-    if (!p->prefetched[slot]) P_TRY(enqueue_pre_part(p, slot, d_flow_override, d_diff_override, p->s_pre[slot & 1]));
+    // A pre-part nobody prefetched: in the lane layout it goes onto the chain's lane (s), whose next work needs it anyway --
+    // the depth lane may already hold later pairs' nets, and it would run behind them
+    if (!p->prefetched[slot])
+        P_TRY(enqueue_pre_part(p, slot, d_flow_override, d_diff_override, p->plan.layout == LAYOUT_LANES ? s : p->s_pre[slot & 1]));
     p->prefetched[slot] = false;
     DFVO_HIP_CHECK(hipEventSynchronize(p->e_pre[slot]));  // keypoint info is in pinned host memory now
     const int* info = p->h_info[slot];
@@ -643,6 +708,30 @@ int dfvo_pipeline_sync(dfvo_pipeline* p) {
     for (int i = 0; i + 1 < p->flow_instances; ++i) DFVO_HIP_CHECK(hipStreamSynchronize(p->s_flow_x[i]));
     DFVO_HIP_CHECK(hipStreamSynchronize(p->s_depth));
     DFVO_HIP_CHECK(hipStreamSynchronize(p->s_trk));
+    return DFVO_OK;
+}
+
+int dfvo_pipeline_stream_layout(dfvo_pipeline* p, char* buf, int n) {
+    DFVO_ARG_CHECK(p && buf && n > 0, "dfvo_pipeline_stream_layout: bad argument");
+    // "layout=lanes groups=4 queues=4 streams=4 trk=3 rep0=3 ... flow_x=1": per role the index of its stream among the
+    // pipeline's distinct streams (lanes: the lane), so equal numbers mean one stream
+    hipStream_t role[ROLE_COUNT] = {p->s_trk, p->tbs[0].s_rep[0], p->tbs[0].s_rep[1], p->s_depth, p->s_pre[0], p->s_pre[1], p->s_flow,
+                                    p->flow_instances > 1 ? p->s_flow_x[0] : nullptr};
+    std::vector<hipStream_t> distinct;
+    const bool lanes = p->plan.layout == LAYOUT_LANES;
+    if (lanes) distinct.assign(p->lane, p->lane + 4);
+    int idx[ROLE_COUNT];
+    for (int r = 0; r < ROLE_COUNT; ++r) {
+        idx[r] = -1;
+        if (!role[r]) continue;
+        auto it = std::find(distinct.begin(), distinct.end(), role[r]);
+        idx[r] = (int)(it - distinct.begin());
+        if (it == distinct.end()) distinct.push_back(role[r]);
+    }
+    int w = snprintf(buf, n, "layout=%s groups=%d queues=%d streams=%d", stream_layout_name(p->plan.layout), p->pool_groups,
+                     p->pool_queues, (int)distinct.size());
+    for (int r = 0; r < ROLE_COUNT && w > 0 && w < n; ++r) w += snprintf(buf + w, n - w, " %s=%d", stream_role_name(r), idx[r]);
+    DFVO_ARG_CHECK(w > 0 && w < n, "dfvo_pipeline_stream_layout: the buffer is too small");
     return DFVO_OK;
 }
 

@@ -48,7 +48,8 @@ int TrackerBuffers::init_own() {
     return DFVO_OK;
 }
 
-int TrackerBuffers::init(hipStream_t rep0, hipStream_t rep1) {
+int TrackerBuffers::init(hipStream_t rep0, hipStream_t rep1, bool borrowed) {
+    DFVO_ARG_CHECK(!borrowed || rep0, "TrackerBuffers::init: borrowed side streams have to be given");
     DFVO_HIP_CHECK(hipMalloc((void**)&mt_state, sizeof(uint32_t) * MT_SNAP_STRIDE * (MAX_REP + 2)));  // the state + its snapshots (mt_snapshots)
     if (int rc = init_own()) return rc;
     // Side streams: [0] runs the five-point batch, [1] the scale stage's fills; the slots past `n_streams` alias them.
@@ -60,8 +61,10 @@ int TrackerBuffers::init(hipStream_t rep0, hipStream_t rep1) {
     // with a torch copy issued first the fast settings are 5 .. 7 (126).  DFVO_REP_STREAMS overrides (tuning aid).
     // (The fused pipeline no longer depends on this: it measures which streams share a pipe and passes rep0 / rep1 in,
     // stream_pool.hip.)
+    // rep0 / rep1 may be one stream, and with `borrowed` the stream of the chain itself (the fused pipeline's lane layout): a
+    // side stream then runs its work in the chain's own order, and the waits between the two are satisfied by stream order.
     const int n_streams = rep0 ? 2 : rep_stream_count();
-    n_rep_owned = n_streams;
+    n_rep_owned = borrowed ? 0 : n_streams;
     for (int r = 0; r < MAX_REP; r++) {
         if (rep0 && r < 2)
             s_rep[r] = r == 0 ? rep0 : (rep1 ? rep1 : rep0);
@@ -75,12 +78,12 @@ int TrackerBuffers::init(hipStream_t rep0, hipStream_t rep1) {
     return DFVO_OK;
 }
 
-int TrackerBuffers::rebind_streams(hipStream_t rep0, hipStream_t rep1) {
-    DFVO_ARG_CHECK(!shared && rep0 && rep1 && rep0 != rep1, "TrackerBuffers::rebind_streams: bad argument");
+int TrackerBuffers::rebind_streams(hipStream_t rep0, hipStream_t rep1, bool borrowed) {
+    DFVO_ARG_CHECK(!shared && rep0 && rep1, "TrackerBuffers::rebind_streams: bad argument");
     DFVO_HIP_CHECK(hipDeviceSynchronize());
     for (int r = 0; r < n_rep_owned && r < MAX_REP; r++)
         if (s_rep[r] && !(r == 1 && s_rep[1] == s_rep[0])) (void)hipStreamDestroy(s_rep[r]);
-    n_rep_owned = 2;
+    n_rep_owned = borrowed ? 0 : 2;  // (release() destroys an aliased pair once)
     for (int r = 0; r < MAX_REP; r++) s_rep[r] = (r & 1) ? rep1 : rep0;
     return DFVO_OK;
 }

@@ -12,23 +12,36 @@
 // and hands the roles out by pipe: the two flow-net instances a pipe each, the depth net and the run-ahead homography
 // chains a third, the RandomState-ordered chain and its side streams the fourth, alone.
 //
+// Hardware queues.  The runtime backs a process's streams with GPU_MAX_HW_QUEUES hardware queues (default 4, read when HIP
+// initialises) and deals further streams onto the same queues.  Streams of one queue execute in host enqueue order whatever
+// their events say, and the chain's own time does not show it: both of its events sit behind the partner's work, so it
+// measures its unloaded time (with four queues the chain-time probe saw twelve groups of one and the pipeline fell back to
+// creation order: profiles/lanes_ab.txt).  The probe therefore also times the END of the chain against the end of the
+// partner's spinning -- a chain that ends a whole chain length after it ran behind it, in its queue -- and the pool reports
+// queue_group[] / nqueues next to group[] / ngroups.  Streams of one queue count as streams of one pipe.  The decision
+// logic (times -> groups, what counts as consistent, the expected shape) is host-only code in stream_layout.h.
+//
 // Robustness (round 6).  The probe is a wall-clock measurement, so it is (a) overridable, (b) accepted only when it repeats,
 // (c) never silently wrong:
 //   DFVO_STREAM_POOL=creation   no probe: every role gets a freshly created stream (the runtime's creation order decides)
 //   DFVO_STREAM_POOL=probe      (default) measure; a classification is ACCEPTED when it has the shape the hardware gives a
-//                               process whose queues are all its own (n = 4 m streams -> four groups of m), or when two
+//                               process whose queues are all its own (n = 4 m streams -> four groups of m, on n queues
+//                               or n / q on each of q), or when two
 //                               passes agree stream for stream (a process that already owns more streams than
 //                               GPU_MAX_HW_QUEUES -- torch, the nets' own -- shares hardware queues and legitimately shows
 //                               other shapes: bench.py --surface mirrors sees six groups, identically, on every pass)
 //   DFVO_STREAM_POOL_FORCE_FAIL=1   (test hook) every measurement reports failure
-// When no pass is accepted (or a measurement fails) the pool reports zero groups, its users fall back to creation-order
-// streams and a line on stderr says so (once per pool, i.e. per session / pipeline object).  DFVO_STREAM_PROBE_VERBOSE=1 prints every pass.
+// A pass whose relations are no equivalence (a with b, b with c, not a with c) is never accepted.
+// When no pass is accepted (or a measurement fails) the pool reports zero groups and zero queues, its users fall back to creation-order
+// streams and a line on stderr says so (once per pool, i.e. per session / pipeline object).  DFVO_STREAM_PROBE_VERBOSE=1 prints every pass, =2 its times too.
 #include "dfvo_common.h"
+#include "stream_layout.h"
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 namespace dfvo {
@@ -48,43 +61,55 @@ static float chain_us(hipStream_t s, hipEvent_t e0, hipEvent_t e1, int n) {
     return ms * 1e3f;
 }
 
-// one classification pass over the already created streams; returns false when a measurement failed
-static bool classify(const std::vector<hipStream_t>& s, hipEvent_t e0, hipEvent_t e1, std::vector<int>* group, int* ngroups) {
+// One measurement: stream a busy for ~0.16 ms (8 x 20 us, wall_clock64 ticks at 100 MHz), the chain on b inside that window.
+// ev: [0] on b in front of everything (the common origin), [1] behind the spinning on a, [2] / [3] around the chain on b.
+static bool loaded_sample(hipStream_t sa, hipStream_t sb, hipEvent_t* ev, int n_chain, PoolSample* m) {
+    if (hipEventRecord(ev[0], sb) != hipSuccess) return false;
+    for (int k = 0; k < 8; ++k) hipLaunchKernelGGL(k_pool_spin, dim3(1), dim3(64), 0, sa, 2000LL);
+    if (hipEventRecord(ev[1], sa) != hipSuccess || hipEventRecord(ev[2], sb) != hipSuccess) return false;
+    for (int k = 0; k < n_chain; ++k) hipLaunchKernelGGL(k_pool_empty, dim3(1), dim3(64), 0, sb);
+    if (hipEventRecord(ev[3], sb) != hipSuccess || hipEventSynchronize(ev[3]) != hipSuccess || hipStreamSynchronize(sa) != hipSuccess)
+        return false;
+    float chain = 0.f, spin_end = 0.f, chain_end = 0.f;
+    if (hipEventElapsedTime(&chain, ev[2], ev[3]) != hipSuccess || hipEventElapsedTime(&spin_end, ev[0], ev[1]) != hipSuccess ||
+        hipEventElapsedTime(&chain_end, ev[0], ev[3]) != hipSuccess)
+        return false;
+    m->chain_us = chain * 1e3f;
+    m->lag_us = (chain_end - spin_end) * 1e3f;
+    return true;
+}
+
+// one classification pass over the already created streams: measures every pair, the decision is stream_layout.h's.
+// Returns false when a measurement failed; *consistent = the relations found are equivalences.
+static bool classify(const std::vector<hipStream_t>& s, hipEvent_t* ev, PoolClasses* out, bool* consistent) {
     const int n = (int)s.size(), CH = 24;  // 24 dependent empty launches: ~40 us alone, ~100 us next to a busy stream on their pipe
     if (getenv("DFVO_STREAM_POOL_FORCE_FAIL")) return false;
-    group->assign(n, -1);
     std::vector<float> base(n);
     for (int i = 0; i < n; ++i) {  // the faster of two: a hiccup in the baseline would hide every partner of the stream
-        const float t0 = chain_us(s[i], e0, e1, CH), t1 = chain_us(s[i], e0, e1, CH);
-        if (t0 < 0.f || t1 < 0.f) return false;
+        const float t0 = chain_us(s[i], ev[2], ev[3], CH), t1 = chain_us(s[i], ev[2], ev[3], CH);
+        if (t0 <= 0.f || t1 <= 0.f) return false;
         base[i] = std::min(t0, t1);
     }
-    // stream a busy for ~0.16 ms (8 x 20 us, wall_clock64 ticks at 100 MHz), the chain on b inside that window; < 0: failed
-    auto slowed = [&](int a, int b) -> int {
-        for (int k = 0; k < 8; ++k) hipLaunchKernelGGL(k_pool_spin, dim3(1), dim3(64), 0, s[a], 2000LL);
-        const float t = chain_us(s[b], e0, e1, CH);
-        if (hipStreamSynchronize(s[a]) != hipSuccess || t < 0.f || base[b] <= 0.f) return -1;
-        return t > 1.6f * base[b] ? 1 : 0;
-    };
-    *ngroups = 0;
-    for (int a = 0; a < n; ++a) {
-        if ((*group)[a] >= 0) continue;
-        (*group)[a] = *ngroups;
+    std::vector<PoolSample> m1((size_t)n * n, PoolSample{0.f, 0.f}), m2 = m1;
+    for (int a = 0; a < n; ++a)
         for (int b = a + 1; b < n; ++b) {
-            if ((*group)[b] >= 0) continue;
-            // A partner slows the chain 2.5x every time; an unrelated hiccup (another process's interrupt, a clock step) slows ONE
-            // measurement.  Round 6 saw a one-measurement false positive repeat on the next pass -- both passes accepted it -- and
-            // the class surface ran at 81 instead of 148 frames/s (profiles/r6o_probe_stability.txt): a positive now has to show
-            // twice in a row before two streams are put on one pipe.
-            int v = slowed(a, b);
-            if (v < 0) return false;
-            if (v == 1) {
-                v = slowed(a, b);
-                if (v < 0) return false;
-            }
-            if (v == 1) (*group)[b] = *ngroups;
+            // A partner slows the chain 2.5x (or holds it back) every time; an unrelated hiccup (another process's interrupt, a
+            // clock step) slows ONE measurement.  Round 6 saw a one-measurement false positive repeat on the next pass -- both
+            // passes accepted it -- and the class surface ran at 81 instead of 148 frames/s (profiles/r6o_probe_stability.txt):
+            // a positive has to show twice in a row before two streams are put on one pipe or one queue.
+            const size_t i = (size_t)a * n + b;
+            if (!loaded_sample(s[a], s[b], ev, CH, &m1[i])) return false;
+            if (pool_rel_of(base[b], m1[i]) != POOL_REL_NONE && !loaded_sample(s[a], s[b], ev, CH, &m2[i])) return false;
         }
-        ++*ngroups;
+    *consistent = pool_classify(n, base.data(), m1.data(), m2.data(), out);
+    if (getenv("DFVO_STREAM_PROBE_VERBOSE")) {
+        const char* v = getenv("DFVO_STREAM_PROBE_VERBOSE");
+        if (atoi(v) >= 2)  // the raw times: chain / lag [us] of the chain on b (column) while a (row) spins
+            for (int a = 0; a < n; ++a) {
+                fprintf(stderr, "dfvo stream pool: base %5.0f | a=%2d:", base[a], a);
+                for (int b = a + 1; b < n; ++b) fprintf(stderr, " %4.0f/%-5.0f", m1[(size_t)a * n + b].chain_us, m1[(size_t)a * n + b].lag_us);
+                fprintf(stderr, "\n");
+            }
     }
     return true;
 }
@@ -93,10 +118,13 @@ int StreamPool::create(int n) {
     release();
     s.resize(n, nullptr);
     group.assign(n, -1);
+    queue_group.assign(n, -1);
     for (int i = 0; i < n; ++i) DFVO_HIP_CHECK(hipStreamCreateWithFlags(&s[i], hipStreamNonBlocking));
-    hipEvent_t e0, e1;
-    DFVO_HIP_CHECK(hipEventCreate(&e0));
-    DFVO_HIP_CHECK(hipEventCreate(&e1));
+    hipEvent_t ev[4];
+    for (auto& e : ev) DFVO_HIP_CHECK(hipEventCreate(&e));
+    auto drop_events = [&] {
+        for (auto& e : ev) (void)hipEventDestroy(e);
+    };
     for (int i = 0; i < n; ++i) hipLaunchKernelGGL(k_pool_empty, dim3(1), dim3(64), 0, s[i]);
     DFVO_HIP_CHECK(hipDeviceSynchronize());
     // The hardware spreads consecutive queues over its four pipes, so n = 4 m streams created back to back must come out as
@@ -107,50 +135,56 @@ int StreamPool::create(int n) {
     const char* mode = getenv("DFVO_STREAM_POOL");
     bool ok = false;
     if (mode && !strcmp(mode, "creation")) {
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        ngroups = 0;  // (the users' "no measurement" branch: creation-order streams)
+        drop_events();
+        ngroups = nqueues = 0;  // (the users' "no measurement" branch: creation-order streams)
         return DFVO_OK;
     }
-    std::vector<std::vector<int>> seen;
+    std::vector<std::pair<std::vector<int>, std::vector<int>>> seen;
     int attempts = 0;
     for (int attempt = 0; attempt < 5 && !ok; ++attempt) {
         for (int k = 0; k < 25 * (attempt + 1); ++k)  // 0.5, 1, 1.5 ... ms of spinning on one stream
             hipLaunchKernelGGL(k_pool_spin, dim3(1), dim3(64), 0, s[0], 2000LL);
         DFVO_HIP_CHECK(hipDeviceSynchronize());
-        std::vector<int> g2;
-        int ng2 = 0;
+        PoolClasses c;
+        bool consistent = false;
         ++attempts;
-        if (!classify(s, e0, e1, &g2, &ng2)) break;  // a failed measurement: nothing is trusted
-        bool shape = n % 4 == 0 && ng2 == 4;
-        for (int g = 0; g < ng2 && shape; ++g) {
-            int c = 0;
-            for (int i = 0; i < n; ++i) c += g2[i] == g ? 1 : 0;
-            shape = c == n / 4;
-        }
-        ok = shape || std::find(seen.begin(), seen.end(), g2) != seen.end();  // (group ids are canonical: first-seen order)
+        if (!classify(s, ev, &c, &consistent)) break;  // a failed measurement: nothing is trusted
+        const bool shape = consistent && pool_expected_shape(c);
+        const auto key = std::make_pair(c.group, c.queue_group);  // (group ids are canonical: first-seen order)
+        ok = shape || (consistent && std::find(seen.begin(), seen.end(), key) != seen.end());
         if (getenv("DFVO_STREAM_PROBE_VERBOSE")) {
-            fprintf(stderr, "dfvo stream pool: attempt %d, %d streams, %d pipe groups (%s):", attempt, n, ng2,
-                    ok ? (shape ? "accepted: expected shape" : "accepted: repeated") : "not yet accepted");
-            for (int i = 0; i < n; ++i) fprintf(stderr, " %d", g2[i]);
+            fprintf(stderr, "dfvo stream pool: attempt %d, %d streams, %d pipe groups, %d queues (%s):", attempt, n, c.ngroups, c.nqueues,
+                    ok ? (shape ? "accepted: expected shape" : "accepted: repeated") : consistent ? "not yet accepted" : "not consistent");
+            for (int i = 0; i < n; ++i) fprintf(stderr, " %d", c.group[i]);
+            fprintf(stderr, " | queues:");
+            for (int i = 0; i < n; ++i) fprintf(stderr, " %d", c.queue_group[i]);
             fprintf(stderr, "\n");
         }
-        seen.push_back(g2);
+        if (consistent) seen.push_back(key);
         if (ok) {
-            group = g2;
-            ngroups = ng2;
+            group = c.group;
+            queue_group = c.queue_group;
+            ngroups = c.ngroups;
+            nqueues = c.nqueues;
         }
     }
     if (!ok) {
         fprintf(stderr, "dfvo stream pool: the pipe probe did not settle in %d pass(es); streams keep the runtime's creation order "
                         "(set DFVO_STREAM_POOL=creation to skip the probe, DFVO_STREAM_PROBE_VERBOSE=1 to see its passes)\n", attempts);
         group.assign(n, -1);
-        ngroups = 0;
+        queue_group.assign(n, -1);
+        ngroups = nqueues = 0;
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    drop_events();
     DFVO_HIP_CHECK(hipGetLastError());
     return DFVO_OK;
+}
+
+hipStream_t StreamPool::take_index(int i) {
+    if (i < 0 || i >= (int)s.size()) return nullptr;
+    hipStream_t r = s[i];
+    s[i] = nullptr;
+    return r;
 }
 
 hipStream_t StreamPool::take(int g) {
@@ -174,7 +208,8 @@ void StreamPool::release() {
         if (q) (void)hipStreamDestroy(q);
     s.clear();
     group.clear();
-    ngroups = 0;
+    queue_group.clear();
+    ngroups = nqueues = 0;
 }
 
 }  // namespace dfvo

@@ -165,11 +165,14 @@ struct TrackerBuffers {
     int *perm = nullptr, *cell_count = nullptr, *cell_sel = nullptr, *pix = nullptr, *scratch = nullptr;
     uint8_t *best_inliers = nullptr, *inl_a = nullptr, *inl_b = nullptr;
     int kp_cap = 0, sel_cap = 0;
-    // rep0 / rep1: side streams chosen by the caller (the fused pipeline hands out streams by dispatch pipe); null = create
-    int init(hipStream_t rep0 = nullptr, hipStream_t rep1 = nullptr);
+    // rep0 / rep1: side streams chosen by the caller (the fused pipeline hands out streams by dispatch pipe); null = create.
+    // They may be the same stream.  borrowed: the caller keeps and destroys them -- they may then also be the stream the
+    // chain itself is enqueued on (the lane layout of the fused pipeline: one stream per hardware queue)
+    int init(hipStream_t rep0 = nullptr, hipStream_t rep1 = nullptr, bool borrowed = false);
     // replaces the side streams of an idle, non-shared buffer set by two streams the caller chose by dispatch pipe (the frame
-    // session, session.hip); this object owns and destroys them from then on
-    int rebind_streams(hipStream_t rep0, hipStream_t rep1);
+    // session, session.hip); this object owns and destroys them from then on, unless they are `borrowed` (see init).  The
+    // two may be one stream
+    int rebind_streams(hipStream_t rep0, hipStream_t rep1, bool borrowed = false);
     // second and further buffer sets of the fused pipeline: own keypoint / RANSAC workspaces, but the numpy
     // RandomState and the (serialised anyway) RNG-side streams and events of `first`
     int init_shared(const TrackerBuffers& first);

@@ -118,6 +118,18 @@ class TrackingPipeline:
     def sync(self):
         capi.check(self.lib.dfvo_pipeline_sync(self.h))
 
+    def stream_layout(self):
+        """the stream layout in use, parsed: {"layout": "lanes" | "wide" | "creation", "groups": n, "queues": n, "streams": n,
+        "trk": i, ...} with, per role, the index of its stream (dfvo_pipeline_stream_layout); "text" is the line itself"""
+        buf = C.create_string_buffer(256)
+        capi.check(self.lib.dfvo_pipeline_stream_layout(self.h, buf, len(buf)))
+        text = buf.value.decode()
+        d = {"text": text}
+        for kv in text.split():
+            k, v = kv.split("=")
+            d[k] = v if k == "layout" else int(v)
+        return d
+
     def net_flops(self):
         return self.lib.dfvo_pipeline_net_flops(self.h)
 

@@ -547,6 +547,17 @@ int dfvo_pipeline_get_keypoints(dfvo_pipeline* p, int slot, int cap, double* h_k
 int dfvo_pipeline_get_rng_state(dfvo_pipeline* p, uint32_t* h_state625);
 int dfvo_pipeline_set_rng_state(dfvo_pipeline* p, const uint32_t* h_state625);
 int dfvo_pipeline_sync(dfvo_pipeline* p);
+/* The stream layout in use, as one line of text in buf[n] (DFVO_ERR_ARG when it does not fit; 256 bytes do):
+ *   "layout=lanes groups=4 queues=4 streams=4 trk=3 rep0=3 rep1=3 depth=2 pre0=2 pre1=2 flow=0 flow_x=1"
+ * layout   wide: a stream per role, placed by dispatch pipe (eight or more hardware queues) | lanes: four streams, one per
+ *          hardware queue, the roles of a lane on one stream (four to seven queues; GPU_MAX_HW_QUEUES defaults to 4) |
+ *          creation: no usable measurement, freshly created streams.  DFVO_STREAM_LAYOUT=auto|wide|lanes (read by
+ *          dfvo_pipeline_create) forces one.
+ * groups / queues   dispatch-pipe groups and hardware queues the pipeline's twelve candidate streams were found to span (0: no
+ *          measurement)
+ * streams  distinct streams the roles run on; per role the index of its stream among them (equal = the same stream; -1 =
+ *          the role does not exist, flow_x with one flow-net instance) */
+int dfvo_pipeline_stream_layout(dfvo_pipeline* p, char* buf, int n);
 double dfvo_pipeline_net_flops(const dfvo_pipeline* p);
 
 /* ---- frame session: the reference's own synchronous call order, fast (df-vo_amd/csrc/session.hip) ----
