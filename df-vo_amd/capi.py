@@ -71,6 +71,12 @@ class PipelineCfg(C.Structure):
                 ("pnp_reproj_thre", C.c_double)]
 
 
+class PipelineOpts(C.Structure):
+    _fields_ = [("kp_source", C.c_int), ("kp_score_method", C.c_int), ("kp_sampled_num", C.c_int),
+                ("flow_crop", C.c_double * 4), ("validity_method", C.c_int), ("validity_thre", C.c_double),
+                ("scale_method", C.c_int), ("tracking_method", C.c_int)]
+
+
 class TrackOut(C.Structure):
     _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("scale", C.c_double), ("status", C.c_int),
                 ("n_kp", C.c_int), ("good_kp_found", C.c_int), ("best_inlier_cnt", C.c_int), ("num_valid", C.c_int),
@@ -210,6 +216,7 @@ SIGNATURES = {
     "dfvo_pipeline_set_depth_param": (_i, [_vp, C.c_char_p, _vp, _i, _ip]),
     "dfvo_pipeline_finalize": (_i, [_vp]),
     "dfvo_pipeline_seed": (_i, [_vp, C.c_uint32]),
+    "dfvo_pipeline_set_options": (_i, [_vp, C.POINTER(PipelineOpts)]),
     "dfvo_pipeline_set_graph": (_i, [_vp, _i]),
     "dfvo_pipeline_enqueue_nets": (_i, [_vp, _i, _vp, _vp, _vp]),
     "dfvo_pipeline_track": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(TrackOut)]),

@@ -3,6 +3,8 @@
 // Orchestration follows /root/reference/libs/dfvo.py:299-345 (deep_model_inference) and :121-262
 // (tracking): the host-side glue of the reference (cv2.resize nearest, preprocess_depth, dict passing)
 // becomes device kernels; the pose composition stays on the host (dfvo.py:109-119).
+// dfvo_pipeline_set_options selects the keypoint source (local_bestN | bestN | sampled), the validity and scale-RANSAC methods
+// and hybrid | PnP-only tracking; without it the pipeline runs default_configuration.yml.
 #include "../../include/dfvo_hip.h"
 #include <algorithm>
 #include <chrono>
@@ -38,9 +40,10 @@ struct dfvo_pipeline {
     int* h_info[DFVO_PIPELINE_SLOTS] = {};
     bool prefetched[DFVO_PIPELINE_SLOTS] = {};
     // dfvo_pipeline_track_begin / _end: results of the RandomState-ordered chain land in pinned host memory behind e_res
-    void* h_res[DFVO_PIPELINE_SLOTS] = {};   // PoseState | ScaleResult
+    void* h_res[DFVO_PIPELINE_SLOTS] = {};   // PoseState | ScaleResult | PnpResult (tracking_method PnP)
     hipEvent_t e_res[DFVO_PIPELINE_SLOTS] = {};
-    int begun_n[DFVO_PIPELINE_SLOTS] = {};   // -1: no chain pending, -2: pending pair had no good keypoints, else keypoint count
+    // -1: no chain pending, -2: pending pair had no good keypoints, -3: PnP-only pair without a reference depth, else keypoint count
+    int begun_n[DFVO_PIPELINE_SLOTS] = {};
     const double* begun_depth_override[DFVO_PIPELINE_SLOTS] = {};
     int pending_slot = -1;  // the one pair begun and not yet collected (the chains consume ONE RandomState, in pair order)
     hipStream_t s_flow = nullptr, s_depth = nullptr, s_trk = nullptr;
@@ -63,6 +66,12 @@ struct dfvo_pipeline {
     float* ref_raw = nullptr;
     bool has_ref_depth = false;
     dfvo_pipeline_cfg cfg;
+    // dfvo_pipeline_set_options: the tracking configuration beyond default_configuration.yml (all zero = that configuration)
+    dfvo_pipeline_opts opts = {};
+    bool started = false;                   // a pair or a reference depth was enqueued: the options are final
+    BestNBuffers bestn[DFVO_PIPELINE_SLOTS];  // kp_source bestN: the whole-image selection's workspace, per slot
+    int* d_samples = nullptr;               // kp_source sampled: generate_kp_samples' index list, uploaded once
+    int sample_crop[4] = {0, 0, 0, 0};      // y0 y1 x0 x1 [px] of cfg.crop.flow_crop
     bool nets_ready = false;
     const FlowNet* last_flow = nullptr;  // the instance that ran the previous pair (carry source of a d_ref == NULL call)
     // Stream layout (stream_layout.h).  LAYOUT_LANES: lane[0 .. 3] are the pipeline's only streams, one per hardware queue,
@@ -231,7 +240,7 @@ int dfvo_pipeline_create(const dfvo_pipeline_cfg* cfg, dfvo_pipeline** out) {
         if (hipEventCreateWithFlags(&p->e_pre[i], hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&p->e_res[i], hipEventDisableTiming) != hipSuccess ||
             hipHostMalloc((void**)&p->h_info[i], 4 * sizeof(int), hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void**)&p->h_res[i], sizeof(PoseState) + sizeof(ScaleResult), hipHostMallocDefault) != hipSuccess)
+            hipHostMalloc((void**)&p->h_res[i], sizeof(PoseState) + sizeof(ScaleResult) + sizeof(PnpResult), hipHostMallocDefault) != hipSuccess)
             return fail(DFVO_ERR_HIP);
         p->begun_n[i] = -1;
     }
@@ -279,6 +288,8 @@ void dfvo_pipeline_destroy(dfvo_pipeline* p) {
     }
     p->depth.destroy();
     for (int i = DFVO_PIPELINE_SLOTS - 1; i >= 0; i--) p->tbs[i].release();
+    for (BestNBuffers& bb : p->bestn) bb.release();
+    if (p->d_samples) (void)hipFree(p->d_samples);
     for (int i = 0; i < 2; i++)
         if (p->s_pre[i] && !lanes) (void)hipStreamDestroy(p->s_pre[i]);
     for (int i = 0; i < DFVO_PIPELINE_SLOTS; i++) {
@@ -360,12 +371,70 @@ int dfvo_pipeline_seed(dfvo_pipeline* p, uint32_t seed) {
     return DFVO_OK;
 }
 
+int dfvo_pipeline_set_options(dfvo_pipeline* p, const dfvo_pipeline_opts* o) {
+    DFVO_ARG_CHECK(p && o, "dfvo_pipeline_set_options: null argument");
+    DFVO_ARG_CHECK(!p->started, "dfvo_pipeline_set_options: comes before the first dfvo_pipeline_enqueue_nets / _set_ref_*");
+    DFVO_ARG_CHECK(o->kp_source >= DFVO_KP_SOURCE_LOCAL_BESTN && o->kp_source <= DFVO_KP_SOURCE_SAMPLED,
+                   "dfvo_pipeline_set_options: kp_source is DFVO_KP_SOURCE_LOCAL_BESTN, _BESTN or _SAMPLED");
+    DFVO_ARG_CHECK(o->kp_score_method == DFVO_KP_SCORE_FLOW || o->kp_score_method == DFVO_KP_SCORE_FLOW_RATIO,
+                   "dfvo_pipeline_set_options: kp_score_method is DFVO_KP_SCORE_FLOW or DFVO_KP_SCORE_FLOW_RATIO");
+    DFVO_ARG_CHECK(o->validity_method >= DFVO_VALIDITY_GRIC && o->validity_method <= DFVO_VALIDITY_HOMO_RATIO,
+                   "dfvo_pipeline_set_options: validity_method is DFVO_VALIDITY_GRIC, _FLOW or _HOMO_RATIO");
+    DFVO_ARG_CHECK(o->validity_method == DFVO_VALIDITY_GRIC || o->validity_thre == o->validity_thre,
+                   "dfvo_pipeline_set_options: validity_thre is NaN");
+    DFVO_ARG_CHECK(o->scale_method == DFVO_SCALE_DEPTH_RATIO || o->scale_method == DFVO_SCALE_ABS_DIFF,
+                   "dfvo_pipeline_set_options: scale_method is DFVO_SCALE_DEPTH_RATIO or DFVO_SCALE_ABS_DIFF");
+    DFVO_ARG_CHECK(o->tracking_method == DFVO_TRACKING_HYBRID || o->tracking_method == DFVO_TRACKING_PNP,
+                   "dfvo_pipeline_set_options: tracking_method is DFVO_TRACKING_HYBRID or DFVO_TRACKING_PNP");
+    const dfvo_pipeline_cfg& c = p->cfg;
+    // every buffer the chosen source needs at its final size, here: nothing on the per-pair path allocates (hipFree waits
+    // for the whole device).  kp_count stays 0 for local_bestN, whose launcher sizes its own buffers as before
+    int kp_count = 0;
+    int crop[4] = {0, 0, 0, 0};
+    std::vector<int> samples;
+    if (o->kp_source == DFVO_KP_SOURCE_BESTN) {
+        DFVO_ARG_CHECK(c.kp_num_bestN >= 1, "dfvo_pipeline_set_options: bestN needs kp_num_bestN >= 1");
+        kp_count = c.kp_num_bestN;
+    } else if (o->kp_source == DFVO_KP_SOURCE_SAMPLED) {
+        DFVO_ARG_CHECK(o->kp_sampled_num >= 1, "dfvo_pipeline_set_options: sampled needs kp_sampled_num >= 1");
+        for (int i = 0; i < 4; ++i)
+            DFVO_ARG_CHECK(o->flow_crop[i] >= 0.0 && o->flow_crop[i] <= 1.0, "dfvo_pipeline_set_options: flow_crop fractions lie in [0, 1]");
+        crop[0] = (int)(o->flow_crop[0] * p->H);
+        crop[1] = (int)(o->flow_crop[1] * p->H);
+        crop[2] = (int)(o->flow_crop[2] * p->W);
+        crop[3] = (int)(o->flow_crop[3] * p->W);
+        DFVO_ARG_CHECK(crop[0] < crop[1] && crop[2] < crop[3], "dfvo_pipeline_set_options: flow_crop is empty");
+        kp_count = o->kp_sampled_num;
+        samples.resize(kp_count);
+        generate_kp_samples(crop[0], crop[1], crop[2], crop[3], kp_count, samples.data());
+    }
+    if (p->d_samples) {
+        (void)hipFree(p->d_samples);
+        p->d_samples = nullptr;
+    }
+    if (!samples.empty()) {
+        DFVO_HIP_CHECK(hipMalloc((void**)&p->d_samples, sizeof(int) * samples.size()));
+        DFVO_HIP_CHECK(hipMemcpy(p->d_samples, samples.data(), sizeof(int) * samples.size(), hipMemcpyHostToDevice));
+    }
+    if (kp_count > 0) {
+        for (int i = 0; i < DFVO_PIPELINE_SLOTS; i++) {
+            P_TRY(p->tbs[i].ensure_kp(kp_count, 1, 1));
+            if (o->kp_source == DFVO_KP_SOURCE_BESTN) P_TRY(p->bestn[i].ensure((size_t)p->H * p->W, 0));
+        }
+        if (c.pnp_iters > 0) P_TRY(p->pnp.ensure(kp_count + 8, c.pnp_iters));
+    }
+    for (int i = 0; i < 4; ++i) p->sample_crop[i] = crop[i];
+    p->opts = *o;
+    return DFVO_OK;
+}
+
 int dfvo_pipeline_enqueue_nets(dfvo_pipeline* p, int slot, const uint8_t* d_ref, const uint8_t* d_cur,
                                const uint8_t* d_cur_feed) {
     DFVO_ARG_CHECK(p && p->nets_ready && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS) && d_cur,
                    "dfvo_pipeline_enqueue_nets: bad argument");
     DFVO_ARG_CHECK(d_ref || p->last_flow, "dfvo_pipeline_enqueue_nets: d_ref == NULL (reference frame = the previous call's "
                                           "current frame) needs a previous call");
+    p->started = true;
     const size_t px = (size_t)p->H * p->W;
     // depth of the current frame (dfvo.py:305-319); without a caller-resized frame the LANCZOS resize of
     // deep_models.py:195-199 runs here, ahead of the net on its stream
@@ -407,6 +476,7 @@ int dfvo_pipeline_enqueue_nets(dfvo_pipeline* p, int slot, const uint8_t* d_ref,
 int dfvo_pipeline_set_ref_depth(dfvo_pipeline* p, const uint8_t* d_feed, const double* d_depth_override) {
     DFVO_ARG_CHECK(p && p->nets_ready && ((d_feed != nullptr) != (d_depth_override != nullptr)),
                    "dfvo_pipeline_set_ref_depth: exactly one of d_feed / d_depth_override");
+    p->started = true;
     const size_t px = (size_t)p->H * p->W;
     if (d_depth_override) {
         DFVO_HIP_CHECK(hipMemcpyAsync(p->ref_depth, d_depth_override, px * sizeof(double), hipMemcpyDeviceToDevice, p->s_trk));
@@ -448,7 +518,9 @@ static int roll_ref_depth(dfvo_pipeline* p, int slot, const double* d_depth_over
     return DFVO_OK;
 }
 
-static void fill_pose_cfg(const dfvo_pipeline_cfg& c, PoseConfig* pc) {
+static void fill_pose_cfg(const dfvo_pipeline_cfg& c, const dfvo_pipeline_opts& o, PoseConfig* pc) {
+    pc->validity = o.validity_method;
+    pc->validity_thre = o.validity_method == DFVO_VALIDITY_GRIC ? 0.0 : o.validity_thre;
     pc->fx = c.fx;
     pc->cx = c.cx;
     pc->cy = c.cy;
@@ -461,6 +533,29 @@ static void fill_pose_cfg(const dfvo_pipeline_cfg& c, PoseConfig* pc) {
     }
 }
 
+static void fill_pnp_cfg(const dfvo_pipeline_cfg& c, PnpConfig* pc3) {
+    pc3->fx = c.fx;
+    pc3->fy = c.fy;
+    pc3->cx = c.cx;
+    pc3->cy = c.cy;
+    for (int i = 0; i < 9; i++) pc3->inv_K[i] = c.Kinv[i];
+    pc3->min_depth = c.min_depth;
+    pc3->max_depth = c.max_depth;
+    pc3->repeat = c.pnp_repeat;
+    pc3->iters = c.pnp_iters;
+    pc3->reproj_thre = c.pnp_reproj_thre;
+}
+
+static void fill_pnp_out(const PnpResult& pr, dfvo_track_out* out) {
+    for (int i = 0; i < 9; i++) out->R[i] = pr.R[i];
+    for (int i = 0; i < 3; i++) out->t[i] = pr.tvec[i];
+    out->scale = 1.0;
+    out->pnp_found = pr.found;
+    out->pnp_inliers = pr.best_inliers;
+    out->pnp_n_filtered = pr.n_filtered;
+    out->status = DFVO_TRACK_PNP;
+}
+
 // RNG-independent half of the solver stage of `slot` (keypoint selection, homography RANSAC + refinement, GRIC-H):
 // waits on the device for the slot's flow outputs and runs on a stream of its own, so it executes as soon as those
 // nets are done -- typically while dfvo_pipeline_track of the previous pair is still blocking the host.  The numpy
@@ -468,15 +563,31 @@ static void fill_pose_cfg(const dfvo_pipeline_cfg& c, PoseConfig* pc) {
 static int enqueue_pre_part(dfvo_pipeline* p, int slot, const float* d_flow_override, const float* d_diff_override,
                             hipStream_t sp) {
     const dfvo_pipeline_cfg& c = p->cfg;
+    const dfvo_pipeline_opts& o = p->opts;
     TrackerBuffers& tb = p->tbs[slot];
     DFVO_HIP_CHECK(hipStreamWaitEvent(sp, p->e_flow[slot], 0));
     const float* flow = d_flow_override ? d_flow_override : p->fwd[slot];
     const float* diff = d_diff_override ? d_diff_override : p->diff[slot];
-    P_TRY(enqueue_local_bestn(tb, flow, diff, p->H, p->W, c.kp_num_row, c.kp_num_col, c.kp_num_bestN, (float)c.kp_thre, sp));
+    // the keypoint stage by source; each leaves tb.kp_ref / tb.kp_cur / tb.kp_info = [n, good_kp_found, ..] behind on sp
+    if (o.kp_source == DFVO_KP_SOURCE_BESTN) {
+        P_TRY(enqueue_bestn_flow_kp(p->bestn[slot], flow, diff, p->H, p->W, c.kp_num_bestN, sp, tb.kp_ref, tb.kp_cur, tb.kp_info));
+    } else if (o.kp_source == DFVO_KP_SOURCE_SAMPLED) {
+        P_TRY(enqueue_kp_sampled(flow, p->H, p->W, p->sample_crop[0], p->sample_crop[1], p->sample_crop[2], p->sample_crop[3],
+                                 p->d_samples, o.kp_sampled_num, tb.kp_ref, tb.kp_cur, sp, tb.kp_info));
+    } else {
+        P_TRY(enqueue_local_bestn(tb, flow, diff, p->H, p->W, c.kp_num_row, c.kp_num_col, c.kp_num_bestN, (float)c.kp_thre, sp,
+                                  o.kp_score_method));
+    }
     DFVO_HIP_CHECK(hipMemcpyAsync(p->h_info[slot], tb.kp_info, 3 * sizeof(int), hipMemcpyDeviceToHost, sp));
     DFVO_HIP_CHECK(hipEventRecord(p->e_pre[slot], sp));  // the host only needs the keypoint count; tb.ev_h orders the rest
+    if (o.tracking_method == DFVO_TRACKING_PNP) {
+        // dfvo.py:165: no E-tracker at all.  The inlier mask stays what dfvo_pipeline_get_keypoints documents for a pair
+        // the E-tracker did not see: all ones
+        DFVO_HIP_CHECK(hipMemsetAsync(tb.best_inliers, 1, (size_t)tb.kp_cap, sp));
+        return DFVO_OK;
+    }
     PoseConfig pc;
-    fill_pose_cfg(c, &pc);
+    fill_pose_cfg(c, p->opts, &pc);
     P_TRY(enqueue_pose_h_part(tb, tb.kp_cap, pc, sp));  // keypoint count read on the device; kp_cap bounds the launches
     return DFVO_OK;
 }
@@ -504,7 +615,9 @@ int dfvo_pipeline_track_begin(dfvo_pipeline* p, int slot, const float* d_flow_ov
     static const bool trace = getenv("DFVO_TRACK_TRACE") != nullptr;
     if (trace && !tb.ev_t[0])
         for (int i = 0; i < 4; i++) DFVO_HIP_CHECK(hipEventCreate(&tb.ev_t[i]));
-    P_TRY(enqueue_scale_prepare(tb, p->H, p->W));  // side stream: the scale stage's fills leave the dependent chain
+    const bool pnp_only = p->opts.tracking_method == DFVO_TRACKING_PNP;
+    // side stream: the scale stage's fills leave the dependent chain
+    if (!pnp_only) P_TRY(enqueue_scale_prepare(tb, p->H, p->W));
     // A pre-part nobody prefetched: in the lane layout it goes onto the chain's lane (s), whose next work needs it anyway --
     // the depth lane may already hold later pairs' nets, and it would run behind them
     if (!p->prefetched[slot])
@@ -519,8 +632,27 @@ int dfvo_pipeline_track_begin(dfvo_pipeline* p, int slot, const float* d_flow_ov
         return DFVO_OK;
     }
     const int n = info[0];
+    if (pnp_only) {
+        // dfvo.py:225-250 on every pair: E_pose stays SE3(), so the only RandomState draws of the pair are PnP's shuffles.
+        // The keypoint stage is complete (the host waited for e_pre above); the reference depth is ordered on s by
+        // set_ref_depth / the previous pair's roll-over
+        if (!p->has_ref_depth) {
+            p->begun_n[slot] = -3;
+            p->pending_slot = slot;
+            return DFVO_OK;
+        }
+        PnpConfig pc3;
+        fill_pnp_cfg(c, &pc3);
+        P_TRY(enqueue_compute_pose_3d2d(p->pnp, tb.mt_state, tb.kp_ref, tb.kp_cur, tb.kp_info, n, p->ref_depth, p->H, p->W, pc3, s));
+        char* hr = (char*)p->h_res[slot] + sizeof(PoseState) + sizeof(ScaleResult);
+        DFVO_HIP_CHECK(hipMemcpyAsync(hr, p->pnp.result, sizeof(PnpResult), hipMemcpyDeviceToHost, s));
+        DFVO_HIP_CHECK(hipEventRecord(p->e_res[slot], s));
+        p->begun_n[slot] = n;
+        p->pending_slot = slot;
+        return DFVO_OK;
+    }
     PoseConfig pc;
-    fill_pose_cfg(c, &pc);
+    fill_pose_cfg(c, p->opts, &pc);
     P_TRY(enqueue_pose_e_part(tb, n, pc, s, p->d_T21));  // waits for tb.ev_h (the prefetched half) on the device
     DFVO_HIP_CHECK(hipStreamWaitEvent(s, p->e_depth[slot], 0));
     ScaleConfig sc;
@@ -532,6 +664,7 @@ int dfvo_pipeline_track_begin(dfvo_pipeline* p, int slot, const float* d_flow_ov
     sc.max_trials = c.scale_max_trials;
     sc.stop_prob = c.scale_stop_prob;
     sc.thre = c.scale_thre;
+    sc.method = p->opts.scale_method;
     const double* depth = d_depth_override ? d_depth_override : p->proc_depth[slot];
     P_TRY(enqueue_find_scale(tb, n, p->d_T21, depth, p->H, p->W, sc, s, tb.pose, true));
     if (tb.ev_t[3]) DFVO_HIP_CHECK(hipEventRecord(tb.ev_t[3], s));
@@ -575,6 +708,18 @@ int dfvo_pipeline_track_end(dfvo_pipeline* p, int slot, dfvo_track_out* out) {
         DFVO_HIP_CHECK(hipStreamSynchronize(s));
         return DFVO_OK;
     }
+    if (p->opts.tracking_method == DFVO_TRACKING_PNP) {
+        // the PnP chain was enqueued by track_begin: nothing to decide here, only its result to wait for
+        out->status = DFVO_TRACK_NEEDS_PNP;
+        if (n != -3) {
+            DFVO_HIP_CHECK(hipEventSynchronize(p->e_res[slot]));
+            PnpResult pr;
+            memcpy(&pr, (const char*)p->h_res[slot] + sizeof(PoseState) + sizeof(ScaleResult), sizeof(pr));
+            DFVO_ARG_CHECK(pr.status >= 0, "dfvo_pipeline_track: the PnP tracker reported an internal error");
+            fill_pnp_out(pr, out);
+        }
+        return roll_ref_depth(p, slot, d_depth_override);
+    }
     DFVO_HIP_CHECK(hipEventSynchronize(p->e_res[slot]));
     const double tr_wait = tr_ms(tr0);
     PoseState ps;
@@ -595,29 +740,14 @@ int dfvo_pipeline_track_end(dfvo_pipeline* p, int slot, dfvo_track_out* out) {
         out->status = DFVO_TRACK_NEEDS_PNP;
         if (p->has_ref_depth) {
             PnpConfig pc3;
-            pc3.fx = c.fx;
-            pc3.fy = c.fy;
-            pc3.cx = c.cx;
-            pc3.cy = c.cy;
-            for (int i = 0; i < 9; i++) pc3.inv_K[i] = c.Kinv[i];
-            pc3.min_depth = c.min_depth;
-            pc3.max_depth = c.max_depth;
-            pc3.repeat = c.pnp_repeat;
-            pc3.iters = c.pnp_iters;
-            pc3.reproj_thre = c.pnp_reproj_thre;
+            fill_pnp_cfg(c, &pc3);
             P_TRY(enqueue_compute_pose_3d2d(p->pnp, tb.mt_state, tb.kp_ref, tb.kp_cur, tb.kp_info, n,
                                             p->ref_depth, p->H, p->W, pc3, s));
             PnpResult pr;
             DFVO_HIP_CHECK(hipMemcpyAsync(&pr, p->pnp.result, sizeof(pr), hipMemcpyDeviceToHost, s));
             DFVO_HIP_CHECK(hipStreamSynchronize(s));
             DFVO_ARG_CHECK(pr.status >= 0, "dfvo_pipeline_track: the PnP fallback reported an internal error");
-            for (int i = 0; i < 9; i++) out->R[i] = pr.R[i];
-            for (int i = 0; i < 3; i++) out->t[i] = pr.tvec[i];
-            out->scale = 1.0;
-            out->pnp_found = pr.found;
-            out->pnp_inliers = pr.best_inliers;
-            out->pnp_n_filtered = pr.n_filtered;
-            out->status = DFVO_TRACK_PNP;
+            fill_pnp_out(pr, out);
         }
     } else {
         out->status = DFVO_TRACK_E;

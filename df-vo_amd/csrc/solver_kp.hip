@@ -174,7 +174,8 @@ __global__ __launch_bounds__(256) void k_bestn_select(const float* __restrict__ 
                                                        int W, int N, float* __restrict__ key, int* __restrict__ tosort,
                                                        int* __restrict__ map, int* __restrict__ Lpos, int* __restrict__ Rpos,
                                                        const int* __restrict__ count, double* __restrict__ kp1,
-                                                       double* __restrict__ kp2, int* __restrict__ info) {
+                                                       double* __restrict__ kp2, int* __restrict__ info, int tracker_info) {
+    // tracker_info: info is a tracker's kp_info [n, good_kp_found, regions] and not the one-int result size
     __shared__ int s_ctl[8], s_wsum[4], s_base;
     const int t = threadIdx.x;
     const int n = H * W;
@@ -202,7 +203,10 @@ __global__ __launch_bounds__(256) void k_bestn_select(const float* __restrict__ 
         cnt = s_base;
     }
     if (cnt <= N) {  // kth = N out of bounds
-        if (t == 0) info[0] = 0;
+        if (t == 0) {
+            info[0] = 0;
+            if (tracker_info) info[1] = info[2] = 0;
+        }
         return;
     }
     __threadfence_block();
@@ -219,7 +223,13 @@ __global__ __launch_bounds__(256) void k_bestn_select(const float* __restrict__ 
         kp2[i * 2] = (double)x + (double)flow[e];
         kp2[i * 2 + 1] = (double)y + (double)flow[(size_t)n + e];
     }
-    if (t == 0) info[0] = N;
+    if (t == 0) {
+        info[0] = N;
+        if (tracker_info) {
+            info[1] = 1;  // keypoint_sampler.py:96: only local_bestN clears good_kp_found
+            info[2] = 0;
+        }
+    }
 }
 
 void BestNBuffers::release() {
@@ -233,17 +243,16 @@ void BestNBuffers::release() {
     kp_cap = 0;
 }
 
-int enqueue_bestn_flow_kp(BestNBuffers& bb, const float* d_flow, const float* d_diff, int H, int W, int N, hipStream_t s) {
-    DFVO_ARG_CHECK(H > 0 && W > 0 && N >= 1 && (long long)H * W < (1ll << 30), "bestN: bad size");
-    const int n = H * W;
-    if ((size_t)n > bb.cap) {
+int BestNBuffers::ensure(size_t n, int N) {
+    BestNBuffers& bb = *this;
+    if (n > bb.cap) {
         const int keep_kp = bb.kp_cap;
         double* kp_keep = bb.kp;
         bb.kp = nullptr;
         bb.release();
         bb.kp = kp_keep;
         bb.kp_cap = keep_kp;
-        bb.cap = (size_t)n;
+        bb.cap = n;
         DFVO_HIP_CHECK(hipMalloc((void**)&bb.key_base, sizeof(float) * ((size_t)n + 16)));  // slack: the 4-wide scans over-read
         DFVO_HIP_CHECK(hipMemset(bb.key_base, 0, sizeof(float) * ((size_t)n + 16)));
         DFVO_HIP_CHECK(hipMalloc((void**)&bb.tosort, sizeof(int) * (size_t)n));
@@ -257,11 +266,22 @@ int enqueue_bestn_flow_kp(BestNBuffers& bb, const float* d_flow, const float* d_
         bb.kp_cap = N;
         DFVO_HIP_CHECK(hipMalloc((void**)&bb.kp, sizeof(double) * 4 * (size_t)N));
     }
+    return DFVO_OK;
+}
+
+int enqueue_bestn_flow_kp(BestNBuffers& bb, const float* d_flow, const float* d_diff, int H, int W, int N, hipStream_t s,
+                          double* d_kp1, double* d_kp2, int* d_info) {
+    DFVO_ARG_CHECK(H > 0 && W > 0 && N >= 1 && (long long)H * W < (1ll << 30), "bestN: bad size");
+    DFVO_ARG_CHECK((d_kp1 != nullptr) == (d_kp2 != nullptr) && (d_kp1 != nullptr) == (d_info != nullptr),
+                   "bestN: the destination is kp1, kp2 and info together");
+    const int n = H * W;
+    if (int rc = bb.ensure((size_t)n, d_kp1 ? 0 : N)) return rc;
     float* key = bb.key_base + 8;
     DFVO_HIP_CHECK(hipMemsetAsync(bb.count, 0, sizeof(int) * 4, s));
     hipLaunchKernelGGL(k_bestn_fill, dim3(cdiv(n, 256)), dim3(256), 0, s, d_diff, n, key, bb.tosort, bb.count);
     hipLaunchKernelGGL(k_bestn_select, dim3(1), dim3(256), 0, s, d_diff, d_flow, H, W, N, key, bb.tosort, bb.map, bb.Lpos,
-                       bb.Rpos, bb.count, bb.kp, bb.kp + 2 * (size_t)N, bb.count + 1);
+                       bb.Rpos, bb.count, d_kp1 ? d_kp1 : bb.kp, d_kp1 ? d_kp2 : bb.kp + 2 * (size_t)N, d_kp1 ? d_info : bb.count + 1,
+                       d_kp1 ? 1 : 0);
     DFVO_HIP_CHECK(hipGetLastError());
     return DFVO_OK;
 }
@@ -606,8 +626,14 @@ int enqueue_rigid_flow_kp(RigidKpBuffers& rb, const float* d_flow, const float* 
 // sampled_kp (kp_selection.py:327-378): the k-th pixel (row-major) of the cropped grid [y0:y1, x0:x1] for every k of
 // the uniform index list; kp1 = (x, y), kp2 = kp1 + flow (float32 promoted to float64, as numpy does)
 __global__ void k_kp_sampled(const float* __restrict__ flow, int H, int W, int y0, int x0, int cw,
-                             const int* __restrict__ idx, int n, double* __restrict__ kp1, double* __restrict__ kp2) {
+                             const int* __restrict__ idx, int n, double* __restrict__ kp1, double* __restrict__ kp2,
+                             int* __restrict__ info /*optional: a tracker's kp_info [n, good_kp_found, regions]*/) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (info && i == 0) {
+        info[0] = n;
+        info[1] = 1;
+        info[2] = 0;
+    }
     if (i >= n) return;
     const int k = idx[i];
     const int yy = y0 + k / cw, xx = x0 + k % cw;
@@ -619,12 +645,21 @@ __global__ void k_kp_sampled(const float* __restrict__ flow, int H, int W, int y
 }
 
 int enqueue_kp_sampled(const float* d_flow, int H, int W, int y0, int y1, int x0, int x1, const int* d_idx, int n,
-                       double* d_kp1, double* d_kp2, hipStream_t s) {
+                       double* d_kp1, double* d_kp2, hipStream_t s, int* d_info) {
     DFVO_ARG_CHECK(0 <= y0 && y0 < y1 && y1 <= H && 0 <= x0 && x0 < x1 && x1 <= W, "sampled_kp: crop outside the image");
     if (n <= 0) return DFVO_OK;
-    hipLaunchKernelGGL(k_kp_sampled, dim3(cdiv(n, 256)), dim3(256), 0, s, d_flow, H, W, y0, x0, x1 - x0, d_idx, n, d_kp1, d_kp2);
+    hipLaunchKernelGGL(k_kp_sampled, dim3(cdiv(n, 256)), dim3(256), 0, s, d_flow, H, W, y0, x0, x1 - x0, d_idx, n, d_kp1, d_kp2,
+                       d_info);
     DFVO_HIP_CHECK(hipGetLastError());
     return DFVO_OK;
+}
+
+// numpy's linspace: arange(n) * (stop / (n - 1)), the last element set to stop, then truncated (all values are >= 0)
+void generate_kp_samples(int y0, int y1, int x0, int x1, int n, int* h_idx) {
+    const double stop = (double)((long long)(x1 - x0) * (y1 - y0) - 1);
+    const double step = n > 1 ? stop / (double)(n - 1) : 0.0;
+    for (int i = 0; i < n; ++i) h_idx[i] = (int)((double)i * step);
+    if (n > 1) h_idx[n - 1] = (int)stop;
 }
 
 // score_method 'flow_ratio' (kp_selection.py:137-141,155): mask and score are flow_diff / |flow| per pixel, float32 as numpy

@@ -194,9 +194,13 @@ struct BestNBuffers {
     double* kp = nullptr;        // [kp1 | kp2], N x 2 doubles each
     size_t cap = 0;
     int kp_cap = 0;
+    int ensure(size_t px, int N);  // allocates (hipMalloc / hipFree: not for a per-pair path once the sizes are final)
     void release();
 };
-int enqueue_bestn_flow_kp(BestNBuffers& bb, const float* d_flow, const float* d_diff, int H, int W, int N, hipStream_t s);
+// d_kp1 / d_kp2 / d_info (all three or none): the picks go straight to these [N][2] arrays instead of bb.kp, and d_info
+// receives a tracker's kp_info triple [n, good_kp_found, 0] (n = 0 and good_kp_found = 0 where numpy would raise)
+int enqueue_bestn_flow_kp(BestNBuffers& bb, const float* d_flow, const float* d_diff, int H, int W, int N, hipStream_t s,
+                          double* d_kp1 = nullptr, double* d_kp2 = nullptr, int* d_info = nullptr);
 
 // rigid-flow keypoints (E_tracker.py:645-705 kp_selection_good_depth)
 struct RigidKpConfig {
@@ -217,8 +221,11 @@ struct RigidKpBuffers {
 };
 int enqueue_rigid_flow_kp(RigidKpBuffers& rb, const float* d_flow, const float* d_odiff, const float* d_depth32, int H,
                           int W, const RigidKpConfig& cfg, const float* d_rdiff_override, hipStream_t s);
+// d_info (optional): receives a tracker's kp_info triple [n, 1, 0] (keypoint_sampler.py:96: good_kp_found stays True)
 int enqueue_kp_sampled(const float* d_flow, int H, int W, int y0, int y1, int x0, int x1, const int* d_idx, int n,
-                       double* d_kp1, double* d_kp2, hipStream_t s);
+                       double* d_kp1, double* d_kp2, hipStream_t s, int* d_info = nullptr);
+// generate_kp_samples (keypoint_sampler.py:52-74): np.linspace(0, (y1 - y0) * (x1 - x0) - 1, n, dtype=int) into h_idx[n]
+void generate_kp_samples(int y0, int y1, int x0, int x1, int n, int* h_idx);
 int enqueue_mt_seed(TrackerBuffers& tb, uint32_t seed, hipStream_t s);
 // d_T21 (optional): 16 doubles that receive the inverse of the accepted pose (input of the scale stage)
 int enqueue_compute_pose_2d2d(TrackerBuffers& tb, int n_host, const PoseConfig& cfg, hipStream_t s,

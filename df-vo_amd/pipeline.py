@@ -1,6 +1,8 @@
 """Host driver of the fused per-pair pipeline (dfvo_pipeline_*): configuration marshalling, the
 double-buffered net/solver software pipeline, and pose accumulation as in
-/root/reference/libs/dfvo.py:109-119 (update_global_pose) and :121-262 (tracking, hybrid path)."""
+the reference's libs/dfvo.py:109-119 (update_global_pose) and :121-262 (tracking: the hybrid path of
+default_configuration.yml, and through the option keys below the keypoint sources, validity / scale methods and the
+PnP-only tracking of the shipped ablation files; options_from_cfg maps the reference's configuration object to them)."""
 import ctypes as C
 
 import numpy as np
@@ -16,13 +18,133 @@ DEFAULTS = dict(  # options/examples/default_configuration.yml
 
 STATUS = {0: "E", 1: "constant_motion", 2: "needs_pnp", 3: "PnP"}
 
+# dfvo_pipeline_set_options: the tracking configurations beyond default_configuration.yml.  Every key defaults to that
+# configuration; the values are the reference's own spellings (options/examples/ablation_*.yml)
+OPTION_DEFAULTS = dict(kp_source="local_bestN", kp_score_method="flow", kp_sampled_num=2000, flow_crop=((0.0, 1.0), (0.0, 1.0)),
+                       validity="GRIC", validity_thre=None, scale_method="depth_ratio", tracking_method="hybrid")
+_KP_SOURCE = {"local_bestN": 0, "bestN": 1, "sampled": 2}
+_KP_SCORE = {"flow": 0, "flow_ratio": 1}
+_VALIDITY = {"GRIC": 0, "flow": 1, "homo_ratio": 2}
+_SCALE_METHOD = {"depth_ratio": 0, "abs_diff": 1}
+_TRACKING = {"hybrid": 0, "PnP": 1}
+
+
+def _choice(o, key, table):
+    v = o[key]
+    if v not in table:
+        raise ValueError("%s = %r: one of %s" % (key, v, ", ".join(repr(k) for k in table)))
+    return table[v]
+
+
+def check_options(o):
+    """the option keys of `o` (OPTION_DEFAULTS filled in) as the fields of capi.PipelineOpts; ValueError on a bad value"""
+    f = dict(kp_source=_choice(o, "kp_source", _KP_SOURCE), kp_score_method=_choice(o, "kp_score_method", _KP_SCORE),
+             validity_method=_choice(o, "validity", _VALIDITY), scale_method=_choice(o, "scale_method", _SCALE_METHOD),
+             tracking_method=_choice(o, "tracking_method", _TRACKING))
+    num = o["kp_sampled_num"]
+    if isinstance(num, bool) or int(num) != num or num < 1:
+        raise ValueError("kp_sampled_num = %r: a positive integer" % (num,))
+    f["kp_sampled_num"] = int(num)
+    try:
+        (y0, y1), (x0, x1) = o["flow_crop"]
+        crop = [float(v) for v in (y0, y1, x0, x1)]
+    except (TypeError, ValueError):
+        raise ValueError("flow_crop = %r: [[y0, y1], [x0, x1]] fractions" % (o["flow_crop"],))
+    if not (0.0 <= crop[0] < crop[1] <= 1.0 and 0.0 <= crop[2] < crop[3] <= 1.0):
+        raise ValueError("flow_crop = %r: 0 <= y0 < y1 <= 1 and 0 <= x0 < x1 <= 1" % (o["flow_crop"],))
+    f["flow_crop"] = crop
+    thre = o["validity_thre"]
+    if o["validity"] == "GRIC":
+        thre = 0.0  # (unused: E_tracker.py:196-205)
+    elif thre is None or isinstance(thre, bool) or not np.isfinite(float(thre)):
+        raise ValueError("validity_thre = %r: validity %r needs a finite threshold" % (thre, o["validity"]))
+    f["validity_thre"] = float(thre)
+    return f
+
+
+def options_from_cfg(cfg):
+    """The reference's configuration object (default_cfg.Cfg / EasyDict of options/examples/*.yml) as the override dict of
+    TrackingPipeline -- only the keys that differ from DEFAULTS / OPTION_DEFAULTS, so default_configuration.yml maps to {}.
+    NotImplementedError, naming the key, for what the fused pipeline does not run."""
+    def get(path, default=None):
+        node = cfg
+        for k in path.split("."):
+            if node is None or k not in node:
+                return default
+            node = node[k]
+        return node
+
+    for path in ("e_tracker.iterative_kp.enable", "scale_recovery.iterative_kp.enable", "pnp_tracker.iterative_kp.enable",
+                 "kp_selection.rigid_flow_kp.enable", "kp_selection.depth_consistency.enable", "deep_pose.enable",
+                 "online_finetune.enable"):
+        if get(path, False):
+            raise NotImplementedError("%s: not run by the fused pipeline" % path)
+    if get("scale_recovery.method", "simple") != "simple":
+        raise NotImplementedError("scale_recovery.method: %s: not run by the fused pipeline" % get("scale_recovery.method"))
+    srcs = {k: get(k + ".kp_src", "kp_best") for k in ("e_tracker", "scale_recovery", "pnp_tracker")}
+    for k, v in srcs.items():
+        if v == "kp_depth":
+            raise NotImplementedError("%s.kp_src: kp_depth: not run by the fused pipeline" % k)
+        if v not in ("kp_best", "kp_list"):
+            raise NotImplementedError("%s.kp_src: %s: unknown keypoint source" % (k, v))
+    if len(set(srcs.values())) != 1:
+        raise NotImplementedError("kp_src: %s disagree; the fused pipeline tracks one keypoint set" % ", ".join(
+            "%s.kp_src = %s" % kv for kv in sorted(srcs.items())))
+    src = srcs["e_tracker"]
+    if src == "kp_best":  # keypoint_sampler.py:108-129: local_bestN, else bestN
+        if get("kp_selection.local_bestN.enable", False):
+            source = "local_bestN"
+        elif get("kp_selection.bestN.enable", False):
+            source = "bestN"
+        else:
+            raise NotImplementedError("kp_src: kp_best, but neither kp_selection.local_bestN nor kp_selection.bestN is enabled")
+    else:
+        if not get("kp_selection.sampled_kp.enable", False):
+            raise NotImplementedError("kp_src: kp_list, but kp_selection.sampled_kp is not enabled")
+        source = "sampled"
+    full = dict(kp_source=source, tracking_method=get("tracking_method", "hybrid"),
+                validity=get("e_tracker.validity.method", "GRIC"),
+                scale_method=get("scale_recovery.ransac.method", "depth_ratio"),
+                seed=get("seed", 4869), min_depth=get("depth.min_depth", 0.0), max_depth=get("depth.max_depth", 50.0),
+                e_reproj_thre=get("e_tracker.ransac.reproj_thre", 0.2), e_repeat=get("e_tracker.ransac.repeat", 5),
+                scale_min_samples=get("scale_recovery.ransac.min_samples", 3),
+                scale_max_trials=get("scale_recovery.ransac.max_trials", 100),
+                scale_stop_prob=get("scale_recovery.ransac.stop_prob", 0.99), scale_thre=get("scale_recovery.ransac.thre", 0.1),
+                pnp_repeat=get("pnp_tracker.ransac.repeat", 5), pnp_iters=get("pnp_tracker.ransac.iter", 100),
+                pnp_reproj_thre=get("pnp_tracker.ransac.reproj_thre", 1.0))
+    crop = get("crop.depth_crop")
+    if crop is not None:
+        full["depth_crop"] = tuple(tuple(float(v) for v in r) for r in crop)
+    if full["validity"] != "GRIC":
+        full["validity_thre"] = get("e_tracker.validity.thre")
+    if source == "local_bestN":
+        full.update(kp_num_bestN=get("kp_selection.local_bestN.num_bestN", 2000), kp_num_row=get("kp_selection.local_bestN.num_row", 10),
+                    kp_num_col=get("kp_selection.local_bestN.num_col", 10), kp_thre=get("kp_selection.local_bestN.thre", 0.1),
+                    kp_score_method=get("kp_selection.local_bestN.score_method", "flow"))
+    elif source == "bestN":
+        full["kp_num_bestN"] = get("kp_selection.bestN.num_bestN", 2000)
+    else:
+        full["kp_sampled_num"] = get("kp_selection.sampled_kp.num_kp", 2000)
+        fc = get("crop.flow_crop")
+        if fc is not None:
+            full["flow_crop"] = tuple(tuple(float(v) for v in r) for r in fc)
+    base = dict(DEFAULTS)
+    base.update(OPTION_DEFAULTS)
+    out = {k: v for k, v in full.items() if base.get(k) != v}
+    check = dict(OPTION_DEFAULTS)
+    check.update({k: v for k, v in out.items() if k in OPTION_DEFAULTS})
+    check_options(check)
+    return out
+
 
 class TrackingPipeline:
     def __init__(self, img_h, img_w, feed_h, feed_w, K, flow_sd, depth_sd, **overrides):
+        o = dict(DEFAULTS)
+        o.update(OPTION_DEFAULTS)
+        o.update(overrides)
+        fields = check_options(o)  # (before anything touches the device: a bad value is a ValueError)
         capi.require_gpu()
         self.lib = capi.lib()
-        o = dict(DEFAULTS)
-        o.update(overrides)
         self.opts = o
         self.H, self.W, self.feed_h, self.feed_w = img_h, img_w, feed_h, feed_w
         K = np.asarray(K, np.float64)
@@ -47,6 +169,18 @@ class TrackingPipeline:
         h = C.c_void_p()
         capi.check(self.lib.dfvo_pipeline_create(C.byref(cfg), C.byref(h)))
         self.h = h
+        if any(o[k] != v for k, v in OPTION_DEFAULTS.items()):
+            crop = fields.pop("flow_crop")
+            po = capi.PipelineOpts(**fields)
+            for i, v in enumerate(crop):
+                po.flow_crop[i] = v
+            try:
+                capi.check(self.lib.dfvo_pipeline_set_options(h, C.byref(po)))
+            except capi.DfvoError:
+                self.close()
+                raise
+        # keypoints a pair can have (get_keypoints' default capacity)
+        self.kp_max = {"local_bestN": o["kp_num_bestN"], "bestN": o["kp_num_bestN"], "sampled": o["kp_sampled_num"]}[o["kp_source"]]
         nh, nw = self._net_size(img_h, img_w)
         params = {k: (v.detach().cpu().float().numpy() if hasattr(v, "detach") else np.asarray(v, np.float32))
                   for k, v in flow_sd.items()}
@@ -58,6 +192,13 @@ class TrackingPipeline:
                    if hasattr(v, "detach") and v.dim() > 0 and "num_batches_tracked" not in k}
         capi.set_params(self.lib.dfvo_pipeline_set_depth_param, h, dparams)
         capi.check(self.lib.dfvo_pipeline_finalize(h))
+
+    @classmethod
+    def from_cfg(cls, cfg, K, flow_sd, depth_sd, feed_h, feed_w, **overrides):
+        """a pipeline for the reference's configuration object `cfg` (image size from cfg.image); `overrides` win"""
+        o = options_from_cfg(cfg)
+        o.update(overrides)
+        return cls(int(cfg["image"]["height"]), int(cfg["image"]["width"]), feed_h, feed_w, K, flow_sd, depth_sd, **o)
 
     @staticmethod
     def _net_size(h, w):
@@ -144,8 +285,10 @@ class TrackingPipeline:
                                                    capi.as_ptr(raw), capi.as_ptr(dep)))
         return fwd, bwd, diff, raw, dep
 
-    def get_keypoints(self, slot, cap=4096):
-        """kp_best of the reference / current frame [n,2] f64 and the E-tracker's inlier mask [n] bool for `slot`"""
+    def get_keypoints(self, slot, cap=None):
+        """the tracked keypoints of the reference / current frame [n,2] f64 and the E-tracker's inlier mask [n] bool for `slot`"""
+        if cap is None:
+            cap = max(4096, int(self.kp_max))
         kr = np.zeros((cap, 2))
         kc = np.zeros((cap, 2))
         inl = np.zeros(cap, np.uint8)

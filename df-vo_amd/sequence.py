@@ -4,7 +4,9 @@ for one contiguous chunk of a sequence, and the frame-batch data-parallel wrappe
 Pair j = (frame j, frame j+1).  A chunk [lo, hi) of pairs needs frames lo .. hi: frame lo is the chunk's 1-frame halo
 (its depth is the PnP fallback's reference depth for pair lo; the reference computes it when frame lo is `cur`, here it
 is recomputed by the rank that owns the chunk -- no activation exchange between ranks).  The nets run `ahead` pairs
-ahead of the solver stage; nothing but the relative poses leaves the device.
+ahead of the solver stage; nothing but the relative poses leaves the device.  The driver reads nothing but the status word
+and the pose of a pair, so it runs a pipeline of any tracking configuration (pipeline.TrackingPipeline's kp_source / validity /
+scale_method / tracking_method keys, TrackingPipeline.from_cfg): with tracking_method "PnP" every row has status 3.
 
 RandomState modes (SURVEY hard part 2):
   "sequential"  one stream seeded once (np.random.seed(cfg.seed), run.py:81-84) and carried from pair to pair -- the

@@ -488,6 +488,37 @@ int dfvo_pipeline_set_flow_param(dfvo_pipeline* p, const char* name, const float
 int dfvo_pipeline_set_depth_param(dfvo_pipeline* p, const char* name, const float* h_data, int ndim, const int* shape);
 int dfvo_pipeline_finalize(dfvo_pipeline* p);
 int dfvo_pipeline_seed(dfvo_pipeline* p, uint32_t seed);
+/* The tracking configurations beyond default_configuration.yml (ablation_correspondences_best_n.yml, _uniform.yml,
+ * ablation_model_sel_flow.yml, ablation_tracker_pnp.yml and the unshipped branches flow_ratio / homo_ratio / abs_diff).
+ * All zero = the default configuration; a pipeline on which dfvo_pipeline_set_options is never called runs exactly that.
+ * Legal after dfvo_pipeline_create and before the first dfvo_pipeline_enqueue_nets / _set_ref_depth / _set_ref_image; it
+ * allocates every buffer the chosen keypoint source needs.  kp_source:
+ *   LOCAL_BESTN  kp_selection.py:74-200, the grid of dfvo_pipeline_cfg (kp_num_row x kp_num_col, kp_num_bestN, kp_thre)
+ *   BESTN        kp_selection.py:33-71: the kp_num_bestN most consistent pixels of the whole image, in np.argpartition's
+ *                order.  An image with kp_num_bestN or fewer non-NaN pixels (numpy raises there) reports no good keypoints.
+ *   SAMPLED      kp_selection.py:327-378 at the kp_sampled_num indices of keypoint_sampler.py:52-74 over flow_crop
+ * good_kp_found is always 1 for BESTN / SAMPLED (keypoint_sampler.py:96).
+ * tracking_method PNP (dfvo.py:165,225: no E-tracker, PnP on every pair): dfvo_pipeline_track_begin enqueues the keypoint
+ * stage and the PnP chain, dfvo_pipeline_track_end only waits for it; status DFVO_TRACK_PNP, or DFVO_TRACK_NEEDS_PNP while
+ * no reference depth is known; the inlier mask of dfvo_pipeline_get_keypoints is all ones. */
+#define DFVO_KP_SOURCE_LOCAL_BESTN 0
+#define DFVO_KP_SOURCE_BESTN 1
+#define DFVO_KP_SOURCE_SAMPLED 2
+#define DFVO_SCALE_DEPTH_RATIO 0
+#define DFVO_SCALE_ABS_DIFF 1
+#define DFVO_TRACKING_HYBRID 0
+#define DFVO_TRACKING_PNP 1
+typedef struct dfvo_pipeline_opts {
+    int kp_source;        /* DFVO_KP_SOURCE_* */
+    int kp_score_method;  /* local_bestN only: DFVO_KP_SCORE_FLOW | DFVO_KP_SCORE_FLOW_RATIO */
+    int kp_sampled_num;   /* sampled: cfg.kp_selection.sampled_kp.num_kp */
+    double flow_crop[4];  /* sampled: y0 y1 x0 x1 fractions (cfg.crop.flow_crop) */
+    int validity_method;  /* DFVO_VALIDITY_GRIC | _FLOW | _HOMO_RATIO */
+    double validity_thre; /* e_tracker.validity.thre (unused under GRIC) */
+    int scale_method;     /* DFVO_SCALE_DEPTH_RATIO | DFVO_SCALE_ABS_DIFF (scale_recovery.ransac.method) */
+    int tracking_method;  /* DFVO_TRACKING_HYBRID | DFVO_TRACKING_PNP */
+} dfvo_pipeline_opts;
+int dfvo_pipeline_set_options(dfvo_pipeline* p, const dfvo_pipeline_opts* opts);
 int dfvo_pipeline_set_graph(dfvo_pipeline* p, int enable);   /* hipGraph replay of the nets (default on) */
 /* number of output slots: the host may run the nets this many pairs ahead of the solver stage (the nets of pairs
  * k+1 .. k+3 queue up behind each other on their streams while dfvo_pipeline_track(k) blocks the host) */
