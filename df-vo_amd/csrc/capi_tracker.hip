@@ -67,9 +67,8 @@ int dfvo_tracker_create(void* stream, dfvo_tracker** out) {
         }
         t->own_stream = true;
     }
-    if (hipMalloc((void**)&t->d_small, 64 * sizeof(double)) != hipSuccess || t->tb.init() != DFVO_OK) {
-        delete t;
-        dfvo::set_last_error("hipMalloc failed");
+    if (t->d_small.alloc(64) != DFVO_OK || t->tb.init() != DFVO_OK) {
+        dfvo_tracker_destroy(t);
         return DFVO_ERR_HIP;
     }
     enqueue_mt_seed(t->tb, 5489u, t->stream);
@@ -114,16 +113,22 @@ void dfvo_tracker_destroy(dfvo_tracker* t) {
     t->pnp.release();
     t->rigid.release();
     t->bestn.release();
-    if (t->d_flow) (void)hipFree(t->d_flow);
-    if (t->d_diff) (void)hipFree(t->d_diff);
-    if (t->d_depth) (void)hipFree(t->d_depth);
-    if (t->d_small) (void)hipFree(t->d_small);
-    if (t->d_x1) (void)hipFree(t->d_x1);
-    if (t->d_x2) (void)hipFree(t->d_x2);
-    if (t->d_X4) (void)hipFree(t->d_X4);
     if (t->own_stream && t->stream) (void)hipStreamDestroy(t->stream);
-    delete t;
+    delete t;  // (the staging arrays and the buffer sets' memory are DevArr members)
 }
+
+// the staging buffers of the host-array entry points: d_flow / d_diff for `px` pixels, d_depth for `px` doubles.  Freed
+// first, allocated then; a failed call leaves them empty
+static int stage_flow(dfvo_tracker* t, size_t px) {
+    if (px <= t->d_diff.n) return DFVO_OK;
+    t->d_diff.release();
+    if (t->d_flow.alloc(2 * px) || t->d_diff.alloc(px)) {
+        t->d_flow.release();
+        return DFVO_ERR_HIP;
+    }
+    return DFVO_OK;
+}
+static int stage_depth(dfvo_tracker* t, size_t px) { return t->d_depth.grow(px); }
 
 static int stage_points(dfvo_tracker* t, const double* h1, const double* h2, int n, int iters) {
     int rc = t->ws.ensure(n > 8 ? n : 8, iters);
@@ -194,15 +199,7 @@ int dfvo_triangulate_points(dfvo_tracker* t, const double* h_P1, const double* h
                             const double* h_x2, int n, double* h_X4) {
     DFVO_ARG_CHECK(t && h_P1 && h_P2 && h_x1 && h_x2 && h_X4 && n >= 0, "dfvo_triangulate_points: bad argument");
     if (n == 0) return DFVO_OK;
-    if (n > t->tri_cap) {
-        if (t->d_x1) (void)hipFree(t->d_x1);
-        if (t->d_x2) (void)hipFree(t->d_x2);
-        if (t->d_X4) (void)hipFree(t->d_X4);
-        t->tri_cap = n;
-        DFVO_HIP_CHECK(hipMalloc((void**)&t->d_x1, sizeof(double) * 2 * n));
-        DFVO_HIP_CHECK(hipMalloc((void**)&t->d_x2, sizeof(double) * 2 * n));
-        DFVO_HIP_CHECK(hipMalloc((void**)&t->d_X4, sizeof(double) * 4 * n));
-    }
+    if (t->d_x1.grow((size_t)2 * n) || t->d_x2.grow((size_t)2 * n) || t->d_X4.grow((size_t)4 * n)) return DFVO_ERR_HIP;
     double P[24];
     for (int i = 0; i < 12; i++) {
         P[i] = h_P1[i];
@@ -254,13 +251,7 @@ int dfvo_kp_local_bestn_ex(dfvo_tracker* t, const float* h_flow, const float* h_
     DFVO_ARG_CHECK(score_method == DFVO_KP_SCORE_FLOW || score_method == DFVO_KP_SCORE_FLOW_RATIO,
                    "dfvo_kp_local_bestn_ex: score_method must be DFVO_KP_SCORE_FLOW or DFVO_KP_SCORE_FLOW_RATIO");
     const size_t px = (size_t)H * W;
-    if (px > t->flow_cap) {
-        if (t->d_flow) (void)hipFree(t->d_flow);
-        if (t->d_diff) (void)hipFree(t->d_diff);
-        t->flow_cap = px;
-        DFVO_HIP_CHECK(hipMalloc((void**)&t->d_flow, sizeof(float) * 2 * px));
-        DFVO_HIP_CHECK(hipMalloc((void**)&t->d_diff, sizeof(float) * px));
-    }
+    if (int rc_f = stage_flow(t, px)) return rc_f;
     DFVO_HIP_CHECK(hipMemcpyAsync(t->d_flow, h_flow, sizeof(float) * 2 * px, hipMemcpyHostToDevice, t->stream));
     DFVO_HIP_CHECK(hipMemcpyAsync(t->d_diff, h_diff, sizeof(float) * px, hipMemcpyHostToDevice, t->stream));
     int rc = enqueue_local_bestn(t->tb, t->d_flow, t->d_diff, H, W, num_row, num_col, num_bestN, thre, t->stream, score_method);
@@ -282,13 +273,7 @@ int dfvo_kp_bestn(dfvo_tracker* t, const float* h_flow, const float* h_diff, int
     DFVO_ARG_CHECK(t && h_flow && h_diff && h_kp1 && h_kp2 && n_out && H > 0 && W > 0 && num_bestN >= 1,
                    "dfvo_kp_bestn: bad argument");
     const size_t px = (size_t)H * W;
-    if (px > t->flow_cap) {
-        if (t->d_flow) (void)hipFree(t->d_flow);
-        if (t->d_diff) (void)hipFree(t->d_diff);
-        t->flow_cap = px;
-        DFVO_HIP_CHECK(hipMalloc((void**)&t->d_flow, sizeof(float) * 2 * px));
-        DFVO_HIP_CHECK(hipMalloc((void**)&t->d_diff, sizeof(float) * px));
-    }
+    if (int rc_f = stage_flow(t, px)) return rc_f;
     DFVO_HIP_CHECK(hipMemcpyAsync(t->d_flow, h_flow, sizeof(float) * 2 * px, hipMemcpyHostToDevice, t->stream));
     DFVO_HIP_CHECK(hipMemcpyAsync(t->d_diff, h_diff, sizeof(float) * px, hipMemcpyHostToDevice, t->stream));
     int rc = enqueue_bestn_flow_kp(t->bestn, t->d_flow, t->d_diff, H, W, num_bestN, t->stream);
@@ -310,22 +295,11 @@ int dfvo_kp_sampled(dfvo_tracker* t, const float* h_flow, int H, int W, int y0, 
     const long long cells = (long long)(y1 - y0) * (x1 - x0);
     for (int i = 0; i < n; ++i) DFVO_ARG_CHECK(h_idx[i] >= 0 && h_idx[i] < cells, "dfvo_kp_sampled: index outside the cropped grid");
     const size_t px = (size_t)H * W;
-    if (px > t->flow_cap) {
-        if (t->d_flow) (void)hipFree(t->d_flow);
-        if (t->d_diff) (void)hipFree(t->d_diff);
-        t->flow_cap = px;
-        DFVO_HIP_CHECK(hipMalloc((void**)&t->d_flow, sizeof(float) * 2 * px));
-        DFVO_HIP_CHECK(hipMalloc((void**)&t->d_diff, sizeof(float) * px));
-    }
+    if (int rc_f = stage_flow(t, px)) return rc_f;
     if (n == 0) return DFVO_OK;
-    int* d_idx = nullptr;
-    double* d_kp = nullptr;
-    DFVO_HIP_CHECK(hipMalloc((void**)&d_idx, sizeof(int) * n));
-    if (hipMalloc((void**)&d_kp, sizeof(double) * 4 * n) != hipSuccess) {
-        (void)hipFree(d_idx);
-        set_last_error("dfvo_kp_sampled: hipMalloc failed");
-        return DFVO_ERR_HIP;
-    }
+    DevArr<int> d_idx;
+    DevArr<double> d_kp;
+    if (d_idx.alloc(n) || d_kp.alloc((size_t)4 * n)) return DFVO_ERR_HIP;
     hipError_t e = hipMemcpyAsync(t->d_flow, h_flow, sizeof(float) * 2 * px, hipMemcpyHostToDevice, t->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_idx, h_idx, sizeof(int) * n, hipMemcpyHostToDevice, t->stream);
     int rc = e == hipSuccess ? enqueue_kp_sampled(t->d_flow, H, W, y0, y1, x0, x1, d_idx, n, d_kp, d_kp + 2 * n, t->stream)
@@ -339,9 +313,7 @@ int dfvo_kp_sampled(dfvo_tracker* t, const float* h_flow, int H, int W, int y0, 
             rc = DFVO_ERR_HIP;
         }
     }
-    (void)hipStreamSynchronize(t->stream);
-    (void)hipFree(d_idx);
-    (void)hipFree(d_kp);
+    (void)hipStreamSynchronize(t->stream);  // before d_idx / d_kp go
     return rc;
 }
 
@@ -354,13 +326,7 @@ int dfvo_kp_rigid_flow(dfvo_tracker* t, const float* h_flow, const float* h_flow
                    "dfvo_kp_rigid_flow: bad argument");
     DFVO_ARG_CHECK(cfg->score_method == 0 || cfg->score_method == 1, "dfvo_kp_rigid_flow: score_method");
     const size_t px = (size_t)H * W;
-    if (px > t->flow_cap) {
-        if (t->d_flow) (void)hipFree(t->d_flow);
-        if (t->d_diff) (void)hipFree(t->d_diff);
-        t->flow_cap = px;
-        DFVO_HIP_CHECK(hipMalloc((void**)&t->d_flow, sizeof(float) * 2 * px));
-        DFVO_HIP_CHECK(hipMalloc((void**)&t->d_diff, sizeof(float) * px));
-    }
+    if (int rc_f = stage_flow(t, px)) return rc_f;
     RigidKpConfig rc;
     rc.num_row = cfg->num_row;
     rc.num_col = cfg->num_col;
@@ -448,11 +414,7 @@ static int find_scale_impl(dfvo_tracker* t, const double* h_kp1, const double* h
     if (h_rng625)
         DFVO_HIP_CHECK(hipMemcpyAsync(t->tb.mt_state, h_rng625, 625 * sizeof(uint32_t), hipMemcpyHostToDevice, t->stream));
     const size_t px = per_kp ? (size_t)(n > 0 ? n : 1) : (size_t)H * W;
-    if (px > t->depth_cap) {
-        if (t->d_depth) (void)hipFree(t->d_depth);
-        t->depth_cap = px;
-        DFVO_HIP_CHECK(hipMalloc((void**)&t->d_depth, sizeof(double) * px));
-    }
+    if (int rc_d = stage_depth(t, px)) return rc_d;
     if (!(per_kp && n == 0))  // (a zero-length per-keypoint array has no element to read)
         DFVO_HIP_CHECK(hipMemcpyAsync(t->d_depth, h_depth, sizeof(double) * px, hipMemcpyHostToDevice, t->stream));
     DFVO_HIP_CHECK(hipMemcpyAsync(t->d_small, h_T21, 16 * sizeof(double), hipMemcpyHostToDevice, t->stream));
@@ -538,11 +500,7 @@ static int pose_3d2d_impl(dfvo_tracker* t, const double* h_kp1, const double* h_
     if (h_rng625)
         DFVO_HIP_CHECK(hipMemcpyAsync(t->tb.mt_state, h_rng625, 625 * sizeof(uint32_t), hipMemcpyHostToDevice, t->stream));
     const size_t px = per_kp ? (size_t)(n > 0 ? n : 1) : (size_t)H * W;
-    if (px > t->depth_cap) {
-        if (t->d_depth) (void)hipFree(t->d_depth);
-        t->depth_cap = px;
-        DFVO_HIP_CHECK(hipMalloc((void**)&t->d_depth, sizeof(double) * px));
-    }
+    if (int rc_d = stage_depth(t, px)) return rc_d;
     if (!(per_kp && n == 0))  // (a zero-length per-keypoint array has no element to read)
         DFVO_HIP_CHECK(hipMemcpyAsync(t->d_depth, h_depth, sizeof(double) * px, hipMemcpyHostToDevice, t->stream));
     PnpConfig pc;
@@ -594,12 +552,11 @@ int dfvo_compose_trajectory_device(const double* d_rows, int n, const double* d_
                                    void* stream) {
     DFVO_ARG_CHECK(n >= 0 && d_poses && h_bad_row, "dfvo_compose_trajectory_device: bad argument");
     hipStream_t s = (hipStream_t)stream;
-    int* d_bad = nullptr;
-    DFVO_HIP_CHECK(hipMalloc((void**)&d_bad, sizeof(int)));
+    DevArr<int> d_bad;
+    if (int rc_b = d_bad.alloc(1)) return rc_b;
     int rc = enqueue_compose_trajectory(d_rows, n, d_first, d_poses, d_bad, s);
     hipError_t e = hipStreamSynchronize(s);
     if (rc == DFVO_OK && e == hipSuccess) e = hipMemcpy(h_bad_row, d_bad, sizeof(int), hipMemcpyDeviceToHost);
-    (void)hipFree(d_bad);
     if (rc != DFVO_OK) return rc;
     DFVO_HIP_CHECK(e);
     return DFVO_OK;
@@ -608,17 +565,13 @@ int dfvo_compose_trajectory_device(const double* d_rows, int n, const double* d_
 // host arrays in and out
 int dfvo_compose_trajectory(const double* h_rows, int n, const double* h_first, double* h_poses, int* h_bad_row) {
     DFVO_ARG_CHECK(n >= 0 && h_poses && h_bad_row && (n == 0 || h_rows), "dfvo_compose_trajectory: bad argument");
-    double *d_rows = nullptr, *d_first = nullptr, *d_poses = nullptr;
-    DFVO_HIP_CHECK(hipMalloc((void**)&d_rows, sizeof(double) * 17 * (size_t)(n > 0 ? n : 1)));
-    DFVO_HIP_CHECK(hipMalloc((void**)&d_poses, sizeof(double) * 16 * (size_t)(n + 1)));
-    if (h_first) DFVO_HIP_CHECK(hipMalloc((void**)&d_first, sizeof(double) * 16));
+    DevArr<double> d_rows, d_first, d_poses;
+    if (d_rows.alloc(17 * (size_t)(n > 0 ? n : 1)) || d_poses.alloc(16 * (size_t)(n + 1)) || (h_first && d_first.alloc(16)))
+        return DFVO_ERR_HIP;
     hipError_t e = n ? hipMemcpy(d_rows, h_rows, sizeof(double) * 17 * (size_t)n, hipMemcpyHostToDevice) : hipSuccess;
     if (e == hipSuccess && h_first) e = hipMemcpy(d_first, h_first, sizeof(double) * 16, hipMemcpyHostToDevice);
     int rc = e == hipSuccess ? dfvo_compose_trajectory_device(d_rows, n, d_first, d_poses, h_bad_row, nullptr) : DFVO_ERR_HIP;
     if (rc == DFVO_OK) e = hipMemcpy(h_poses, d_poses, sizeof(double) * 16 * (size_t)(n + 1), hipMemcpyDeviceToHost);
-    (void)hipFree(d_rows);
-    (void)hipFree(d_poses);
-    if (d_first) (void)hipFree(d_first);
     if (rc != DFVO_OK) return rc;
     DFVO_HIP_CHECK(e);
     return DFVO_OK;

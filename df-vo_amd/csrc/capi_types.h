@@ -23,12 +23,11 @@ struct dfvo_tracker {
     dfvo::RigidKpBuffers rigid;
     dfvo::BestNBuffers bestn;
     dfvo::RansacWorkspace& ws = tb.ws_e;
-    float *d_flow = nullptr, *d_diff = nullptr;
-    double* d_depth = nullptr;
-    size_t flow_cap = 0, depth_cap = 0;
-    double* d_small = nullptr;  // 64 doubles
-    double *d_x1 = nullptr, *d_x2 = nullptr, *d_X4 = nullptr;
-    int tri_cap = 0;
+    // staging of the host-array entry points, grown on demand (capi_tracker.hip: stage_flow, stage_depth)
+    dfvo::DevArr<float> d_flow, d_diff;  // [2][px], [px]
+    dfvo::DevArr<double> d_depth;
+    dfvo::DevArr<double> d_small;        // 64 doubles
+    dfvo::DevArr<double> d_x1, d_x2, d_X4;
     dfvo::PnpBuffers pnp;
 };
 

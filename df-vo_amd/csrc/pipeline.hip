@@ -8,6 +8,7 @@
 #include "../../include/dfvo_hip.h"
 #include <algorithm>
 #include <chrono>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,6 +22,45 @@
 
 using namespace dfvo;
 
+// what the RandomState-ordered chain of a pair leaves in pinned host memory behind Slot::e_res
+struct ChainResult {
+    PoseState pose;
+    ScaleResult scale;
+    PnpResult pnp;  // tracking_method PnP
+};
+static_assert(offsetof(ChainResult, scale) == sizeof(PoseState) && offsetof(ChainResult, pnp) == sizeof(PoseState) + sizeof(ScaleResult) &&
+                  sizeof(ChainResult) == sizeof(PoseState) + sizeof(ScaleResult) + sizeof(PnpResult),
+              "ChainResult is the three results back to back");
+
+// a pair between dfvo_pipeline_track_begin and _end
+enum Begun {
+    IDLE,            // no chain pending
+    NO_KEYPOINTS,    // the pending pair had no good keypoints
+    NO_REF_DEPTH,    // PnP-only pair without a reference depth
+    CHAIN_ENQUEUED,  // Slot::n keypoints went into the chain
+};
+
+// what each of the pairs in flight has of its own
+struct Slot {
+    TrackerBuffers tb;   // [0] owns the numpy RandomState and the RNG-side events, the others share them
+    BestNBuffers bestn;  // kp_source bestN: the whole-image selection's workspace
+    hipEvent_t e_flow = nullptr, e_depth = nullptr;
+    // RNG-independent half of the solver stage (keypoint selection, homography chain) enqueued ahead of time
+    // (dfvo_pipeline_prefetch_track): completion event and pinned keypoint info [n, good_kp_found, regions, -]
+    hipEvent_t e_pre = nullptr;
+    PinnedArr<int> h_info;
+    bool prefetched = false;
+    // dfvo_pipeline_track_begin / _end
+    PinnedArr<ChainResult> h_res;
+    hipEvent_t e_res = nullptr;
+    Begun begun = IDLE;
+    int n = 0;
+    const double* depth_override = nullptr;
+    // outputs of the nets
+    DevArr<float> fwd, bwd, diff, raw_depth;
+    DevArr<double> proc_depth;
+};
+
 struct dfvo_pipeline {
     int H = 0, W = 0, feedH = 0, feedW = 0;
     FlowNet flow;
@@ -28,58 +68,45 @@ struct dfvo_pipeline {
     // over the instances, so the latency-bound coarse pyramid levels of one pass overlap the throughput-bound fine
     // levels of another (8.7 -> 7.1 ms per pair with two); costs one set of activations (~1.3 GB) per instance
     FlowNet flow_x[DFVO_PIPELINE_SLOTS - 1];
-    hipStream_t s_flow_x[DFVO_PIPELINE_SLOTS - 1] = {};
     int flow_instances = 1;
     DepthNet depth;
-    TrackerBuffers tbs[DFVO_PIPELINE_SLOTS];  // [0] owns the numpy RandomState and the RNG-side streams, the others share them
-    // RNG-independent half of the solver stage (keypoint selection, homography chain) enqueued ahead of time
-    // (dfvo_pipeline_prefetch_track): two streams used alternately, per-slot completion event and pinned keypoint info
-    hipStream_t s_pre[2] = {nullptr, nullptr};
-    hipEvent_t e_pre[DFVO_PIPELINE_SLOTS] = {};
-    hipEvent_t e_ref = nullptr;  // reference depth of the first frame written (dfvo_pipeline_set_ref_image / _set_ref_depth)
-    int* h_info[DFVO_PIPELINE_SLOTS] = {};
-    bool prefetched[DFVO_PIPELINE_SLOTS] = {};
-    // dfvo_pipeline_track_begin / _end: results of the RandomState-ordered chain land in pinned host memory behind e_res
-    void* h_res[DFVO_PIPELINE_SLOTS] = {};   // PoseState | ScaleResult | PnpResult (tracking_method PnP)
-    hipEvent_t e_res[DFVO_PIPELINE_SLOTS] = {};
-    // -1: no chain pending, -2: pending pair had no good keypoints, -3: PnP-only pair without a reference depth, else keypoint count
-    int begun_n[DFVO_PIPELINE_SLOTS] = {};
-    const double* begun_depth_override[DFVO_PIPELINE_SLOTS] = {};
+    Slot slots[DFVO_PIPELINE_SLOTS];
     int pending_slot = -1;  // the one pair begun and not yet collected (the chains consume ONE RandomState, in pair order)
-    hipStream_t s_flow = nullptr, s_depth = nullptr, s_trk = nullptr;
-    hipEvent_t e_flow[DFVO_PIPELINE_SLOTS] = {}, e_depth[DFVO_PIPELINE_SLOTS] = {};
+    hipEvent_t e_ref = nullptr;  // reference depth of the first frame written (dfvo_pipeline_set_ref_image / _set_ref_depth)
     // the roll-over copy ref_depth <- proc_depth[slot] (s_trk) has read its source / written its target: the depth stream's
-    // next writers of either wait for it on the device (recorded by roll_ref_depth; null until the first roll-over)
+    // next writers of either wait for it on the device (recorded by roll_ref_depth, waited for once roll_pending)
     hipEvent_t e_roll = nullptr;
     bool roll_pending = false;
-    // per-slot outputs of the nets
-    float *fwd[DFVO_PIPELINE_SLOTS] = {}, *bwd[DFVO_PIPELINE_SLOTS] = {}, *diff[DFVO_PIPELINE_SLOTS] = {};
-    float* raw_depth[DFVO_PIPELINE_SLOTS] = {};
-    double* proc_depth[DFVO_PIPELINE_SLOTS] = {};
-    float* depth_small = nullptr;
+    DevArr<float> depth_small;
     LanczosResizer feed_resize;  // current frame -> depth-net feed size (when the caller passes no resized frame)
-    uint8_t* feed_buf = nullptr;
-    double* d_T21 = nullptr;
+    DevArr<uint8_t> feed_buf;
+    DevArr<double> d_T21;
     // PnP fallback: processed depth of the reference frame (= the previous pair's current frame)
     PnpBuffers pnp;
-    double* ref_depth = nullptr;
-    float* ref_raw = nullptr;
+    DevArr<double> ref_depth;
+    DevArr<float> ref_raw;
     bool has_ref_depth = false;
     dfvo_pipeline_cfg cfg;
     // dfvo_pipeline_set_options: the tracking configuration beyond default_configuration.yml (all zero = that configuration)
     dfvo_pipeline_opts opts = {};
     bool started = false;                   // a pair or a reference depth was enqueued: the options are final
-    BestNBuffers bestn[DFVO_PIPELINE_SLOTS];  // kp_source bestN: the whole-image selection's workspace, per slot
-    int* d_samples = nullptr;               // kp_source sampled: generate_kp_samples' index list, uploaded once
+    DevArr<int> d_samples;                  // kp_source sampled: generate_kp_samples' index list, uploaded once
     int sample_crop[4] = {0, 0, 0, 0};      // y0 y1 x0 x1 [px] of cfg.crop.flow_crop
     bool nets_ready = false;
     const FlowNet* last_flow = nullptr;  // the instance that ran the previous pair (carry source of a d_ref == NULL call)
+    // Streams.  `owned` is every stream the pipeline created or took from the pool, destroyed once by dfvo_pipeline_destroy;
+    // the handles below it are the roles, plain copies.  s_pre: the two streams the run-ahead halves alternate on; s_rep: the
+    // chain's side streams, lent to slots[0].tb (null: that object created its own, the creation-order fallback).
     // Stream layout (stream_layout.h).  LAYOUT_LANES: lane[0 .. 3] are the pipeline's only streams, one per hardware queue,
-    // and every role's stream above is one of them (s_flow, s_flow_x[0], s_depth = s_pre[0] = s_pre[1], s_trk = both side
-    // streams of the chain); otherwise every role owns its stream and lane[] is null.
+    // and every role's stream is one of them (s_flow, s_flow_x[0], s_depth = s_pre[0] = s_pre[1], s_trk = s_rep[0] = s_rep[1]);
+    // otherwise every role has a stream to itself and lane[] is null.
+    std::vector<hipStream_t> owned;
+    hipStream_t s_flow = nullptr, s_depth = nullptr, s_trk = nullptr;
+    hipStream_t s_flow_x[DFVO_PIPELINE_SLOTS - 1] = {};
+    hipStream_t s_pre[2] = {nullptr, nullptr}, s_rep[2] = {nullptr, nullptr};
+    hipStream_t lane[4] = {nullptr, nullptr, nullptr, nullptr};
     StreamPlan plan;
     int pool_groups = 0, pool_queues = 0;  // what the pool measured (0: no measurement)
-    hipStream_t lane[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 #define P_TRY(expr)                     \
@@ -99,9 +126,22 @@ int dfvo_pipeline_create(const dfvo_pipeline_cfg* cfg, dfvo_pipeline** out) {
     p->feedH = cfg->feed_h;
     p->feedW = cfg->feed_w;
     auto fail = [&](int rc) {
-        delete p;
+        dfvo_pipeline_destroy(p);  // (tolerates a half-built pipeline)
         return rc;
     };
+    auto own = [&](hipStream_t s) {  // a stream taken from the pool
+        if (s) p->owned.push_back(s);
+        return s;
+    };
+    auto create_owned = [&](hipStream_t* s, bool solver) -> int {
+        DFVO_HIP_CHECK(solver ? create_solver_stream(s) : create_net_stream(s));
+        p->owned.push_back(*s);
+        return DFVO_OK;
+    };
+    // two LiteFlowNet instances on two pipes, alternating pairs (measured 1 / 2 / 3: 217 / 287 / 272 pairs/s, profiles/
+    // r3ag_flow_instances_ab.txt).  DFVO_FLOW_INSTANCES=1 is a test hook: the carry-over from a pass of the SAME instance
+    p->flow_instances = getenv("DFVO_FLOW_INSTANCES") && atoi(getenv("DFVO_FLOW_INSTANCES")) == 1 ? 1 : 2;
+    const bool fx = p->flow_instances > 1;
     // Streams by measurement (stream_pool.hip, stream_layout.h): twelve candidates, classified by dispatch pipe and by
     // hardware queue.  Eight or more queues: the wide layout, a stream per role -- pipe A / B: one flow-net instance each, pipe
     // C: the depth net + the two run-ahead homography chains, pipe D: the RandomState-ordered chain and its two side streams,
@@ -110,8 +150,8 @@ int dfvo_pipeline_create(const dfvo_pipeline_cfg* cfg, dfvo_pipeline** out) {
     // the lane layout takes one stream from each of four queues and puts the roles of a lane on that one stream (flow |
     // flow_x | depth + pre-parts | chain + side streams), so which roles share a queue is decided here and not by the runtime.
     // DFVO_STREAM_LAYOUT=auto|wide|lanes forces one (A/B runs, tests).  Falls back to creation order when the probe does
-    // not settle or finds too few groups / queues for the layout.
-    hipStream_t pool_rep[2] = {nullptr, nullptr}, pool_pre[2] = {nullptr, nullptr}, pool_fx = nullptr;
+    // not settle or finds too few groups / queues for the layout: the roles the pool did not fill stay null here and get
+    // streams created below, in the order the pair rate was measured with (TrackerBuffers::init).
     {
         int choice = LAYOUT_CHOICE_AUTO;
         if (const char* e = getenv("DFVO_STREAM_LAYOUT")) {
@@ -138,10 +178,12 @@ int dfvo_pipeline_create(const dfvo_pipeline_cfg* cfg, dfvo_pipeline** out) {
             c.nqueues = pool.nqueues;
             int pick[4];
             if (pick_lane_candidates(c, pick)) {
-                for (int l = 0; l < 4; ++l) p->lane[l] = pool.take_index(pick[l]);
-                p->s_trk = p->lane[plan.lane[ROLE_TRK]];
-                p->s_depth = p->lane[plan.lane[ROLE_DEPTH]];
-                p->s_flow = p->lane[plan.lane[ROLE_FLOW]];
+                for (int l = 0; l < 4; ++l) p->lane[l] = own(pool.take_index(pick[l]));
+                auto of = [&](int role) { return p->lane[plan.lane[role]]; };
+                p->s_trk = of(ROLE_TRK), p->s_rep[0] = of(ROLE_REP0), p->s_rep[1] = of(ROLE_REP1);
+                p->s_depth = of(ROLE_DEPTH), p->s_pre[0] = of(ROLE_PRE0), p->s_pre[1] = of(ROLE_PRE1);
+                p->s_flow = of(ROLE_FLOW);
+                if (fx) p->s_flow_x[0] = of(ROLE_FLOW_X);
                 p->plan = plan;
             }
         } else if (plan.layout == LAYOUT_WIDE) {
@@ -153,58 +195,42 @@ int dfvo_pipeline_create(const dfvo_pipeline_cfg* cfg, dfvo_pipeline** out) {
             // role -> pipe: trk rep0 rep1 | depth pre0 pre1 | flow | flow_x (plan.lane).  Other placements were measured
             // (profiles/r3k_layouts.txt): a run-ahead homography chain on a flow net's pipe 178-194 pairs/s against 266 -- its
             // long single-workgroup kernels hold up the dispatch of the flow net's hundred short launches per pass.
-            const int* rank = plan.lane;  // wide: per role, the rank (0 = largest) of the pipe group its stream comes from
+            // Per role, the pipe group its stream comes from: by the plan's rank (0 = largest), or, with two small groups,
+            // chain and depth roles on the two large ones
+            int from[ROLE_COUNT] = {g[0], g[0], g[0], g[1], g[1], g[1], g[2], g[3]};
             const bool full = pool.count(g[0]) >= 3 && pool.count(g[1]) >= 3 && pool.count(g[2]) >= 3 && pool.count(g[3]) >= 3;
-            if (full) {
-                p->s_trk = pool.take(g[rank[ROLE_TRK]]);
-                pool_rep[0] = pool.take(g[rank[ROLE_REP0]]);
-                pool_rep[1] = pool.take(g[rank[ROLE_REP1]]);
-                p->s_depth = pool.take(g[rank[ROLE_DEPTH]]);
-                pool_pre[0] = pool.take(g[rank[ROLE_PRE0]]);
-                pool_pre[1] = pool.take(g[rank[ROLE_PRE1]]);
-                p->s_flow = pool.take(g[rank[ROLE_FLOW]]);
-                pool_fx = pool.take(g[rank[ROLE_FLOW_X]]);
-            } else if (pool.count(g[0]) >= 3 && pool.count(g[1]) >= 3 && pool.count(g[2]) >= 1 && pool.count(g[3]) >= 1) {
-                p->s_trk = pool.take(g[0]);
-                pool_rep[0] = pool.take(g[0]);
-                pool_rep[1] = pool.take(g[0]);
-                p->s_depth = pool.take(g[1]);
-                pool_pre[0] = pool.take(g[1]);
-                pool_pre[1] = pool.take(g[1]);
-                p->s_flow = pool.take(g[2]);
-                pool_fx = pool.take(g[3]);
+            if (full)
+                for (int r = 0; r < ROLE_COUNT; ++r) from[r] = g[plan.lane[r]];
+            if (full || (pool.count(g[0]) >= 3 && pool.count(g[1]) >= 3 && pool.count(g[2]) >= 1 && pool.count(g[3]) >= 1)) {
+                p->s_trk = own(pool.take(from[ROLE_TRK]));
+                p->s_rep[0] = own(pool.take(from[ROLE_REP0]));
+                p->s_rep[1] = own(pool.take(from[ROLE_REP1]));
+                p->s_depth = own(pool.take(from[ROLE_DEPTH]));
+                p->s_pre[0] = own(pool.take(from[ROLE_PRE0]));
+                p->s_pre[1] = own(pool.take(from[ROLE_PRE1]));
+                p->s_flow = own(pool.take(from[ROLE_FLOW]));
+                if (fx) p->s_flow_x[0] = own(pool.take(from[ROLE_FLOW_X]));
             }
             if (p->s_trk) p->plan = plan;
         }
         pool.release();
     }
-    const bool lanes = p->plan.layout == LAYOUT_LANES;
-    if (!p->s_trk && (create_net_stream(&p->s_flow) != hipSuccess || create_net_stream(&p->s_depth) != hipSuccess ||
-                      create_solver_stream(&p->s_trk) != hipSuccess)) {
+    if (!p->s_trk && (create_owned(&p->s_flow, false) || create_owned(&p->s_depth, false) || create_owned(&p->s_trk, true))) {
         dfvo::set_last_error("dfvo_pipeline_create: hipStreamCreate failed (no GPU?)");
         return fail(DFVO_ERR_HIP);
     }
-    for (int i = 0; i < DFVO_PIPELINE_SLOTS; i++) {
-        if (hipEventCreateWithFlags(&p->e_flow[i], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&p->e_depth[i], hipEventDisableTiming) != hipSuccess) {
-            dfvo::set_last_error("dfvo_pipeline_create: hipEventCreate failed");
-            return fail(DFVO_ERR_HIP);
-        }
-    }
+    for (hipEvent_t* e : {&p->e_ref, &p->e_roll})
+        if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return fail(DFVO_ERR_HIP);
+    for (Slot& sl : p->slots)
+        for (hipEvent_t* e : {&sl.e_flow, &sl.e_depth, &sl.e_pre, &sl.e_res})
+            if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) {
+                dfvo::set_last_error("dfvo_pipeline_create: hipEventCreate failed");
+                return fail(DFVO_ERR_HIP);
+            }
     int rc = p->flow.init(p->H, p->W, p->s_flow);
     if (rc != DFVO_OK) return fail(rc);
-    // two LiteFlowNet instances on two pipes, alternating pairs (measured 1 / 2 / 3: 217 / 287 / 272 pairs/s, profiles/
-    // r3ag_flow_instances_ab.txt).  DFVO_FLOW_INSTANCES=1 is a test hook: the carry-over from a pass of the SAME instance
-    p->flow_instances = getenv("DFVO_FLOW_INSTANCES") && atoi(getenv("DFVO_FLOW_INSTANCES")) == 1 ? 1 : 2;
     for (int i = 0; i + 1 < p->flow_instances; ++i) {
-        if (i == 0 && lanes) {
-            p->s_flow_x[0] = p->lane[p->plan.lane[ROLE_FLOW_X]];
-        } else if (i == 0 && pool_fx) {
-            p->s_flow_x[0] = pool_fx;
-            pool_fx = nullptr;
-        } else if (create_net_stream(&p->s_flow_x[i]) != hipSuccess) {
-            return fail(DFVO_ERR_HIP);
-        }
+        if (!p->s_flow_x[i] && create_owned(&p->s_flow_x[i], false)) return fail(DFVO_ERR_HIP);
         rc = p->flow_x[i].init(p->H, p->W, p->s_flow_x[i]);
         if (rc != DFVO_OK) return fail(rc);
     }
@@ -213,13 +239,11 @@ int dfvo_pipeline_create(const dfvo_pipeline_cfg* cfg, dfvo_pipeline** out) {
     p->depth.min_depth = cfg->net_min_depth;
     p->depth.max_depth = cfg->net_max_depth;
     p->depth.baseline_mult = cfg->baseline_mult;
-    if (pool_fx) (void)hipStreamDestroy(pool_fx);
-    // (lanes: the chain's side streams are the chain's own stream, borrowed -- the pipeline destroys its lanes)
-    rc = lanes ? p->tbs[0].init(p->lane[p->plan.lane[ROLE_REP0]], p->lane[p->plan.lane[ROLE_REP1]], true)
-               : p->tbs[0].init(pool_rep[0], pool_rep[1]);
+    // (lanes: the chain's side streams are the chain's own stream)
+    rc = p->s_rep[0] ? p->slots[0].tb.init(p->s_rep[0], p->s_rep[1], true) : p->slots[0].tb.init();
     if (rc != DFVO_OK) return fail(rc);
     for (int i = 1; i < DFVO_PIPELINE_SLOTS; i++) {
-        rc = p->tbs[i].init_shared(p->tbs[0]);
+        rc = p->slots[i].tb.init_shared(p->slots[0].tb);
         if (rc != DFVO_OK) return fail(rc);
     }
     // the PnP fallback's buffers at their final size: grown lazily they would be freed and re-allocated (hipFree waits for
@@ -228,46 +252,18 @@ int dfvo_pipeline_create(const dfvo_pipeline_cfg* cfg, dfvo_pipeline** out) {
         rc = p->pnp.ensure(cfg->kp_num_bestN + 8, cfg->pnp_iters);
         if (rc != DFVO_OK) return fail(rc);
     }
-    for (int i = 0; i < 2; i++) {
-        if (lanes)
-            p->s_pre[i] = p->lane[p->plan.lane[ROLE_PRE0 + i]];
-        else if (pool_pre[i])
-            p->s_pre[i] = pool_pre[i];
-        else if (create_solver_stream(&p->s_pre[i], 4) != hipSuccess)
+    for (int i = 0; i < 2; i++)
+        if (!p->s_pre[i] && create_owned(&p->s_pre[i], true)) return fail(DFVO_ERR_HIP);
+    const size_t px = (size_t)p->H * p->W, feed_px = (size_t)p->feedH * p->feedW;
+    for (Slot& sl : p->slots)
+        if (sl.h_info.alloc(4) || sl.h_res.alloc(1) || sl.fwd.alloc(2 * px) || sl.bwd.alloc(2 * px) || sl.diff.alloc(px) ||
+            sl.raw_depth.alloc(px) || sl.proc_depth.alloc(px))
             return fail(DFVO_ERR_HIP);
-    }
-    for (int i = 0; i < DFVO_PIPELINE_SLOTS; i++) {
-        if (hipEventCreateWithFlags(&p->e_pre[i], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&p->e_res[i], hipEventDisableTiming) != hipSuccess ||
-            hipHostMalloc((void**)&p->h_info[i], 4 * sizeof(int), hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void**)&p->h_res[i], sizeof(PoseState) + sizeof(ScaleResult) + sizeof(PnpResult), hipHostMallocDefault) != hipSuccess)
-            return fail(DFVO_ERR_HIP);
-        p->begun_n[i] = -1;
-    }
-    const size_t px = (size_t)p->H * p->W;
-    for (int i = 0; i < DFVO_PIPELINE_SLOTS; i++) {
-        if (hipMalloc((void**)&p->fwd[i], 2 * px * sizeof(float)) != hipSuccess ||
-            hipMalloc((void**)&p->bwd[i], 2 * px * sizeof(float)) != hipSuccess ||
-            hipMalloc((void**)&p->diff[i], px * sizeof(float)) != hipSuccess ||
-            hipMalloc((void**)&p->raw_depth[i], px * sizeof(float)) != hipSuccess ||
-            hipMalloc((void**)&p->proc_depth[i], px * sizeof(double)) != hipSuccess) {
-            dfvo::set_last_error("dfvo_pipeline_create: hipMalloc failed");
-            return fail(DFVO_ERR_HIP);
-        }
-    }
-    if (hipMalloc((void**)&p->depth_small, (size_t)p->feedH * p->feedW * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&p->ref_depth, px * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&p->ref_raw, px * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&p->d_T21, 16 * sizeof(double)) != hipSuccess) {
-        dfvo::set_last_error("dfvo_pipeline_create: hipMalloc failed");
+    if (p->depth_small.alloc(feed_px) || p->ref_depth.alloc(px) || p->ref_raw.alloc(px) || p->d_T21.alloc(16) ||
+        p->feed_buf.alloc(feed_px * 3))
         return fail(DFVO_ERR_HIP);
-    }
-    if (hipMalloc((void**)&p->feed_buf, (size_t)p->feedH * p->feedW * 3) != hipSuccess) {
-        dfvo::set_last_error("dfvo_pipeline_create: hipMalloc failed");
-        return fail(DFVO_ERR_HIP);
-    }
     if (p->feed_resize.init(p->H, p->W, p->feedH, p->feedW) != DFVO_OK) return fail(DFVO_ERR_HIP);
-    enqueue_mt_seed(p->tbs[0], cfg->seed, p->s_trk);
+    enqueue_mt_seed(p->slots[0].tb, cfg->seed, p->s_trk);
     (void)hipStreamSynchronize(p->s_trk);
     if (getenv("DFVO_STREAM_PROBE_VERBOSE")) {
         char line[256];
@@ -277,52 +273,24 @@ int dfvo_pipeline_create(const dfvo_pipeline_cfg* cfg, dfvo_pipeline** out) {
     return DFVO_OK;
 }
 
+// also the failure path of dfvo_pipeline_create: every member may be in its initial state
 void dfvo_pipeline_destroy(dfvo_pipeline* p) {
     if (!p) return;
     (void)hipDeviceSynchronize();
-    const bool lanes = p->plan.layout == LAYOUT_LANES;  // every role's stream is one of lane[]
     p->flow.destroy();
-    for (int i = 0; i + 1 < p->flow_instances; ++i) {
-        p->flow_x[i].destroy();
-        if (p->s_flow_x[i] && !lanes) (void)hipStreamDestroy(p->s_flow_x[i]);
-    }
+    for (int i = 0; i + 1 < p->flow_instances; ++i) p->flow_x[i].destroy();
     p->depth.destroy();
-    for (int i = DFVO_PIPELINE_SLOTS - 1; i >= 0; i--) p->tbs[i].release();
-    for (BestNBuffers& bb : p->bestn) bb.release();
-    if (p->d_samples) (void)hipFree(p->d_samples);
-    for (int i = 0; i < 2; i++)
-        if (p->s_pre[i] && !lanes) (void)hipStreamDestroy(p->s_pre[i]);
-    for (int i = 0; i < DFVO_PIPELINE_SLOTS; i++) {
-        if (p->e_pre[i]) (void)hipEventDestroy(p->e_pre[i]);
-        if (p->e_res[i]) (void)hipEventDestroy(p->e_res[i]);
-        if (p->h_res[i]) (void)hipHostFree(p->h_res[i]);
-        if (i == 0 && p->e_ref) (void)hipEventDestroy(p->e_ref);
-        if (p->h_info[i]) (void)hipHostFree(p->h_info[i]);
+    for (int i = DFVO_PIPELINE_SLOTS - 1; i >= 0; i--) {
+        Slot& sl = p->slots[i];
+        sl.tb.release();  // (the sharing sets before slots[0].tb, whose RandomState and events they borrow)
+        for (hipEvent_t e : {sl.e_flow, sl.e_depth, sl.e_pre, sl.e_res})
+            if (e) (void)hipEventDestroy(e);
     }
-    for (int i = 0; i < DFVO_PIPELINE_SLOTS; i++) {
-        void* ptrs[] = {p->fwd[i], p->bwd[i], p->diff[i], p->raw_depth[i], p->proc_depth[i]};
-        for (void* q : ptrs)
-            if (q) (void)hipFree(q);
-        if (p->e_flow[i]) (void)hipEventDestroy(p->e_flow[i]);
-        if (p->e_depth[i]) (void)hipEventDestroy(p->e_depth[i]);
-        if (i == 0 && p->e_roll) (void)hipEventDestroy(p->e_roll);
-    }
-    if (p->depth_small) (void)hipFree(p->depth_small);
+    for (hipEvent_t e : {p->e_ref, p->e_roll})
+        if (e) (void)hipEventDestroy(e);
     p->feed_resize.release();
-    if (p->feed_buf) (void)hipFree(p->feed_buf);
-    if (p->ref_depth) (void)hipFree(p->ref_depth);
-    if (p->ref_raw) (void)hipFree(p->ref_raw);
-    p->pnp.release();
-    if (p->d_T21) (void)hipFree(p->d_T21);
-    if (lanes) {
-        for (hipStream_t l : p->lane)
-            if (l) (void)hipStreamDestroy(l);
-    } else {
-        if (p->s_flow) (void)hipStreamDestroy(p->s_flow);
-        if (p->s_depth) (void)hipStreamDestroy(p->s_depth);
-        if (p->s_trk) (void)hipStreamDestroy(p->s_trk);
-    }
-    delete p;
+    for (hipStream_t s : p->owned) (void)hipStreamDestroy(s);
+    delete p;  // (device and pinned memory: DevArr / PinnedArr members, here and in the buffer sets)
 }
 
 static int pipe_store(ParamStore* ps, const char* name, const float* h, int ndim, const int* shape) {
@@ -366,7 +334,7 @@ int dfvo_pipeline_seed(dfvo_pipeline* p, uint32_t seed) {
     DFVO_ARG_CHECK(p, "null pipeline");
     // synchronous: the first RandomState consumer of the next pair (the keypoint shuffles) runs on tb.s_rep[0], which is
     // ordered after the keypoint stage but not after s_trk -- the new key must be in place before track() is called
-    P_TRY(enqueue_mt_seed(p->tbs[0], seed, p->s_trk));
+    P_TRY(enqueue_mt_seed(p->slots[0].tb, seed, p->s_trk));
     DFVO_HIP_CHECK(hipStreamSynchronize(p->s_trk));
     return DFVO_OK;
 }
@@ -408,24 +376,34 @@ int dfvo_pipeline_set_options(dfvo_pipeline* p, const dfvo_pipeline_opts* o) {
         samples.resize(kp_count);
         generate_kp_samples(crop[0], crop[1], crop[2], crop[3], kp_count, samples.data());
     }
-    if (p->d_samples) {
-        (void)hipFree(p->d_samples);
-        p->d_samples = nullptr;
-    }
+    p->d_samples.release();
     if (!samples.empty()) {
-        DFVO_HIP_CHECK(hipMalloc((void**)&p->d_samples, sizeof(int) * samples.size()));
+        P_TRY(p->d_samples.alloc(samples.size()));
         DFVO_HIP_CHECK(hipMemcpy(p->d_samples, samples.data(), sizeof(int) * samples.size(), hipMemcpyHostToDevice));
     }
     if (kp_count > 0) {
         for (int i = 0; i < DFVO_PIPELINE_SLOTS; i++) {
-            P_TRY(p->tbs[i].ensure_kp(kp_count, 1, 1));
-            if (o->kp_source == DFVO_KP_SOURCE_BESTN) P_TRY(p->bestn[i].ensure((size_t)p->H * p->W, 0));
+            P_TRY(p->slots[i].tb.ensure_kp(kp_count, 1, 1));
+            if (o->kp_source == DFVO_KP_SOURCE_BESTN) P_TRY(p->slots[i].bestn.ensure((size_t)p->H * p->W, 0));
         }
         if (c.pnp_iters > 0) P_TRY(p->pnp.ensure(kp_count + 8, c.pnp_iters));
     }
     for (int i = 0; i < 4; ++i) p->sample_crop[i] = crop[i];
     p->opts = *o;
     return DFVO_OK;
+}
+
+// preprocess_depth of the depth net's output (crop, clamp, nearest resize to the image size) into a raw / processed pair, on
+// the depth stream.  Either target may still be read or written by the last roll-over copy on s_trk (proc_depth[slot] is its
+// source, ref_depth its target; track_end does not wait for it on the host): ordered behind it.  Placed after the net, so
+// nothing stalls in practice.
+static int enqueue_depth_post(dfvo_pipeline* p, float* raw, double* proc) {
+    const dfvo_pipeline_cfg& c = p->cfg;
+    const int y0 = (int)(p->H * c.depth_crop[0]), y1 = (int)(p->H * c.depth_crop[1]);
+    const int x0 = (int)(p->W * c.depth_crop[2]), x1 = (int)(p->W * c.depth_crop[3]);
+    if (p->roll_pending) DFVO_HIP_CHECK(hipStreamWaitEvent(p->s_depth, p->e_roll, 0));
+    return launch_depth_post(p->depth_small, p->feedH, p->feedW, p->H, p->W, y0, y1, x0, x1, (float)c.min_depth, (float)c.max_depth,
+                             raw, proc, p->s_depth);
 }
 
 int dfvo_pipeline_enqueue_nets(dfvo_pipeline* p, int slot, const uint8_t* d_ref, const uint8_t* d_cur,
@@ -435,6 +413,7 @@ int dfvo_pipeline_enqueue_nets(dfvo_pipeline* p, int slot, const uint8_t* d_ref,
     DFVO_ARG_CHECK(d_ref || p->last_flow, "dfvo_pipeline_enqueue_nets: d_ref == NULL (reference frame = the previous call's "
                                           "current frame) needs a previous call");
     p->started = true;
+    Slot& sl = p->slots[slot];
     const size_t px = (size_t)p->H * p->W;
     // depth of the current frame (dfvo.py:305-319); without a caller-resized frame the LANCZOS resize of
     // deep_models.py:195-199 runs here, ahead of the net on its stream
@@ -443,15 +422,8 @@ int dfvo_pipeline_enqueue_nets(dfvo_pipeline* p, int slot, const uint8_t* d_ref,
         d_cur_feed = p->feed_buf;
     }
     P_TRY(p->depth.forward(d_cur_feed, p->depth_small));
-    const dfvo_pipeline_cfg& c = p->cfg;
-    const int y0 = (int)(p->H * c.depth_crop[0]), y1 = (int)(p->H * c.depth_crop[1]);
-    const int x0 = (int)(p->W * c.depth_crop[2]), x1 = (int)(p->W * c.depth_crop[3]);
-    // proc_depth[slot] may still be the source of the previous occupant's roll-over copy on s_trk (track_end does not
-    // wait for it on the host): order the overwrite behind it.  Placed after the net, so nothing stalls in practice.
-    if (p->roll_pending) DFVO_HIP_CHECK(hipStreamWaitEvent(p->s_depth, p->e_roll, 0));
-    P_TRY(launch_depth_post(p->depth_small, p->feedH, p->feedW, p->H, p->W, y0, y1, x0, x1, (float)c.min_depth,
-                            (float)c.max_depth, p->raw_depth[slot], p->proc_depth[slot], p->s_depth));
-    DFVO_HIP_CHECK(hipEventRecord(p->e_depth[slot], p->s_depth));
+    P_TRY(enqueue_depth_post(p, sl.raw_depth, sl.proc_depth));
+    DFVO_HIP_CHECK(hipEventRecord(sl.e_depth, p->s_depth));
     // forward/backward flow (dfvo.py:321-335)
     const int inst = slot % p->flow_instances;
     FlowNet& fn = inst == 0 ? p->flow : p->flow_x[inst - 1];
@@ -465,11 +437,11 @@ int dfvo_pipeline_enqueue_nets(dfvo_pipeline* p, int slot, const uint8_t* d_ref,
     if (p->last_flow && p->last_flow != &fn && p->last_flow->e_feat) DFVO_HIP_CHECK(hipStreamWaitEvent(sf, p->last_flow->e_feat, 0));
     // (the net writing the slot's buffers itself, one levels graph per slot, was measured: no gain -- profiles/r3x_copy_ab.txt)
     P_TRY(fn.forward(d_ref, d_cur, fn.out_fwd.p, fn.out_bwd.p, fn.out_diff.p, d_ref ? nullptr : p->last_flow));
-    DFVO_HIP_CHECK(hipMemcpyAsync(p->fwd[slot], fn.out_fwd.p, 2 * px * sizeof(float), hipMemcpyDeviceToDevice, sf));
-    DFVO_HIP_CHECK(hipMemcpyAsync(p->bwd[slot], fn.out_bwd.p, 2 * px * sizeof(float), hipMemcpyDeviceToDevice, sf));
-    DFVO_HIP_CHECK(hipMemcpyAsync(p->diff[slot], fn.out_diff.p, px * sizeof(float), hipMemcpyDeviceToDevice, sf));
+    DFVO_HIP_CHECK(hipMemcpyAsync(sl.fwd, fn.out_fwd.p, 2 * px * sizeof(float), hipMemcpyDeviceToDevice, sf));
+    DFVO_HIP_CHECK(hipMemcpyAsync(sl.bwd, fn.out_bwd.p, 2 * px * sizeof(float), hipMemcpyDeviceToDevice, sf));
+    DFVO_HIP_CHECK(hipMemcpyAsync(sl.diff, fn.out_diff.p, px * sizeof(float), hipMemcpyDeviceToDevice, sf));
     p->last_flow = &fn;
-    DFVO_HIP_CHECK(hipEventRecord(p->e_flow[slot], sf));
+    DFVO_HIP_CHECK(hipEventRecord(sl.e_flow, sf));
     return DFVO_OK;
 }
 
@@ -483,15 +455,9 @@ int dfvo_pipeline_set_ref_depth(dfvo_pipeline* p, const uint8_t* d_feed, const d
         DFVO_HIP_CHECK(hipStreamSynchronize(p->s_trk));
     } else {
         P_TRY(p->depth.forward(d_feed, p->depth_small));
-        const dfvo_pipeline_cfg& c = p->cfg;
-        const int y0 = (int)(p->H * c.depth_crop[0]), y1 = (int)(p->H * c.depth_crop[1]);
-        const int x0 = (int)(p->W * c.depth_crop[2]), x1 = (int)(p->W * c.depth_crop[3]);
-        if (p->roll_pending) DFVO_HIP_CHECK(hipStreamWaitEvent(p->s_depth, p->e_roll, 0));  // WAW on ref_depth vs the roll-over
-        P_TRY(launch_depth_post(p->depth_small, p->feedH, p->feedW, p->H, p->W, y0, y1, x0, x1, (float)c.min_depth,
-                                (float)c.max_depth, p->ref_raw, p->ref_depth, p->s_depth));
+        P_TRY(enqueue_depth_post(p, p->ref_raw, p->ref_depth));
         // not waited for on the host: the solver stream (PnP fallback reads the reference depth, the roll-over writes it)
         // is ordered behind it on the device, the depth stream runs its later passes in order anyway
-        if (!p->e_ref) DFVO_HIP_CHECK(hipEventCreateWithFlags(&p->e_ref, hipEventDisableTiming));
         DFVO_HIP_CHECK(hipEventRecord(p->e_ref, p->s_depth));
         DFVO_HIP_CHECK(hipStreamWaitEvent(p->s_trk, p->e_ref, 0));
     }
@@ -508,10 +474,9 @@ int dfvo_pipeline_set_ref_image(dfvo_pipeline* p, const uint8_t* d_img) {
 // the current frame's depth becomes the reference depth of the next pair (dfvo.py:  ref_data <- cur_data)
 static int roll_ref_depth(dfvo_pipeline* p, int slot, const double* d_depth_override) {
     const size_t px = (size_t)p->H * p->W;
-    DFVO_HIP_CHECK(hipStreamWaitEvent(p->s_trk, p->e_depth[slot], 0));
-    const double* depth = d_depth_override ? d_depth_override : p->proc_depth[slot];
+    DFVO_HIP_CHECK(hipStreamWaitEvent(p->s_trk, p->slots[slot].e_depth, 0));
+    const double* depth = d_depth_override ? d_depth_override : p->slots[slot].proc_depth.p;
     DFVO_HIP_CHECK(hipMemcpyAsync(p->ref_depth, depth, px * sizeof(double), hipMemcpyDeviceToDevice, p->s_trk));
-    if (!p->e_roll) DFVO_HIP_CHECK(hipEventCreateWithFlags(&p->e_roll, hipEventDisableTiming));
     DFVO_HIP_CHECK(hipEventRecord(p->e_roll, p->s_trk));
     p->roll_pending = true;
     p->has_ref_depth = true;
@@ -546,6 +511,18 @@ static void fill_pnp_cfg(const dfvo_pipeline_cfg& c, PnpConfig* pc3) {
     pc3->reproj_thre = c.pnp_reproj_thre;
 }
 
+static void fill_scale_cfg(const dfvo_pipeline_cfg& c, const dfvo_pipeline_opts& o, ScaleConfig* sc) {
+    sc->cx = c.cx;
+    sc->cy = c.cy;
+    sc->fx = c.fx;
+    sc->fy = c.fy;
+    sc->min_samples = c.scale_min_samples;
+    sc->max_trials = c.scale_max_trials;
+    sc->stop_prob = c.scale_stop_prob;
+    sc->thre = c.scale_thre;
+    sc->method = o.scale_method;
+}
+
 static void fill_pnp_out(const PnpResult& pr, dfvo_track_out* out) {
     for (int i = 0; i < 9; i++) out->R[i] = pr.R[i];
     for (int i = 0; i < 3; i++) out->t[i] = pr.tvec[i];
@@ -564,13 +541,14 @@ static int enqueue_pre_part(dfvo_pipeline* p, int slot, const float* d_flow_over
                             hipStream_t sp) {
     const dfvo_pipeline_cfg& c = p->cfg;
     const dfvo_pipeline_opts& o = p->opts;
-    TrackerBuffers& tb = p->tbs[slot];
-    DFVO_HIP_CHECK(hipStreamWaitEvent(sp, p->e_flow[slot], 0));
-    const float* flow = d_flow_override ? d_flow_override : p->fwd[slot];
-    const float* diff = d_diff_override ? d_diff_override : p->diff[slot];
+    Slot& sl = p->slots[slot];
+    TrackerBuffers& tb = sl.tb;
+    DFVO_HIP_CHECK(hipStreamWaitEvent(sp, sl.e_flow, 0));
+    const float* flow = d_flow_override ? d_flow_override : sl.fwd.p;
+    const float* diff = d_diff_override ? d_diff_override : sl.diff.p;
     // the keypoint stage by source; each leaves tb.kp_ref / tb.kp_cur / tb.kp_info = [n, good_kp_found, ..] behind on sp
     if (o.kp_source == DFVO_KP_SOURCE_BESTN) {
-        P_TRY(enqueue_bestn_flow_kp(p->bestn[slot], flow, diff, p->H, p->W, c.kp_num_bestN, sp, tb.kp_ref, tb.kp_cur, tb.kp_info));
+        P_TRY(enqueue_bestn_flow_kp(sl.bestn, flow, diff, p->H, p->W, c.kp_num_bestN, sp, tb.kp_ref, tb.kp_cur, tb.kp_info));
     } else if (o.kp_source == DFVO_KP_SOURCE_SAMPLED) {
         P_TRY(enqueue_kp_sampled(flow, p->H, p->W, p->sample_crop[0], p->sample_crop[1], p->sample_crop[2], p->sample_crop[3],
                                  p->d_samples, o.kp_sampled_num, tb.kp_ref, tb.kp_cur, sp, tb.kp_info));
@@ -578,8 +556,8 @@ static int enqueue_pre_part(dfvo_pipeline* p, int slot, const float* d_flow_over
         P_TRY(enqueue_local_bestn(tb, flow, diff, p->H, p->W, c.kp_num_row, c.kp_num_col, c.kp_num_bestN, (float)c.kp_thre, sp,
                                   o.kp_score_method));
     }
-    DFVO_HIP_CHECK(hipMemcpyAsync(p->h_info[slot], tb.kp_info, 3 * sizeof(int), hipMemcpyDeviceToHost, sp));
-    DFVO_HIP_CHECK(hipEventRecord(p->e_pre[slot], sp));  // the host only needs the keypoint count; tb.ev_h orders the rest
+    DFVO_HIP_CHECK(hipMemcpyAsync(sl.h_info, tb.kp_info, 3 * sizeof(int), hipMemcpyDeviceToHost, sp));
+    DFVO_HIP_CHECK(hipEventRecord(sl.e_pre, sp));  // the host only needs the keypoint count; tb.ev_h orders the rest
     if (o.tracking_method == DFVO_TRACKING_PNP) {
         // dfvo.py:165: no E-tracker at all.  The inlier mask stays what dfvo_pipeline_get_keypoints documents for a pair
         // the E-tracker did not see: all ones
@@ -594,9 +572,9 @@ static int enqueue_pre_part(dfvo_pipeline* p, int slot, const float* d_flow_over
 
 int dfvo_pipeline_prefetch_track(dfvo_pipeline* p, int slot, const float* d_flow_override, const float* d_diff_override) {
     DFVO_ARG_CHECK(p && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS), "dfvo_pipeline_prefetch_track: bad argument");
-    DFVO_ARG_CHECK(!p->prefetched[slot], "dfvo_pipeline_prefetch_track: slot already prefetched and not yet tracked");
+    DFVO_ARG_CHECK(!p->slots[slot].prefetched, "dfvo_pipeline_prefetch_track: slot already prefetched and not yet tracked");
     P_TRY(enqueue_pre_part(p, slot, d_flow_override, d_diff_override, p->s_pre[slot & 1]));
-    p->prefetched[slot] = true;
+    p->slots[slot].prefetched = true;
     return DFVO_OK;
 }
 
@@ -606,12 +584,13 @@ int dfvo_pipeline_prefetch_track(dfvo_pipeline* p, int slot, const float* d_flow
 int dfvo_pipeline_track_begin(dfvo_pipeline* p, int slot, const float* d_flow_override, const float* d_diff_override,
                               const double* d_depth_override) {
     DFVO_ARG_CHECK(p && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS), "dfvo_pipeline_track_begin: bad argument");
-    DFVO_ARG_CHECK(p->begun_n[slot] == -1, "dfvo_pipeline_track_begin: the slot's previous pair was not collected (track_end)");
+    DFVO_ARG_CHECK(p->slots[slot].begun == IDLE, "dfvo_pipeline_track_begin: the slot's previous pair was not collected (track_end)");
     DFVO_ARG_CHECK(p->pending_slot == -1, "dfvo_pipeline_track_begin: another pair is begun and not yet collected -- the PnP decision "
                                           "of track_end (RandomState draws) comes before the next pair's chain");
     const dfvo_pipeline_cfg& c = p->cfg;
     hipStream_t s = p->s_trk;
-    TrackerBuffers& tb = p->tbs[slot];
+    Slot& sl = p->slots[slot];
+    TrackerBuffers& tb = sl.tb;
     static const bool trace = getenv("DFVO_TRACK_TRACE") != nullptr;
     if (trace && !tb.ev_t[0])
         for (int i = 0; i < 4; i++) DFVO_HIP_CHECK(hipEventCreate(&tb.ev_t[i]));
@@ -620,61 +599,44 @@ int dfvo_pipeline_track_begin(dfvo_pipeline* p, int slot, const float* d_flow_ov
     if (!pnp_only) P_TRY(enqueue_scale_prepare(tb, p->H, p->W));
     // A pre-part nobody prefetched: in the lane layout it goes onto the chain's lane (s), whose next work needs it anyway --
     // the depth lane may already hold later pairs' nets, and it would run behind them
-    if (!p->prefetched[slot])
+    if (!sl.prefetched)
         P_TRY(enqueue_pre_part(p, slot, d_flow_override, d_diff_override, p->plan.layout == LAYOUT_LANES ? s : p->s_pre[slot & 1]));
-    p->prefetched[slot] = false;
-    DFVO_HIP_CHECK(hipEventSynchronize(p->e_pre[slot]));  // keypoint info is in pinned host memory now
-    const int* info = p->h_info[slot];
-    p->begun_depth_override[slot] = d_depth_override;
-    if (!info[1]) {
-        p->begun_n[slot] = -2;
+    sl.prefetched = false;
+    DFVO_HIP_CHECK(hipEventSynchronize(sl.e_pre));  // keypoint info is in pinned host memory now
+    const int* info = sl.h_info;
+    sl.depth_override = d_depth_override;
+    auto begun = [&](Begun b) {  // the pair is pending from here on
+        sl.begun = b;
         p->pending_slot = slot;
         return DFVO_OK;
-    }
-    const int n = info[0];
+    };
+    if (!info[1]) return begun(NO_KEYPOINTS);
+    const int n = sl.n = info[0];
     if (pnp_only) {
         // dfvo.py:225-250 on every pair: E_pose stays SE3(), so the only RandomState draws of the pair are PnP's shuffles.
         // The keypoint stage is complete (the host waited for e_pre above); the reference depth is ordered on s by
         // set_ref_depth / the previous pair's roll-over
-        if (!p->has_ref_depth) {
-            p->begun_n[slot] = -3;
-            p->pending_slot = slot;
-            return DFVO_OK;
-        }
+        if (!p->has_ref_depth) return begun(NO_REF_DEPTH);
         PnpConfig pc3;
         fill_pnp_cfg(c, &pc3);
         P_TRY(enqueue_compute_pose_3d2d(p->pnp, tb.mt_state, tb.kp_ref, tb.kp_cur, tb.kp_info, n, p->ref_depth, p->H, p->W, pc3, s));
-        char* hr = (char*)p->h_res[slot] + sizeof(PoseState) + sizeof(ScaleResult);
-        DFVO_HIP_CHECK(hipMemcpyAsync(hr, p->pnp.result, sizeof(PnpResult), hipMemcpyDeviceToHost, s));
-        DFVO_HIP_CHECK(hipEventRecord(p->e_res[slot], s));
-        p->begun_n[slot] = n;
-        p->pending_slot = slot;
-        return DFVO_OK;
+        DFVO_HIP_CHECK(hipMemcpyAsync(&sl.h_res.p->pnp, p->pnp.result, sizeof(PnpResult), hipMemcpyDeviceToHost, s));
+        DFVO_HIP_CHECK(hipEventRecord(sl.e_res, s));
+        return begun(CHAIN_ENQUEUED);
     }
     PoseConfig pc;
     fill_pose_cfg(c, p->opts, &pc);
     P_TRY(enqueue_pose_e_part(tb, n, pc, s, p->d_T21));  // waits for tb.ev_h (the prefetched half) on the device
-    DFVO_HIP_CHECK(hipStreamWaitEvent(s, p->e_depth[slot], 0));
+    DFVO_HIP_CHECK(hipStreamWaitEvent(s, sl.e_depth, 0));
     ScaleConfig sc;
-    sc.cx = c.cx;
-    sc.cy = c.cy;
-    sc.fx = c.fx;
-    sc.fy = c.fy;
-    sc.min_samples = c.scale_min_samples;
-    sc.max_trials = c.scale_max_trials;
-    sc.stop_prob = c.scale_stop_prob;
-    sc.thre = c.scale_thre;
-    sc.method = p->opts.scale_method;
-    const double* depth = d_depth_override ? d_depth_override : p->proc_depth[slot];
+    fill_scale_cfg(c, p->opts, &sc);
+    const double* depth = d_depth_override ? d_depth_override : sl.proc_depth.p;
     P_TRY(enqueue_find_scale(tb, n, p->d_T21, depth, p->H, p->W, sc, s, tb.pose, true));
     if (tb.ev_t[3]) DFVO_HIP_CHECK(hipEventRecord(tb.ev_t[3], s));
-    char* hr = (char*)p->h_res[slot];
-    DFVO_HIP_CHECK(hipMemcpyAsync(hr, tb.pose, sizeof(PoseState), hipMemcpyDeviceToHost, s));
-    DFVO_HIP_CHECK(hipMemcpyAsync(hr + sizeof(PoseState), tb.scale_out, sizeof(ScaleResult), hipMemcpyDeviceToHost, s));
-    DFVO_HIP_CHECK(hipEventRecord(p->e_res[slot], s));
-    p->begun_n[slot] = n;
-    p->pending_slot = slot;
-    return DFVO_OK;
+    DFVO_HIP_CHECK(hipMemcpyAsync(&sl.h_res.p->pose, tb.pose, sizeof(PoseState), hipMemcpyDeviceToHost, s));
+    DFVO_HIP_CHECK(hipMemcpyAsync(&sl.h_res.p->scale, tb.scale_out, sizeof(ScaleResult), hipMemcpyDeviceToHost, s));
+    DFVO_HIP_CHECK(hipEventRecord(sl.e_res, s));
+    return begun(CHAIN_ENQUEUED);
 }
 
 // Second half: waits for the chain's results, runs the PnP fallback where the reference takes it (dfvo.py:225-250; decided
@@ -682,10 +644,11 @@ int dfvo_pipeline_track_begin(dfvo_pipeline* p, int slot, const float* d_flow_ov
 // the reference depth over.
 int dfvo_pipeline_track_end(dfvo_pipeline* p, int slot, dfvo_track_out* out) {
     DFVO_ARG_CHECK(p && out && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS), "dfvo_pipeline_track_end: bad argument");
-    DFVO_ARG_CHECK(p->begun_n[slot] != -1, "dfvo_pipeline_track_end: no pair pending in this slot (track_begin)");
+    DFVO_ARG_CHECK(p->slots[slot].begun != IDLE, "dfvo_pipeline_track_end: no pair pending in this slot (track_begin)");
     const dfvo_pipeline_cfg& c = p->cfg;
     hipStream_t s = p->s_trk;
-    TrackerBuffers& tb = p->tbs[slot];
+    Slot& sl = p->slots[slot];
+    TrackerBuffers& tb = sl.tb;
     static const bool trace = getenv("DFVO_TRACK_TRACE") != nullptr;  // host-side phase timing (tuning aid)
     static double tr_acc[2] = {0, 0}, tr_dev[3] = {0, 0, 0};
     static int tr_dev_n = 0, tr_n = 0;
@@ -693,16 +656,17 @@ int dfvo_pipeline_track_end(dfvo_pipeline* p, int slot, dfvo_track_out* out) {
     auto tr_ms = [&](std::chrono::steady_clock::time_point a) {
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
     };
-    const int n = p->begun_n[slot];
-    const double* d_depth_override = p->begun_depth_override[slot];
-    p->begun_n[slot] = -1;
+    const Begun begun = sl.begun;
+    const int n = sl.n;
+    const double* d_depth_override = sl.depth_override;
+    sl.begun = IDLE;
     p->pending_slot = -1;
     memset(out, 0, sizeof(*out));
     for (int i = 0; i < 3; i++) out->R[i * 4] = 1.0;
-    const int* info = p->h_info[slot];
+    const int* info = sl.h_info;
     out->n_kp = info[0];
     out->good_kp_found = info[1];
-    if (n == -2) {
+    if (begun == NO_KEYPOINTS) {
         out->status = DFVO_TRACK_CONSTANT_MOTION;
         P_TRY(roll_ref_depth(p, slot, d_depth_override));
         DFVO_HIP_CHECK(hipStreamSynchronize(s));
@@ -711,21 +675,18 @@ int dfvo_pipeline_track_end(dfvo_pipeline* p, int slot, dfvo_track_out* out) {
     if (p->opts.tracking_method == DFVO_TRACKING_PNP) {
         // the PnP chain was enqueued by track_begin: nothing to decide here, only its result to wait for
         out->status = DFVO_TRACK_NEEDS_PNP;
-        if (n != -3) {
-            DFVO_HIP_CHECK(hipEventSynchronize(p->e_res[slot]));
-            PnpResult pr;
-            memcpy(&pr, (const char*)p->h_res[slot] + sizeof(PoseState) + sizeof(ScaleResult), sizeof(pr));
+        if (begun != NO_REF_DEPTH) {
+            DFVO_HIP_CHECK(hipEventSynchronize(sl.e_res));
+            const PnpResult pr = sl.h_res.p->pnp;
             DFVO_ARG_CHECK(pr.status >= 0, "dfvo_pipeline_track: the PnP tracker reported an internal error");
             fill_pnp_out(pr, out);
         }
         return roll_ref_depth(p, slot, d_depth_override);
     }
-    DFVO_HIP_CHECK(hipEventSynchronize(p->e_res[slot]));
+    DFVO_HIP_CHECK(hipEventSynchronize(sl.e_res));
     const double tr_wait = tr_ms(tr0);
-    PoseState ps;
-    ScaleResult sr;
-    memcpy(&ps, p->h_res[slot], sizeof(ps));
-    memcpy(&sr, (const char*)p->h_res[slot] + sizeof(PoseState), sizeof(sr));
+    const PoseState ps = sl.h_res.p->pose;
+    const ScaleResult sr = sl.h_res.p->scale;
     for (int i = 0; i < 9; i++) out->R[i] = ps.R[i];
     for (int i = 0; i < 3; i++) out->t[i] = ps.t[i];
     out->best_inlier_cnt = ps.best_cnt;
@@ -793,12 +754,13 @@ int dfvo_pipeline_get_flow(dfvo_pipeline* p, int slot, float* h_fwd, float* h_bw
                            double* h_depth) {
     DFVO_ARG_CHECK(p && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS), "dfvo_pipeline_get_flow: bad argument");
     const size_t px = (size_t)p->H * p->W;
+    const Slot& sl = p->slots[slot];
     DFVO_HIP_CHECK(hipDeviceSynchronize());
-    if (h_fwd) DFVO_HIP_CHECK(hipMemcpy(h_fwd, p->fwd[slot], 2 * px * sizeof(float), hipMemcpyDeviceToHost));
-    if (h_bwd) DFVO_HIP_CHECK(hipMemcpy(h_bwd, p->bwd[slot], 2 * px * sizeof(float), hipMemcpyDeviceToHost));
-    if (h_diff) DFVO_HIP_CHECK(hipMemcpy(h_diff, p->diff[slot], px * sizeof(float), hipMemcpyDeviceToHost));
-    if (h_raw_depth) DFVO_HIP_CHECK(hipMemcpy(h_raw_depth, p->raw_depth[slot], px * sizeof(float), hipMemcpyDeviceToHost));
-    if (h_depth) DFVO_HIP_CHECK(hipMemcpy(h_depth, p->proc_depth[slot], px * sizeof(double), hipMemcpyDeviceToHost));
+    if (h_fwd) DFVO_HIP_CHECK(hipMemcpy(h_fwd, sl.fwd, 2 * px * sizeof(float), hipMemcpyDeviceToHost));
+    if (h_bwd) DFVO_HIP_CHECK(hipMemcpy(h_bwd, sl.bwd, 2 * px * sizeof(float), hipMemcpyDeviceToHost));
+    if (h_diff) DFVO_HIP_CHECK(hipMemcpy(h_diff, sl.diff, px * sizeof(float), hipMemcpyDeviceToHost));
+    if (h_raw_depth) DFVO_HIP_CHECK(hipMemcpy(h_raw_depth, sl.raw_depth, px * sizeof(float), hipMemcpyDeviceToHost));
+    if (h_depth) DFVO_HIP_CHECK(hipMemcpy(h_depth, sl.proc_depth, px * sizeof(double), hipMemcpyDeviceToHost));
     return DFVO_OK;
 }
 
@@ -806,7 +768,7 @@ int dfvo_pipeline_get_keypoints(dfvo_pipeline* p, int slot, int cap, double* h_k
                                 uint8_t* h_inliers, int* n_out) {
     DFVO_ARG_CHECK(p && n_out && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS) && cap >= 0,
                    "dfvo_pipeline_get_keypoints: bad argument");
-    TrackerBuffers& tb = p->tbs[slot];
+    TrackerBuffers& tb = p->slots[slot].tb;
     DFVO_HIP_CHECK(hipDeviceSynchronize());
     int info[3] = {0, 0, 0};
     DFVO_HIP_CHECK(hipMemcpy(info, tb.kp_info, sizeof(info), hipMemcpyDeviceToHost));
@@ -821,14 +783,14 @@ int dfvo_pipeline_get_keypoints(dfvo_pipeline* p, int slot, int cap, double* h_k
 int dfvo_pipeline_get_rng_state(dfvo_pipeline* p, uint32_t* h_state) {
     DFVO_ARG_CHECK(p && h_state, "dfvo_pipeline_get_rng_state: null argument");
     DFVO_HIP_CHECK(hipStreamSynchronize(p->s_trk));
-    DFVO_HIP_CHECK(hipMemcpy(h_state, p->tbs[0].mt_state, 625 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    DFVO_HIP_CHECK(hipMemcpy(h_state, p->slots[0].tb.mt_state, 625 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return DFVO_OK;
 }
 
 int dfvo_pipeline_set_rng_state(dfvo_pipeline* p, const uint32_t* h_state) {
     DFVO_ARG_CHECK(p && h_state, "dfvo_pipeline_set_rng_state: null argument");
     DFVO_HIP_CHECK(hipStreamSynchronize(p->s_trk));
-    DFVO_HIP_CHECK(hipMemcpy(p->tbs[0].mt_state, h_state, 625 * sizeof(uint32_t), hipMemcpyHostToDevice));
+    DFVO_HIP_CHECK(hipMemcpy(p->slots[0].tb.mt_state, h_state, 625 * sizeof(uint32_t), hipMemcpyHostToDevice));
     return DFVO_OK;
 }
 
@@ -845,7 +807,7 @@ int dfvo_pipeline_stream_layout(dfvo_pipeline* p, char* buf, int n) {
     DFVO_ARG_CHECK(p && buf && n > 0, "dfvo_pipeline_stream_layout: bad argument");
     // "layout=lanes groups=4 queues=4 streams=4 trk=3 rep0=3 ... flow_x=1": per role the index of its stream among the
     // pipeline's distinct streams (lanes: the lane), so equal numbers mean one stream
-    hipStream_t role[ROLE_COUNT] = {p->s_trk, p->tbs[0].s_rep[0], p->tbs[0].s_rep[1], p->s_depth, p->s_pre[0], p->s_pre[1], p->s_flow,
+    hipStream_t role[ROLE_COUNT] = {p->s_trk, p->slots[0].tb.s_rep[0], p->slots[0].tb.s_rep[1], p->s_depth, p->s_pre[0], p->s_pre[1], p->s_flow,
                                     p->flow_instances > 1 ? p->s_flow_x[0] : nullptr};
     std::vector<hipStream_t> distinct;
     const bool lanes = p->plan.layout == LAYOUT_LANES;

@@ -1,6 +1,6 @@
 // Device-side RANSAC state + workspaces shared by the solver kernels and the tracker pipeline.
 #pragma once
-#include "dfvo_common.h"
+#include "dev_mem.h"
 
 namespace dfvo {
 
@@ -20,22 +20,22 @@ struct RansacState {
 };
 
 struct RansacWorkspace {
-    RansacState* state = nullptr;
-    double *pts_a = nullptr, *pts_b = nullptr;    // staged input points [n][2]
-    double *norm_a = nullptr, *norm_b = nullptr;  // K-normalised points (E, recoverPose)
-    float *f_a = nullptr, *f_b = nullptr;         // float points (homography)
-    int* idx = nullptr;                           // subset indices [iters][5]
-    double* ws = nullptr;                         // five-point scratch [iters][E_WS]
-    int* ok = nullptr;
-    double* models = nullptr;                     // [iters][10][9]
-    int* nmodels = nullptr;
-    int* counts = nullptr;                        // [iters][10]
-    uint8_t* mask = nullptr;                      // [n]
-    double* out = nullptr;                        // 64 doubles of small results
-    double* lm = nullptr;                         // LM / recoverPose scratch
-    int* cidx = nullptr;                          // compacted inlier indices
+    DevArr<RansacState> state;
+    DevArr<double> pts_a, pts_b;    // staged input points [n][2]
+    DevArr<double> norm_a, norm_b;  // K-normalised points (E, recoverPose)
+    DevArr<float> f_a, f_b;         // float points (homography)
+    DevArr<int> idx;                // subset indices [iters][5]
+    DevArr<double> ws;              // five-point scratch [iters][E_WS]
+    DevArr<int> ok;
+    DevArr<double> models;          // [iters][10][9]
+    DevArr<int> nmodels;
+    DevArr<int> counts;             // [iters][10]
+    DevArr<uint8_t> mask;           // [n]
+    DevArr<double> out;             // 64 doubles of small results
+    DevArr<double> lm;              // LM / recoverPose scratch
+    DevArr<int> cidx;               // compacted inlier indices
     int cap_n = 0, cap_iters = 0;
-    int ensure(int n, int max_iters);
+    int ensure(int n, int max_iters);  // (solver_buffers.hip, as every ensure / release)
     void release();
 };
 

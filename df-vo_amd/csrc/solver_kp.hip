@@ -232,43 +232,6 @@ __global__ __launch_bounds__(256) void k_bestn_select(const float* __restrict__ 
     }
 }
 
-void BestNBuffers::release() {
-    void* ptrs[] = {key_base, tosort, map, Lpos, Rpos, count, kp};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    key_base = nullptr;
-    tosort = map = Lpos = Rpos = count = nullptr;
-    kp = nullptr;
-    cap = 0;
-    kp_cap = 0;
-}
-
-int BestNBuffers::ensure(size_t n, int N) {
-    BestNBuffers& bb = *this;
-    if (n > bb.cap) {
-        const int keep_kp = bb.kp_cap;
-        double* kp_keep = bb.kp;
-        bb.kp = nullptr;
-        bb.release();
-        bb.kp = kp_keep;
-        bb.kp_cap = keep_kp;
-        bb.cap = n;
-        DFVO_HIP_CHECK(hipMalloc((void**)&bb.key_base, sizeof(float) * ((size_t)n + 16)));  // slack: the 4-wide scans over-read
-        DFVO_HIP_CHECK(hipMemset(bb.key_base, 0, sizeof(float) * ((size_t)n + 16)));
-        DFVO_HIP_CHECK(hipMalloc((void**)&bb.tosort, sizeof(int) * (size_t)n));
-        DFVO_HIP_CHECK(hipMalloc((void**)&bb.map, sizeof(int) * (size_t)n));
-        DFVO_HIP_CHECK(hipMalloc((void**)&bb.Lpos, sizeof(int) * ((size_t)n + 2)));
-        DFVO_HIP_CHECK(hipMalloc((void**)&bb.Rpos, sizeof(int) * ((size_t)n + 2)));
-        DFVO_HIP_CHECK(hipMalloc((void**)&bb.count, sizeof(int) * 4));
-    }
-    if (N > bb.kp_cap) {
-        if (bb.kp) (void)hipFree(bb.kp);
-        bb.kp_cap = N;
-        DFVO_HIP_CHECK(hipMalloc((void**)&bb.kp, sizeof(double) * 4 * (size_t)N));
-    }
-    return DFVO_OK;
-}
-
 int enqueue_bestn_flow_kp(BestNBuffers& bb, const float* d_flow, const float* d_diff, int H, int W, int N, hipStream_t s,
                           double* d_kp1, double* d_kp2, int* d_info) {
     DFVO_ARG_CHECK(H > 0 && W > 0 && N >= 1 && (long long)H * W < (1ll << 30), "bestN: bad size");
@@ -536,50 +499,6 @@ __global__ __launch_bounds__(256) void k_kp_cell_rigid(const float* __restrict__
     }
 }
 
-void RigidKpBuffers::release() {
-    void* ptrs[] = {depth32, rdiff, mats, cell_count, cell_sel, cell_sel_uni, lidx, kp, info, zero};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    depth32 = rdiff = mats = nullptr;
-    cell_count = cell_sel = cell_sel_uni = info = zero = nullptr;
-    lidx = nullptr;
-    kp = nullptr;
-    px_cap = sel_cap = 0;
-    lidx_cap = 0;
-}
-
-int RigidKpBuffers::ensure(int H, int W, int cells, int n_best, int cap) {
-    const size_t px = (size_t)H * W;
-    if (px > px_cap) {
-        if (depth32) (void)hipFree(depth32);
-        if (rdiff) (void)hipFree(rdiff);
-        px_cap = px;
-        DFVO_HIP_CHECK(hipMalloc((void**)&depth32, sizeof(float) * px));
-        DFVO_HIP_CHECK(hipMalloc((void**)&rdiff, sizeof(float) * px));
-    }
-    if (!mats) {
-        DFVO_HIP_CHECK(hipMalloc((void**)&mats, sizeof(float) * 40));
-        DFVO_HIP_CHECK(hipMalloc((void**)&cell_count, sizeof(int) * 1024));
-        DFVO_HIP_CHECK(hipMalloc((void**)&info, sizeof(int) * 8));
-        DFVO_HIP_CHECK(hipMalloc((void**)&zero, sizeof(int) * 2));
-        DFVO_HIP_CHECK(hipMemset(zero, 0, sizeof(int) * 2));
-    }
-    if (cells * n_best > sel_cap) {
-        for (void* p : {(void*)cell_sel, (void*)cell_sel_uni, (void*)kp})
-            if (p) (void)hipFree(p);
-        sel_cap = cells * n_best;
-        DFVO_HIP_CHECK(hipMalloc((void**)&cell_sel, sizeof(int) * sel_cap));
-        DFVO_HIP_CHECK(hipMalloc((void**)&cell_sel_uni, sizeof(int) * sel_cap));
-        DFVO_HIP_CHECK(hipMalloc((void**)&kp, sizeof(double) * 8 * sel_cap));
-    }
-    if ((size_t)cells * cap > lidx_cap) {
-        if (lidx) (void)hipFree(lidx);
-        lidx_cap = (size_t)cells * cap;
-        DFVO_HIP_CHECK(hipMalloc((void**)&lidx, sizeof(unsigned short) * lidx_cap));
-    }
-    return DFVO_OK;
-}
-
 // rigid flow of the reference depth under `T` (ref -> cur), its distance to the optical flow (kept in rb.rdiff), then
 // the two keypoint sets: rb.kp = [kp1_best | kp2_best | kp1_uniform | kp2_uniform], each sel_cap x 2 doubles;
 // rb.info[0] = their common count.  d_rdiff_override (optional) replaces the computed distance map.
@@ -687,19 +606,11 @@ int enqueue_local_bestn(TrackerBuffers& tb, const float* d_flow, const float* d_
     if (par) lds += (size_t)cap * 4 + 16;
     int rc = tb.ensure_kp(cells * n_best, cells, n_best);
     if (rc != DFVO_OK) return rc;
-    if ((size_t)cells * cap > tb.lidx_cap) {
-        if (tb.lidx) (void)hipFree(tb.lidx);
-        tb.lidx_cap = (size_t)cells * cap;
-        DFVO_HIP_CHECK(hipMalloc((void**)&tb.lidx, sizeof(unsigned short) * tb.lidx_cap));
-    }
+    if (int rc_l = tb.grow_lidx(cells, cap)) return rc_l;
     if (int rc_lds = ensure_dyn_lds((const void*)k_kp_cell, lds)) return rc_lds;
     const float* d_key = d_diff;  // what the cells threshold and rank: the consistency map, or its ratio to the flow magnitude
     if (score_method == 1) {
-        if ((size_t)H * W > tb.ratio_cap) {
-            if (tb.ratio_map) (void)hipFree(tb.ratio_map);
-            tb.ratio_cap = (size_t)H * W;
-            DFVO_HIP_CHECK(hipMalloc((void**)&tb.ratio_map, sizeof(float) * tb.ratio_cap));
-        }
+        if (int rc_r = tb.grow_ratio_map(H, W)) return rc_r;
         hipLaunchKernelGGL(k_flow_ratio, dim3(cdiv(H * W, 256)), dim3(256), 0, s, d_flow, d_diff, H * W, tb.ratio_map);
         d_key = tb.ratio_map;
     }

@@ -651,46 +651,6 @@ __global__ void k_pnp_select(const PBatch B, PnpResult* __restrict__ res) {
 }
 
 // ================================================================================================
-int PnpBuffers::ensure(int n, int iters) {
-    if (n <= cap && iters <= iters_cap) return DFVO_OK;
-    release();
-    cap = n > cap ? n : cap;
-    iters_cap = iters > iters_cap ? iters : iters_cap;
-    const size_t c = (size_t)cap, it = (size_t)iters_cap;
-    DFVO_HIP_CHECK(hipMalloc((void**)&info, sizeof(int) * 4));
-    DFVO_HIP_CHECK(hipMalloc((void**)&fk1, sizeof(double) * 2 * c));
-    DFVO_HIP_CHECK(hipMalloc((void**)&fk2, sizeof(double) * 2 * c));
-    DFVO_HIP_CHECK(hipMalloc((void**)&xyz, sizeof(double) * 3 * c));
-    DFVO_HIP_CHECK(hipMalloc((void**)&perm, sizeof(int) * MAX_REP * (c + 8)));
-    DFVO_HIP_CHECK(hipMalloc((void**)&obj, sizeof(float) * MAX_REP * 3 * c));
-    DFVO_HIP_CHECK(hipMalloc((void**)&img, sizeof(float) * MAX_REP * 2 * c));
-    DFVO_HIP_CHECK(hipMalloc((void**)&state, sizeof(RansacState) * MAX_REP));
-    DFVO_HIP_CHECK(hipMalloc((void**)&idx, sizeof(int) * 5 * it));
-    DFVO_HIP_CHECK(hipMalloc((void**)&models, sizeof(double) * MAX_REP * 6 * it));
-    DFVO_HIP_CHECK(hipMalloc((void**)&nmodels, sizeof(int) * MAX_REP * it));
-    DFVO_HIP_CHECK(hipMalloc((void**)&counts, sizeof(int) * MAX_REP * it));
-    DFVO_HIP_CHECK(hipMalloc((void**)&mask, MAX_REP * c));
-    DFVO_HIP_CHECK(hipMalloc((void**)&keep, c));
-    DFVO_HIP_CHECK(hipMalloc((void**)&pts5, sizeof(float) * MAX_REP * 5 * c));
-    DFVO_HIP_CHECK(hipMalloc((void**)&rep_out, sizeof(PnpRepOut) * MAX_REP));
-    DFVO_HIP_CHECK(hipMalloc((void**)&result, sizeof(PnpResult)));
-    return DFVO_OK;
-}
-
-void PnpBuffers::release() {
-    void* ptrs[] = {info, fk1, fk2, xyz, perm, obj, img, state, idx, models, nmodels, counts, mask, keep, pts5, rep_out, result};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    info = perm = idx = nmodels = counts = nullptr;
-    fk1 = fk2 = xyz = models = nullptr;
-    obj = img = pts5 = nullptr;
-    state = nullptr;
-    mask = keep = nullptr;
-    rep_out = nullptr;
-    result = nullptr;
-    cap = iters_cap = 0;
-}
-
 // kp1 / kp2: device [n][2] doubles (n = *d_n when d_n != nullptr, else n_host); depth: device f64 [H][W].
 // Results: pb.result (PnpResult), pb.fk1 / pb.fk2 (filtered keypoints, pb.info[0] of them)
 int enqueue_compute_pose_3d2d(PnpBuffers& pb, uint32_t* mt_state, const double* d_kp1, const double* d_kp2,

@@ -446,7 +446,7 @@ int enqueue_pose_e_part(TrackerBuffers& tb, int n_host, const PoseConfig& cfg, h
         PoseFinish fin;
         fin.ps = tb.pose;
         fin.T21 = d_T21;
-        rc = enqueue_recover_pose(tb.ws_rep[0], (const double*)((const char*)tb.pose + offsetof(PoseState, best_E)),
+        rc = enqueue_recover_pose(tb.ws_rep[0], (const double*)((const char*)tb.pose.p + offsetof(PoseState, best_E)),
                                   tb.kp_cur, tb.kp_ref, n_host, cfg.fx, cfg.cx, cfg.cy, s, fin);
         if (rc != DFVO_OK) return rc;
         if (tb.ev_t[2]) DFVO_HIP_CHECK(hipEventRecord(tb.ev_t[2], s));

@@ -322,44 +322,6 @@ __global__ void k_e_mask(const EBatch B, int n, float thr2, int all_inliers) {
     mask[i] = (all_inliers || e <= thr2) ? 1 : 0;
 }
 
-int RansacWorkspace::ensure(int n, int max_iters) {
-    if (n <= cap_n && max_iters <= cap_iters) return DFVO_OK;
-    release();
-    cap_n = n > cap_n ? n : cap_n;
-    cap_iters = max_iters > cap_iters ? max_iters : cap_iters;
-    DFVO_HIP_CHECK(hipMalloc((void**)&state, sizeof(RansacState)));
-    DFVO_HIP_CHECK(hipMalloc((void**)&pts_a, sizeof(double) * 2 * cap_n));
-    DFVO_HIP_CHECK(hipMalloc((void**)&pts_b, sizeof(double) * 2 * cap_n));
-    DFVO_HIP_CHECK(hipMalloc((void**)&norm_a, sizeof(double) * 2 * cap_n));
-    DFVO_HIP_CHECK(hipMalloc((void**)&norm_b, sizeof(double) * 2 * cap_n));
-    DFVO_HIP_CHECK(hipMalloc((void**)&f_a, sizeof(float) * 2 * cap_n));
-    DFVO_HIP_CHECK(hipMalloc((void**)&f_b, sizeof(float) * 2 * cap_n));
-    DFVO_HIP_CHECK(hipMalloc((void**)&idx, sizeof(int) * 5 * cap_iters));
-    DFVO_HIP_CHECK(hipMalloc((void**)&ws, sizeof(double) * E_WS * cap_iters));
-    DFVO_HIP_CHECK(hipMalloc((void**)&ok, sizeof(int) * cap_iters));
-    DFVO_HIP_CHECK(hipMalloc((void**)&models, sizeof(double) * 90 * cap_iters));
-    DFVO_HIP_CHECK(hipMalloc((void**)&nmodels, sizeof(int) * cap_iters));
-    DFVO_HIP_CHECK(hipMalloc((void**)&counts, sizeof(int) * 10 * cap_iters));
-    DFVO_HIP_CHECK(hipMalloc((void**)&mask, cap_n));
-    DFVO_HIP_CHECK(hipMalloc((void**)&out, sizeof(double) * 64));
-    DFVO_HIP_CHECK(hipMalloc((void**)&lm, sizeof(double) * (size_t)(2 * cap_n) * 10 + 4096));
-    DFVO_HIP_CHECK(hipMalloc((void**)&cidx, sizeof(int) * (cap_n + 16)));
-    return DFVO_OK;
-}
-
-void RansacWorkspace::release() {
-    void* ptrs[] = {state, pts_a, pts_b, norm_a, norm_b, f_a, f_b, idx, ws, ok, models, nmodels, counts, mask, out, lm, cidx};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    state = nullptr;
-    pts_a = pts_b = norm_a = norm_b = nullptr;
-    f_a = f_b = nullptr;
-    idx = ok = nmodels = counts = cidx = nullptr;
-    ws = models = out = lm = nullptr;
-    mask = nullptr;
-    cap_n = cap_iters = 0;
-}
-
 
 // batch of `nrep` problems (workspaces w[r], inputs d_pts1[r]/d_pts2[r], all with n correspondences).
 // Results per problem: w[r].state (RansacState), w[r].out[0..8] = E, w[r].mask[n]

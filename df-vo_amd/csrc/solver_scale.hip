@@ -247,11 +247,7 @@ __global__ __launch_bounds__(256) void k_scale_ransac(uint32_t* __restrict__ mt_
 // tb.ev_rep[1]; enqueue_find_scale(prepared = true) then only waits for that event, so the two fills leave the
 // solver's chain of dependent launches
 int enqueue_scale_prepare(TrackerBuffers& tb, int H, int W) {
-    if ((size_t)H * W > tb.winner_cap) {
-        if (tb.winner) (void)hipFree(tb.winner);
-        tb.winner_cap = (size_t)H * W;
-        DFVO_HIP_CHECK(hipMalloc((void**)&tb.winner, sizeof(int) * tb.winner_cap));
-    }
+    if (int rc = tb.grow_winner(H, W)) return rc;
     hipStream_t side = tb.s_rep[1];
     DFVO_HIP_CHECK(hipMemsetAsync(tb.winner, 0xff, sizeof(int) * (size_t)H * W, side));
     DFVO_HIP_CHECK(hipMemsetAsync(tb.kp_total + KPT_SCALE_VALID, 0, sizeof(int), side));
@@ -289,14 +285,10 @@ int enqueue_find_scale(TrackerBuffers& tb, int n_host, const double* d_T21, cons
                        const ScaleConfig& cfg, hipStream_t s, const PoseState* d_gate, bool prepared, bool depth_per_kp) {
     DFVO_ARG_CHECK(n_host >= 0 && n_host <= tb.kp_cap, "find_scale: keypoint capacity");
     if (prepared) {
-        DFVO_ARG_CHECK((size_t)H * W <= tb.winner_cap, "find_scale: enqueue_scale_prepare was not called for this size");
+        DFVO_ARG_CHECK((size_t)H * W <= tb.winner.n, "find_scale: enqueue_scale_prepare was not called for this size");
         DFVO_HIP_CHECK(hipStreamWaitEvent(s, tb.ev_rep[1], 0));
     } else {
-        if ((size_t)H * W > tb.winner_cap) {
-            if (tb.winner) (void)hipFree(tb.winner);
-            tb.winner_cap = (size_t)H * W;
-            DFVO_HIP_CHECK(hipMalloc((void**)&tb.winner, sizeof(int) * tb.winner_cap));
-        }
+        if (int rc = tb.grow_winner(H, W)) return rc;
         DFVO_HIP_CHECK(hipMemsetAsync(tb.winner, 0xff, sizeof(int) * (size_t)H * W, s));
         DFVO_HIP_CHECK(hipMemsetAsync(tb.kp_total + KPT_SCALE_VALID, 0, sizeof(int), s));
     }

@@ -4,7 +4,7 @@
 //   solver_pose2d2d.hip         EssTracker.compute_pose_2d2d: GRIC, the repeated shuffled five-point RANSAC, bookkeeping
 //   solver_scale.hip            depth-ratio scale recovery (find_scale_from_depth)
 //   solver_trajectory.hip       update_global_pose over a gathered sequence
-//   solver_tracker_buffers.hip  lifetime of TrackerBuffers (host only)
+//   solver_buffers.hip          lifetime of every buffer set declared here and in solver.h (host only)
 // Sequential semantics that leak into the results (argpartition order, python-loop summation order, the global
 // np.random stream, last-writer-wins scatter) are kept by giving each sequential chain to one lane and spreading
 // independent chains over lanes / workgroups.  All solver_*.hip units are built with -ffp-contract=off.
@@ -107,18 +107,18 @@ struct PnpResult {
 };
 struct PnpBuffers {
     int cap = 0, iters_cap = 0;
-    int* info = nullptr;
-    double *fk1 = nullptr, *fk2 = nullptr, *xyz = nullptr;
-    int* perm = nullptr;
-    float *obj = nullptr, *img = nullptr;
-    RansacState* state = nullptr;
-    int* idx = nullptr;
-    double* models = nullptr;
-    int *nmodels = nullptr, *counts = nullptr;
-    uint8_t *mask = nullptr, *keep = nullptr;  // keep[i]: input keypoint i survived the filters
-    float* pts5 = nullptr;
-    PnpRepOut* rep_out = nullptr;
-    PnpResult* result = nullptr;
+    DevArr<int> info;
+    DevArr<double> fk1, fk2, xyz;
+    DevArr<int> perm;
+    DevArr<float> obj, img;
+    DevArr<RansacState> state;
+    DevArr<int> idx;
+    DevArr<double> models;
+    DevArr<int> nmodels, counts;
+    DevArr<uint8_t> mask, keep;  // keep[i]: input keypoint i survived the filters
+    DevArr<float> pts5;
+    DevArr<PnpRepOut> rep_out;
+    DevArr<PnpResult> result;
     int ensure(int n, int iters);
     void release();
 };
@@ -144,26 +144,27 @@ struct TrackerBuffers {
     int enable_stage_timing();
     int mark(int i, hipStream_t s);
     bool shared = false;  // streams / events / RandomState borrowed from another TrackerBuffers (see share_from)
-    uint32_t* mt_state = nullptr;  // numpy RandomState: key[624], pos
-    int* kp_info = nullptr;        // [n, good_kp_found, regions]
-    int* kp_total = nullptr;       // [KPT_SIZE], layout: KPT_* above
+    uint32_t* mt_state = nullptr;  // numpy RandomState: key[624], pos (mt_own's, or the first set's when `shared`)
+    DevArr<uint32_t> mt_own;
+    DevArr<int> kp_info;           // [n, good_kp_found, regions]
+    DevArr<int> kp_total;          // [KPT_SIZE], layout: KPT_* above
     int e_pre_iters = 0;  // > 0: enqueue_pose_h_part drew the five-point sampler's first chunk ahead, for this iteration budget
-    PoseState* pose = nullptr;
-    double* small = nullptr;       // [SMALL_SIZE], layout: SMALL_* above
+    DevArr<PoseState> pose;
+    DevArr<double> small;          // [SMALL_SIZE], layout: SMALL_* above
     double h_small[18] = {};       // host copy of the 18 intrinsics doubles held in `small` (uploaded only when they change)
     bool small_valid = false;
-    ScaleResult* scale_out = nullptr;
-    int* winner = nullptr;
-    size_t winner_cap = 0;
-    unsigned short* lidx = nullptr;
-    size_t lidx_cap = 0;
-    float* ratio_map = nullptr;  // flow_diff / |flow| per pixel (local_bestN score_method 'flow_ratio')
-    size_t ratio_cap = 0;
+    DevArr<ScaleResult> scale_out;
+    // grown on demand by the stages that use them
+    DevArr<int> winner;            // per pixel (the scale stage)
+    DevArr<unsigned short> lidx;   // cells x pixels of a cell (local_bestN)
+    DevArr<float> ratio_map;       // flow_diff / |flow| per pixel (local_bestN score_method 'flow_ratio')
+    int grow_winner(int H, int W) { return winner.grow((size_t)H * W); }
+    int grow_lidx(int cells, int cap) { return lidx.grow((size_t)cells * cap); }
+    int grow_ratio_map(int H, int W) { return ratio_map.grow((size_t)H * W); }
     // keypoint-sized buffers
-    double *kp_ref = nullptr, *kp_cur = nullptr, *pa = nullptr, *pb = nullptr, *res = nullptr, *z2 = nullptr,
-           *ratios = nullptr;
-    int *perm = nullptr, *cell_count = nullptr, *cell_sel = nullptr, *pix = nullptr, *scratch = nullptr;
-    uint8_t *best_inliers = nullptr, *inl_a = nullptr, *inl_b = nullptr;
+    DevArr<double> kp_ref, kp_cur, pa, pb, res, z2, ratios;
+    DevArr<int> perm, cell_count, cell_sel, pix, scratch;
+    DevArr<uint8_t> best_inliers, inl_a, inl_b;
     int kp_cap = 0, sel_cap = 0;
     // rep0 / rep1: side streams chosen by the caller (the fused pipeline hands out streams by dispatch pipe); null = create.
     // They may be the same stream.  borrowed: the caller keeps and destroys them -- they may then also be the stream the
@@ -189,11 +190,10 @@ int enqueue_local_bestn(TrackerBuffers& tb, const float* d_flow, const float* d_
                         int num_col, int num_bestN, float thre, hipStream_t s, int score_method = 0);
 // bestN_flow_kp (kp_selection.py:33-71): whole-image argpartition
 struct BestNBuffers {
-    float* key_base = nullptr;   // keys carried along with the index array, with slack on either side
-    int *tosort = nullptr, *map = nullptr, *Lpos = nullptr, *Rpos = nullptr, *count = nullptr;  // count[1] = result size
-    double* kp = nullptr;        // [kp1 | kp2], N x 2 doubles each
-    size_t cap = 0;
-    int kp_cap = 0;
+    DevArr<float> key_base;      // keys carried along with the index array, with slack on either side
+    DevArr<int> tosort, map, Lpos, Rpos, count;  // count[1] = result size
+    DevArr<double> kp;           // [kp1 | kp2], N x 2 doubles each
+    size_t cap = 0;              // pixels the six selection arrays hold (kp holds kp.n / 4 picks)
     int ensure(size_t px, int N);  // allocates (hipMalloc / hipFree: not for a per-pair path once the sizes are final)
     void release();
 };
@@ -210,11 +210,10 @@ struct RigidKpConfig {
     float K[9], Kinv[9], T[16];   // float32 intrinsics, their inverse, the ref -> cur motion (row-major)
 };
 struct RigidKpBuffers {
-    float *depth32 = nullptr, *rdiff = nullptr, *mats = nullptr;
-    int *cell_count = nullptr, *cell_sel = nullptr, *cell_sel_uni = nullptr, *info = nullptr, *zero = nullptr;
-    unsigned short* lidx = nullptr;
-    double* kp = nullptr;         // [4][sel_cap][2]: kp1 best, kp2 best, kp1 uniform, kp2 uniform
-    size_t px_cap = 0, lidx_cap = 0;
+    DevArr<float> depth32, rdiff, mats;  // depth32, rdiff: one float per pixel
+    DevArr<int> cell_count, cell_sel, cell_sel_uni, info, zero;
+    DevArr<unsigned short> lidx;
+    DevArr<double> kp;            // [4][sel_cap][2]: kp1 best, kp2 best, kp1 uniform, kp2 uniform
     int sel_cap = 0;
     int ensure(int H, int W, int cells, int n_best, int cap);
     void release();

@@ -558,3 +558,121 @@ def test_bestn_large_image_vs_oracle(gpu, trk):
                                       gpu.as_ptr(np.ascontiguousarray(diff[:10, :10, 0])), 10, 10, 100, gpu.as_ptr(kp1),
                                       gpu.as_ptr(kp2), C.byref(n)))
     assert n.value == 0
+
+
+def _fields(s):
+    """every field of a ctypes result struct as bytes (no padding), for byte-for-byte comparisons"""
+    return [(f[0], np.array(getattr(s, f[0])).tobytes()) for f in s._fields_]
+
+
+def test_results_do_not_depend_on_allocation_history(gpu):
+    """One fresh tracker handle, each entry point at a small size, then a large one, then the small one again, with the scale
+    stage and the PnP tracker in between: every buffer set (keypoint buffers, the RANSAC workspaces, the scale stage's pixel
+    map, the PnP buffers, the staging arrays) grows at least once while the others are live, and none shrinks.  Each result
+    meets the oracle by the criteria of the tests above (of tests/test_pnp_gpu.py for compute_pose_3d2d); the first and the
+    third call of an entry point agree byte for byte, the RandomState read back included."""
+    lib = gpu.lib()
+    trk = C.c_void_p()
+    gpu.check(lib.dfvo_tracker_create(None, C.byref(trk)))
+    try:
+        kp_refs, pose_refs = {}, {}
+
+        def bestn(h, w, seed, frac):
+            diff, flow = kp_case(h, w, seed, frac)
+            if seed not in kp_refs:
+                kp_refs[seed] = T.local_bestN(flow, diff)
+            ref = kp_refs[seed]
+            kp1, kp2 = np.zeros((2000, 2)), np.zeros((2000, 2))
+            n, good = C.c_int(), C.c_int()
+            gpu.check(lib.dfvo_kp_local_bestn(trk, gpu.as_ptr(np.ascontiguousarray(flow)), gpu.as_ptr(np.ascontiguousarray(diff[..., 0])),
+                                              h, w, 10, 10, 2000, 0.1, gpu.as_ptr(kp1), gpu.as_ptr(kp2), C.byref(n), C.byref(good)))
+            assert bool(good.value) == bool(ref["good_kp_found"])
+            if ref["good_kp_found"]:
+                assert n.value == ref["kp1_best"].shape[1]
+                assert np.array_equal(kp1[:n.value], ref["kp1_best"][0]) and np.array_equal(kp2[:n.value], ref["kp2_best"][0])
+            return n.value, good.value, kp1.tobytes(), kp2.tobytes()
+
+        def pose(seed, n, of, noise):
+            c = tracker_case(seed, n, of, noise)
+            K = c["K"]
+            np.random.seed(4869 + seed)
+            push_rng(gpu, trk)
+            if seed not in pose_refs:
+                pose_refs[seed] = (T.compute_pose_2d2d(c["kp_ref"], c["kp_cur"], K), np_state())
+            ref, state_ref = pose_refs[seed]
+            cfg = gpu.Pose2d2dCfg(fx=K[0, 0], cx=K[0, 2], cy=K[1, 2], reproj_thre=0.2, repeat=5, max_iters=1000)
+            KinvT, Kinv = np.linalg.inv(K.T), np.linalg.inv(K)
+            for i in range(9):
+                cfg.KinvT[i] = KinvT.flat[i]
+                cfg.Kinv[i] = Kinv.flat[i]
+            out = gpu.Pose2d2dOut()
+            inl = np.zeros(n, np.uint8)
+            gpu.check(lib.dfvo_compute_pose_2d2d(trk, gpu.as_ptr(c["kp_ref"]), gpu.as_ptr(c["kp_cur"]), n, C.byref(cfg), C.byref(out),
+                                                 gpu.as_ptr(inl)))
+            assert n > 10
+            assert list(out.rep_inliers[:5]) == ref["rep_inliers"]
+            assert [bool(v) for v in out.rep_valid[:5]] == ref["rep_valid"]
+            assert abs(out.h_gric - ref["h_gric"]) <= 1e-9 * abs(ref["h_gric"])
+            for a, b in zip(out.rep_gric[:5], ref["rep_gric"]):
+                assert abs(a - b) <= 1e-9 * abs(b)
+            assert out.cheirality == ref["cheirality"]
+            assert np.array_equal(inl == 1, ref["inliers"])
+            assert np.array_equal(np.array(out.R[:]).reshape(3, 3), ref["R"]) and np.array_equal(np.array(out.t[:]).reshape(3, 1), ref["t"])
+            state = pull_rng(gpu, trk)
+            assert np.array_equal(state, state_ref), "RandomState diverged after compute_pose_2d2d"
+            return _fields(out), inl.tobytes(), state.tobytes(), c, ref
+
+        small_kp, large_kp = (100, 130, 13, 0.02), (192, 640, 11, 0.6)
+        small_pose, large_pose = (53, 40, 0.1, 0.05), (33, 600, 0.2, 0.1)
+        kp_first = bestn(*small_kp)
+        pose_first = pose(*small_pose)[:3]
+        bestn(*large_kp)
+        # the scale stage on the large case's pose, as test_compute_pose_2d2d_and_scale runs it: the pixel map grows under live
+        # keypoint buffers of the small size, and the keypoint buffers with it
+        _, _, _, c, ref = pose(*large_pose)
+        K, n = c["K"], large_pose[1]
+        assert np.linalg.norm(ref["t"]) != 0
+        pose_mat = np.eye(4)
+        pose_mat[:3, :3] = ref["R"]
+        pose_mat[:3, 3:] = ref["t"]
+        T21 = np.ascontiguousarray(np.linalg.inv(pose_mat))
+        diag = {}
+        s_ref = T.find_scale_from_depth(c["kp_ref"], c["kp_cur"], T21, c["depth_cur"], K, diag=diag)
+        scfg = gpu.ScaleCfg(cx=K[0, 2], cy=K[1, 2], fx=K[0, 0], fy=K[1, 1], min_samples=3, max_trials=100, stop_prob=0.99, thre=0.1)
+        scale, info = C.c_double(), np.zeros(4, np.int32)
+        h, w = c["depth_cur"].shape
+        depth = np.ascontiguousarray(c["depth_cur"], dtype=np.float64)
+        gpu.check(lib.dfvo_find_scale_from_depth(trk, gpu.as_ptr(c["kp_ref"]), gpu.as_ptr(c["kp_cur"]), n, gpu.as_ptr(T21), gpu.as_ptr(depth),
+                                                 h, w, C.byref(scfg), C.byref(scale), gpu.as_ptr(info)))
+        assert info[0] == diag["n_valid"]
+        if s_ref == -1:
+            assert scale.value == -1
+        else:
+            assert info[1] == diag["n_trials"] and info[2] == diag["n_inliers"]
+            assert abs(scale.value - s_ref) <= 1e-12 * abs(s_ref)
+        assert np.array_equal(pull_rng(gpu, trk), np_state()), "RandomState diverged after scale recovery"
+        # the PnP tracker from the current frame back to the reference frame (the case carries the current frame's depth)
+        np.random.seed(4869)
+        push_rng(gpu, trk)
+        pref = T.compute_pose_3d2d(c["kp_cur"], c["kp_ref"], depth, K, 0.0, 50.0, 5, 100, 1.0)
+        pcfg = gpu.Pose3d2dCfg(fx=K[0, 0], fy=K[1, 1], cx=K[0, 2], cy=K[1, 2], min_depth=0.0, max_depth=50.0, repeat=5, iters=100,
+                               reproj_thre=1.0)
+        Kinv = np.linalg.inv(K)
+        for i in range(9):
+            pcfg.Kinv[i] = Kinv.flat[i]
+        pout, keep = gpu.Pose3d2dOut(), np.zeros(n, np.uint8)
+        gpu.check(lib.dfvo_compute_pose_3d2d(trk, gpu.as_ptr(c["kp_cur"]), gpu.as_ptr(c["kp_ref"]), n, gpu.as_ptr(depth), h, w,
+                                             C.byref(pcfg), C.byref(pout), gpu.as_ptr(keep)))
+        keep = keep.astype(bool)
+        print("pnp in between: filtered %d found %d inliers %d | oracle %d" % (pout.n_filtered, pout.found, pout.best_inliers, pref["best_inlier"]))
+        assert pout.n_filtered == len(pref["kp1"])
+        assert np.array_equal(c["kp_cur"][keep], pref["kp1"]) and np.array_equal(c["kp_ref"][keep], pref["kp2"])
+        assert pout.found == 1 and pout.best_inliers == pref["best_inlier"]
+        assert np.array_equal(np.array(pout.R[:]).reshape(3, 3), pref["R"])
+        assert np.array_equal(np.array(pout.tvec[:]).reshape(3, 1), pref["t"])
+        assert np.array_equal(pull_rng(gpu, trk), np_state())
+        # small again: what the first calls returned, byte for byte
+        assert bestn(*small_kp) == kp_first
+        assert pose(*small_pose)[:3] == pose_first
+    finally:
+        lib.dfvo_tracker_destroy(trk)
