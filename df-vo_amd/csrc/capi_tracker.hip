@@ -1,6 +1,7 @@
 // extern "C" surface, part 2: pose solvers with host arrays (see include/dfvo_hip.h).
 #include <vector>
 
+#include "kp_select.h"  // sm::kp_axis_cap
 #include "solver.h"
 #include "tracker.h"
 #include "capi_types.h"
@@ -342,7 +343,7 @@ int dfvo_kp_rigid_flow(dfvo_tracker* t, const float* h_flow, const float* h_flow
     DFVO_ARG_CHECK(rc.num_row > 0 && rc.num_col > 0, "dfvo_kp_rigid_flow: grid");
     const int cells = rc.num_row * rc.num_col;
     int rcode = t->rigid.ensure(H, W, cells, rc.num_bestN / cells > 0 ? rc.num_bestN / cells : 1,
-                                (H / rc.num_row + 2) * (W / rc.num_col + 2));
+                                sm::kp_axis_cap(H, rc.num_row) * sm::kp_axis_cap(W, rc.num_col));
     if (rcode != DFVO_OK) return rcode;
     hipStream_t s = t->stream;
     DFVO_HIP_CHECK(hipMemcpyAsync(t->d_flow, h_flow, sizeof(float) * 2 * px, hipMemcpyHostToDevice, s));

@@ -49,6 +49,14 @@ SM_HD int kp_median5(const float* v, IdxT* tosort) {
     return 2;
 }
 
+// Recursion cap (a deviation from numpy).  numpy's amedian_of_median5_ selects the median of the group medians with a
+// fresh introselect whenever there are more than two of them, and that call can exhaust its own depth limit and recurse
+// again: numpy puts no bound on the nesting.  On the device every level costs stack (112 bytes per lane on gfx950: 96 for
+// kp_introselect_cp_from, 16 for kp_introselect_cp), so kp_median_of_median5* stop selecting at `depth < 4` and take the
+// middle group's median as it stands: at most five levels, 560 bytes (the runtime's default per-lane limit is 1024).  The
+// order can differ from numpy's only on an input that reaches the capped level, which takes an adversary nested inside the
+// median sub-selection of the adversary against the outer selection, level after level; the tests construct level one
+// (tests/select_world.py) and no nested one.  See docs/parity.md, "introselect's recursion cap".
 template <typename IdxT>
 SM_HD_NOINLINE void kp_introselect(const float* v, IdxT* tosort, int num, int kth, int depth);
 
@@ -271,6 +279,20 @@ SM_HD void kp_cell_bounds(int h, int w, int num_row, int num_col, int row, int c
     *x0 = (int)((double)w / (double)num_col * (double)col);
     *y1 = (int)((double)h / (double)num_row * (double)(row + 1)) - 1;
     *x1 = (int)((double)w / (double)num_col * (double)(col + 1)) - 1;
+}
+
+// Rows (or columns) of the slice [a0:a1] of an axis of n pixels, as numpy takes it (kp_selection.py:133).  The end index
+// int(h / num_row * (row + 1)) - 1 is -1 for a cell less than one pixel high -- an image with fewer rows than the grid --
+// and a negative end counts from the back: such a cell is rows 0 .. n-2, not empty.
+SM_HD int kp_slice_len(int a0, int a1, int n) {
+    if (a1 < 0) a1 += n;
+    return a1 - a0 > 0 ? a1 - a0 : 0;
+}
+
+// upper bound of kp_slice_len over the cells of one axis: a regular cell has at most n / cells + 1 pixels, a wrapped one n - 1
+inline int kp_axis_cap(int n, int cells) {
+    const int regular = n / cells + 2;
+    return (n < cells && n - 1 > regular) ? n - 1 : regular;
 }
 
 }  // namespace sm

@@ -283,7 +283,7 @@ __global__ __launch_bounds__(256) void k_kp_cell(const float* __restrict__ diff,
     const int row = cell / num_col, col = cell - row * num_col;
     int y0, y1, x0, x1;
     sm::kp_cell_bounds(H, W, num_row, num_col, row, col, &y0, &y1, &x0, &x1);
-    const int th = y1 - y0 > 0 ? y1 - y0 : 0, tw = x1 - x0 > 0 ? x1 - x0 : 0;
+    const int th = sm::kp_slice_len(y0, y1, H), tw = sm::kp_slice_len(x0, x1, W);
     const int total = th * tw;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     if (t == 0) s_base = 0;
@@ -443,7 +443,7 @@ __global__ __launch_bounds__(256) void k_kp_cell_rigid(const float* __restrict__
     const int row = cell / num_col, col = cell - row * num_col;
     int y0, y1, x0, x1;
     sm::kp_cell_bounds(H, W, num_row, num_col, row, col, &y0, &y1, &x0, &x1);
-    const int th = y1 - y0 > 0 ? y1 - y0 : 0, tw = x1 - x0 > 0 ? x1 - x0 : 0;
+    const int th = sm::kp_slice_len(y0, y1, H), tw = sm::kp_slice_len(x0, x1, W);
     const int total = th * tw;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     if (t == 0) s_base = 0;
@@ -508,7 +508,7 @@ int enqueue_rigid_flow_kp(RigidKpBuffers& rb, const float* d_flow, const float* 
     DFVO_ARG_CHECK(cells > 0 && cells <= 1024 && H < 65536 && W < 65536, "rigid_flow_kp: grid too large");
     const int n_best = cfg.num_bestN / cells;
     DFVO_ARG_CHECK(n_best >= 1 && n_best <= 256, "rigid_flow_kp: n_best out of range");
-    const int cap = (H / cfg.num_row + 2) * (W / cfg.num_col + 2);
+    const int cap = sm::kp_axis_cap(H, cfg.num_row) * sm::kp_axis_cap(W, cfg.num_col);
     DFVO_ARG_CHECK(cap < 65536, "rigid_flow_kp: cell larger than 65535 pixels");
     size_t lds = (size_t)cap * (4 + 2) + 32;
     DFVO_ARG_CHECK(lds <= 158 * 1024, "rigid_flow_kp: cell does not fit in LDS");
@@ -597,7 +597,7 @@ int enqueue_local_bestn(TrackerBuffers& tb, const float* d_flow, const float* d_
     DFVO_ARG_CHECK(cells > 0 && cells <= 1024 && H < 65536 && W < 65536, "local_bestN: grid too large");
     const int n_best = num_bestN / cells;  // math.floor(N / (rows*cols))
     DFVO_ARG_CHECK(n_best >= 1 && n_best <= 256, "local_bestN: n_best out of range");
-    const int cap = (H / num_row + 2) * (W / num_col + 2);
+    const int cap = sm::kp_axis_cap(H, num_row) * sm::kp_axis_cap(W, num_col);
     DFVO_ARG_CHECK(cap < 65536, "local_bestN: cell larger than 65535 pixels");
     size_t lds = (size_t)cap * (4 + 2) + 32;
     DFVO_ARG_CHECK(lds <= 158 * 1024, "local_bestN: cell does not fit in LDS");

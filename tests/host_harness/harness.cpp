@@ -362,6 +362,23 @@ void hh_argpartition(const float* v, int num, int kth, int* tosort) {
 void hh_cell_bounds(int h, int w, int nr, int nc, int row, int col, int* out) {
     sm::kp_cell_bounds(h, w, nr, nc, row, col, out, out + 1, out + 2, out + 3);
 }
+// kp_cell_bounds, kp_slice_len and kp_axis_cap of every row of every grid with 1 .. max_rows rows on every side length
+// 1 .. max_h, for one vectorised comparison with Python's float arithmetic and slicing:
+// out[((h - 1) * max_rows + nr - 1) * max_rows + row] = {y0, y1, rows of the cell, the launchers' bound on them}, row < nr
+void hh_cell_bounds_sweep(int max_h, int max_rows, int* out) {
+    for (int h = 1; h <= max_h; h++)
+        for (int nr = 1; nr <= max_rows; nr++)
+            for (int row = 0; row < nr; row++) {
+                int b[4];
+                sm::kp_cell_bounds(h, h, nr, nr, row, row, b, b + 1, b + 2, b + 3);
+                int* o = out + 4 * (((size_t)(h - 1) * max_rows + (nr - 1)) * max_rows + row);
+                o[0] = b[0];
+                o[1] = b[1];
+                o[2] = sm::kp_slice_len(b[0], b[1], h);
+                o[3] = sm::kp_axis_cap(h, nr);
+                if (b[2] != b[0] || b[3] != b[1]) o[0] = o[1] = -12345;  // x and y bounds are the same expression
+            }
+}
 double hh_np_pairwise_sum(const double* a, int n) { return sm::np_pairwise_sum(a, n); }
 double hh_np_add_reduce(const double* a, int n) { return sm::np_add_reduce(a, n); }
 // k_rigid_flow_diff per pixel: mats = Kinv[9] | T[16] | K[9]; out [2][H][W] rigid flow
@@ -369,6 +386,16 @@ void hh_rigid_flow(const float* mats, const float* depth, int H, int W, float* o
     for (int i = 0; i < H * W; i++)
         sm::rigid_flow_px(mats, mats + 9, mats + 25, (float)(i % W), (float)(i / W), depth[i], out + i, out + (size_t)H * W + i);
 }
+}
+
+// ---- lock-step host emulation of kp_introselect_block (kp_block_lockstep.h); packed != 0: the 16-bit flavour of the LDS
+// kernels (num < 65536), else the int flavour of k_bestn_select.  Returns 0 when the emulation's whole (key, tosort) state
+// equals sm::kp_introselect_cp's; tosort / key receive the emulation's state.
+#include "kp_block_lockstep.h"
+extern "C" int hh_introselect_block_lockstep(const float* v, int num, int kth, int par_min, int packed, int* tosort, float* key) {
+    if (num <= 0) return 0;
+    return packed ? kp_lockstep::run_and_compare<unsigned short>(v, num, kth, par_min, tosort, key)
+                  : kp_lockstep::run_and_compare<int>(v, num, kth, par_min, tosort, key);
 }
 
 // ---- lock-step host emulation of df-vo_amd/csrc/solver_poly_lanes.h (one root per lane, sixteen lanes per row):

@@ -176,6 +176,90 @@ def test_argpartition_lane_matches_oracle(hh):
         assert np.array_equal(tos2, tos)
 
 
+def _inventory():
+    import select_world as S
+    for c in S.cases():
+        keys = np.ascontiguousarray(c[1], np.float32) if c[3] else S.rank_keys(c[1])  # raw keys keep their NaN / inf
+        yield c[0], keys, min(c[2], len(keys)) - 1
+
+
+def test_argpartition_lanes_on_the_case_inventory(hh):
+    """tests/select_world.py in full -- killers (depth limit exhausted: median of medians, recursive selection, ll-- / hh++),
+    sorted / sawtooth / organ-pipe / constant / two-valued keys with and without ties, +inf, -0.0, denormals, NaN, counts at
+    every switch: both scalar lanes against the C oracle on the WHOLE permutation"""
+    n_cases = 0
+    for name, keys, kth in _inventory():
+        n = len(keys)
+        want = T.argpartition_c(keys, kth)
+        tos, tos2 = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        hh.hh_argpartition(_p(keys, C.c_float), n, kth, _p(tos, C.c_int))
+        hh.hh_argpartition_cp(_p(keys, C.c_float), n, kth, _p(tos2, C.c_int))
+        assert np.array_equal(tos, want), name
+        assert np.array_equal(tos2, want), name
+        n_cases += 1
+    assert n_cases > 1000
+
+
+def test_workgroup_partition_lockstep_matches_oracle(hh):
+    """kp_introselect_block restated in lock step (tests/host_harness/kp_block_lockstep.h; tests/test_kp_select_cpu.py runs
+    it under the sanitizers): whole permutation and permuted keys against the C oracle, 16-bit packed scan and int scans, at
+    the real switch of 256 and with the parallel passes taken down to ranges of 6"""
+    hh.hh_introselect_block_lockstep.restype = C.c_int
+    n_par = 0
+    for name, keys, kth in _inventory():
+        n = len(keys)
+        want = T.argpartition_c(keys, kth)
+        for par_min in (256, 6):
+            for packed in (1, 0):
+                tos, key = np.zeros(n, np.int32), np.zeros(n, np.float32)
+                rc = hh.hh_introselect_block_lockstep(_p(keys, C.c_float), n, kth, par_min, packed, _p(tos, C.c_int), _p(key, C.c_float))
+                assert rc == 0, (name, par_min, packed)
+                assert np.array_equal(tos, want), (name, par_min, packed)
+                assert np.array_equal(key.view(np.uint32), keys[want].view(np.uint32)), (name, par_min, packed)
+        n_par += n >= 256 and 3 <= kth < n - 1
+    assert n_par > 100
+
+
+def test_cell_bounds_match_python_float_arithmetic(hh):
+    """sm::kp_cell_bounds against the reference's expressions int(h / num_row * row), int(h / num_row * (row + 1)) - 1
+    evaluated by numpy in float64 (IEEE division and product, truncation: what Python's float arithmetic and int() do),
+    every side 1 .. 2048 x every grid 1 .. 32 x every row.  0 <= y0 and y1 <= h; the rows of a cell (sm::kp_slice_len) are
+    those of the Python slice [y0:y1] -- an end of -1, which a side shorter than the grid produces, counts from the back --
+    and never more than the bound the launchers size LDS and scratch with (sm::kp_axis_cap)."""
+    max_h, max_rows = 2048, 32
+    out = np.full((max_h, max_rows, max_rows, 4), -1, np.int32)
+    hh.hh_cell_bounds_sweep(max_h, max_rows, _p(out, C.c_int))
+    h = np.arange(1, max_h + 1, dtype=np.float64)[:, None, None]
+    nr = np.arange(1, max_rows + 1, dtype=np.float64)[None, :, None]
+    row = np.arange(max_rows, dtype=np.float64)[None, None, :]
+    valid = np.broadcast_to(row < nr, out.shape[:3])
+    y0 = np.trunc(h / nr * row).astype(np.int64)
+    y1 = np.trunc(h / nr * (row + 1)).astype(np.int64) - 1
+    n_wrapped = 0
+    for hi in list(range(1, 41)) + [376, 1241, 2048]:  # numpy's arithmetic is Python's, the slice lengths are Python's
+        for ni in range(1, max_rows + 1):
+            for ri in range(ni):
+                a0, a1 = int(hi / ni * ri), int(hi / ni * (ri + 1)) - 1
+                assert (y0[hi - 1, ni - 1, ri], y1[hi - 1, ni - 1, ri]) == (a0, a1)
+                assert out[hi - 1, ni - 1, ri, 2] == len(range(hi)[a0:a1]), (hi, ni, ri)
+                n_wrapped += a1 < 0 and hi > 1
+    assert n_wrapped > 100
+    assert np.array_equal(out[..., 0][valid], y0[valid]) and np.array_equal(out[..., 1][valid], y1[valid])
+    assert (out[..., 0][valid] >= 0).all()
+    assert (out[..., 1][valid] <= np.broadcast_to(h, valid.shape)[valid]).all()
+    hb = np.broadcast_to(h, valid.shape).astype(np.int64)
+    side = np.maximum(np.where(y1 < 0, y1 + hb, y1) - y0, 0)
+    assert np.array_equal(out[..., 2][valid], side[valid])
+    assert (out[..., 2][valid] <= out[..., 3][valid]).all()
+    regular = np.broadcast_to(np.floor_divide(h, nr) + 2, valid.shape)  # H / num_row + 2 wherever the side covers the grid
+    assert np.array_equal(out[..., 3][valid & (hb >= nr)], regular[valid & (hb >= nr)])
+    # spot checks through the single-cell export, rows and columns at once
+    b = np.zeros(4, np.int32)
+    for hh_, ww, nrr, ncc, r, c in ((120, 160, 3, 4, 2, 3), (300, 320, 2, 2, 1, 0), (5, 97, 7, 3, 6, 2), (1, 1, 1, 1, 0, 0)):
+        hh.hh_cell_bounds(hh_, ww, nrr, ncc, r, c, _p(b, C.c_int))
+        assert b.tolist() == [int(hh_ / nrr * r), int(hh_ / nrr * (r + 1)) - 1, int(ww / ncc * c), int(ww / ncc * (c + 1)) - 1]
+
+
 def test_pairwise_sum_lane_matches_numpy(hh):
     """np.add.reduce's pairwise summation (the mean displacement of validity.method 'flow'), every size class: below 8,
     up to the 128-element block, and the recursive split, with magnitudes spread so that the order matters"""

@@ -43,6 +43,51 @@ np.save(sys.argv[1], np.concatenate(out))
         if n < 1500:
             assert np.array_equal(T.argpartition_scalar(v, k - 1)[:k], got_c[-1])
     assert np.array_equal(np.concatenate(got_c), want)
+    # adversarial and structured keys (tests/select_world.py): every killer, and the structured / special sequences at
+    # three counts, NaN and inf left in.  numpy itself on the first kth + 1 indices, the two restatements on the whole
+    # permutation -- through the median-of-medians branch, which white noise never enters.
+    import select_world as S
+    picked = [c for c in S.cases() if c[0].startswith("killer") or len(c[1]) in (21, 257, 1000)]
+    assert sum(c[0].startswith("killer") for c in picked) == len(S.KILLERS) + len(S.KILLERS_DISTINCT)
+    keys = [np.asarray(c[1], np.float32) if c[3] else S.rank_keys(c[1]) for c in picked]
+    kths = [min(c[2], len(c[1])) - 1 for c in picked]
+    np.savez(str(tmp_path / "in.npz"), kth=np.asarray(kths), **{"k%d" % i: k for i, k in enumerate(keys)})
+    code2 = r"""
+import numpy as np, sys
+g = np.load(sys.argv[1])
+kth = g["kth"]
+np.save(sys.argv[2], np.concatenate([np.argpartition(g["k%d" % i], kth[i])[:kth[i] + 1] for i in range(len(kth))]))
+"""
+    path2 = str(tmp_path / "np_scalar_order2.npy")
+    subprocess.check_call([sys.executable, "-c", code2, str(tmp_path / "in.npz"), path2], env=env)
+    want2 = np.load(path2)
+    at = 0
+    for c, k, kth in zip(picked, keys, kths):
+        full_c = T.argpartition_c(k, kth)
+        before = T.FALLBACK_ENTRIES[0]
+        full_py = T.argpartition_scalar(k, kth)
+        entries = T.FALLBACK_ENTRIES[0] - before
+        assert np.array_equal(full_c, full_py), c[0]
+        assert np.array_equal(full_c[:kth + 1], want2[at:at + kth + 1]), c[0]
+        at += kth + 1
+        if c[0].startswith("killer"):
+            assert entries >= 1, "%s does not reach the median-of-medians branch" % c[0]
+    assert at == len(want2)
+
+
+def test_killers_enter_the_median_of_medians_branch():
+    """the inputs do what they claim: the pure-Python restatement counts its entries into the fallback, >= 1 for every
+    killer (select_world.killer asserts it too), 0 for white noise of the same sizes"""
+    import select_world as S
+    for num, kth in S.KILLERS:
+        assert S.killer_entries(num, kth) >= 1, (num, kth)
+    for num, kth in S.KILLERS_DISTINCT:
+        assert S.killer_entries(num, kth, True) >= 1, (num, kth)
+    rng = np.random.default_rng(9)
+    before = T.FALLBACK_ENTRIES[0]
+    for num, kth in S.KILLERS[:8]:
+        T.argpartition_scalar(rng.random(num).astype(np.float32), kth)
+    assert T.FALLBACK_ENTRIES[0] == before
 
 
 def test_local_bestN_matches_reference_fixture():
