@@ -13,6 +13,8 @@ from . import LIB_PATH
 
 PUSH_NO_FLOW = 1   # dfvo_session_push_frame flags (include/dfvo_hip.h)
 ERR_RANGE = -4     # DFVO_ERR_RANGE: an activation left f16's range under an f16x3 / f16 packing
+ERR_EMPTY_SELECTION = -5  # dfvo_scale_recovery_iterative: the reference's "sampling threshold is too small." assertion
+ERR_NO_CONSENSUS = -6     # dfvo_scale_recovery_iterative: sklearn's "could not find a valid consensus set"
 
 
 class DfvoError(RuntimeError):
@@ -45,6 +47,12 @@ class ScaleCfg(C.Structure):
     _fields_ = [("cx", C.c_double), ("cy", C.c_double), ("fx", C.c_double), ("fy", C.c_double),
                 ("min_samples", C.c_int), ("max_trials", C.c_int), ("stop_prob", C.c_double), ("thre", C.c_double),
                 ("method", C.c_int)]
+
+
+class ScaleIterOut(C.Structure):
+    _fields_ = [("scale", C.c_double), ("n_iter", C.c_int), ("n_kp", C.c_int), ("kp_round", C.c_int), ("status", C.c_int),
+                ("scale_in", C.c_double * 5), ("scale_out", C.c_double * 5), ("n_kp_round", C.c_int * 5),
+                ("device_ms", C.c_float)]
 
 
 class Pose3d2dCfg(C.Structure):
@@ -236,6 +244,8 @@ SIGNATURES = {
     "dfvo_find_scale_from_depth_at_kp": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, C.POINTER(ScaleCfg), _vp, C.POINTER(_d), _vp]),
     "dfvo_compute_pose_3d2d": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, C.POINTER(Pose3d2dCfg), C.POINTER(Pose3d2dOut), _vp]),
     "dfvo_compute_pose_3d2d_at_kp": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, C.POINTER(Pose3d2dCfg), _vp, C.POINTER(Pose3d2dOut), _vp]),
+    "dfvo_scale_recovery_iterative": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(RigidKpCfg), C.POINTER(ScaleCfg), _vp, _vp, _d,
+                                           _i, _vp, _vp, _i, _vp, C.POINTER(ScaleIterOut), _vp, _vp, _vp]),
     "dfvo_ransac_regressor": (_i, [_vp, _vp, _vp, _i, C.POINTER(ScaleCfg), C.POINTER(_d), _vp]),
 }
 

@@ -1,4 +1,6 @@
 // extern "C" surface, part 2: pose solvers with host arrays (see include/dfvo_hip.h).
+#include <string.h>
+
 #include <vector>
 
 #include "kp_select.h"  // sm::kp_axis_cap
@@ -114,6 +116,8 @@ void dfvo_tracker_destroy(dfvo_tracker* t) {
     t->pnp.release();
     t->rigid.release();
     t->bestn.release();
+    for (hipEvent_t e : t->ev_iter)
+        if (e) (void)hipEventDestroy(e);
     if (t->own_stream && t->stream) (void)hipStreamDestroy(t->stream);
     delete t;  // (the staging arrays and the buffer sets' memory are DevArr members)
 }
@@ -458,6 +462,133 @@ int dfvo_find_scale_from_depth_at_kp(dfvo_tracker* t, const double* h_kp1, const
                                      const double* h_depth_at_kp2, int H, int W, const dfvo_scale_cfg* cfg,
                                      uint32_t* h_rng625, double* scale, int* h_info) {
     return find_scale_impl(t, h_kp1, h_kp2, n, h_T21, h_depth_at_kp2, true, H, W, cfg, h_rng625, scale, h_info);
+}
+
+static int rigid_config_from(const dfvo_rigid_kp_cfg* cfg, RigidKpConfig* out) {
+    RigidKpConfig& rc = *out;
+    rc.num_row = cfg->num_row;
+    rc.num_col = cfg->num_col;
+    rc.num_bestN = cfg->num_bestN;
+    rc.rigid_thre = (float)cfg->rigid_flow_thre;
+    rc.opt_thre = (float)cfg->optical_flow_thre;
+    rc.score_rigid = cfg->score_method;
+    for (int i = 0; i < 9; i++) {
+        rc.K[i] = (float)cfg->K[i];
+        rc.Kinv[i] = (float)cfg->Kinv[i];
+    }
+    for (int i = 0; i < 16; i++) rc.T[i] = (float)cfg->T_ref_to_cur[i];
+    return DFVO_OK;
+}
+
+int dfvo_scale_recovery_iterative(dfvo_tracker* t, const float* h_flow, const float* h_flow_diff, const float* h_raw_depth_ref,
+                                  const double* h_depth_cur, int H, int W, const dfvo_rigid_kp_cfg* cfg,
+                                  const dfvo_scale_cfg* scfg, const double* h_E_pose, const double* h_T21, double prev_scale,
+                                  int kp_src, const double* h_kp_best_ref, const double* h_kp_best_cur, int n_kp_best,
+                                  uint32_t* h_rng625, dfvo_scale_iter_out* out, double* h_kp_ref, double* h_kp_cur,
+                                  float* h_rigid_flow_diff) {
+    DFVO_ARG_CHECK(t && h_flow && h_flow_diff && h_raw_depth_ref && h_depth_cur && cfg && scfg && h_E_pose && h_rng625 && out &&
+                       h_kp_ref && h_kp_cur && H > 0 && W > 0,
+                   "dfvo_scale_recovery_iterative: bad argument");
+    DFVO_ARG_CHECK(cfg->score_method == 0 || cfg->score_method == 1, "dfvo_scale_recovery_iterative: score_method");
+    DFVO_ARG_CHECK(kp_src == DFVO_ITER_KP_DEPTH || kp_src == DFVO_ITER_KP_BEST, "dfvo_scale_recovery_iterative: unknown kp_src");
+    DFVO_ARG_CHECK(kp_src == DFVO_ITER_KP_DEPTH || (h_kp_best_ref && h_kp_best_cur && n_kp_best >= 0),
+                   "dfvo_scale_recovery_iterative: kp_src DFVO_ITER_KP_BEST needs the keypoint pair");
+    DFVO_ARG_CHECK(scfg->min_samples >= 1 && scfg->min_samples <= 8, "dfvo_scale_recovery_iterative: min_samples in [1,8]");
+    DFVO_ARG_CHECK(scfg->method == DFVO_SCALE_DEPTH_RATIO || scfg->method == DFVO_SCALE_ABS_DIFF,
+                   "dfvo_scale_recovery_iterative: unknown scale method");
+    RigidKpConfig rc;
+    rigid_config_from(cfg, &rc);
+    DFVO_ARG_CHECK(rc.num_row > 0 && rc.num_col > 0, "dfvo_scale_recovery_iterative: grid");
+    int cells, n_best, cap, par;
+    size_t lds;
+    if (int rc_g = rigid_flow_kp_geometry(H, W, rc, &cells, &n_best, &cap, &lds, &par)) return rc_g;  // the launcher's refusals
+    (void)lds, (void)par;
+    const int n_sel = cells * n_best;
+    DFVO_ARG_CHECK((kp_src == DFVO_ITER_KP_DEPTH ? n_sel : n_kp_best) <= ITER_MAX_KP,
+                   "dfvo_scale_recovery_iterative: more keypoints than the depth-ratio kernel holds in 64 KB of LDS (16384)");
+    ScaleConfig sc;
+    sc.cx = scfg->cx, sc.cy = scfg->cy, sc.fx = scfg->fx, sc.fy = scfg->fy;
+    sc.min_samples = scfg->min_samples, sc.max_trials = scfg->max_trials;
+    sc.stop_prob = scfg->stop_prob, sc.thre = scfg->thre, sc.method = scfg->method;
+    const size_t px = (size_t)H * W;
+    if (int rc_f = stage_flow(t, px)) return rc_f;
+    if (int rc_d = stage_depth(t, px)) return rc_d;
+    if (int rc_e = t->rigid.ensure(H, W, cells, n_best, cap)) return rc_e;
+    // results: IterCtl | 625 RandomState words | uniform keypoints kp1 [sel_cap][2], kp2 [sel_cap][2]
+    const size_t off_rng = (sizeof(IterCtl) + 7) & ~(size_t)7, off_kp = off_rng + 632 * sizeof(uint32_t);
+    const size_t kp_doubles = 4 * (size_t)t->rigid.sel_cap;
+    if (int rc_p = t->h_iter.grow(off_kp + sizeof(double) * kp_doubles)) return rc_p;
+    hipStream_t s = t->stream;
+    if (kp_src == DFVO_ITER_KP_BEST) {  // tb.kp_ref / kp_cur / kp_info
+        if (int rc_k = stage_kp(t, h_kp_best_ref, h_kp_best_cur, n_kp_best)) return rc_k;
+    }
+    double pose[32];
+    for (int i = 0; i < 16; i++) pose[i] = h_E_pose[i];
+    if (h_T21) {
+        for (int i = 0; i < 16; i++) pose[16 + i] = h_T21[i];
+    } else {
+        for (int r = 0; r < 3; r++) {
+            const double a = h_E_pose[r], b = h_E_pose[4 + r], c = h_E_pose[8 + r];
+            pose[16 + r * 4] = a, pose[16 + r * 4 + 1] = b, pose[16 + r * 4 + 2] = c;
+            pose[16 + r * 4 + 3] = -(a * h_E_pose[3] + b * h_E_pose[7] + c * h_E_pose[11]);
+        }
+        pose[28] = pose[29] = pose[30] = 0.0, pose[31] = 1.0;
+    }
+    DFVO_HIP_CHECK(hipMemcpyAsync(t->d_small, pose, sizeof(pose), hipMemcpyHostToDevice, s));
+    DFVO_HIP_CHECK(hipStreamSynchronize(s));  // `pose` is a stack buffer (before anything of the loop is enqueued)
+    DFVO_HIP_CHECK(hipMemcpyAsync(t->tb.mt_state, h_rng625, 625 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    DFVO_HIP_CHECK(hipMemcpyAsync(t->d_flow, h_flow, sizeof(float) * 2 * px, hipMemcpyHostToDevice, s));
+    DFVO_HIP_CHECK(hipMemcpyAsync(t->d_diff, h_flow_diff, sizeof(float) * px, hipMemcpyHostToDevice, s));
+    DFVO_HIP_CHECK(hipMemcpyAsync(t->rigid.depth32, h_raw_depth_ref, sizeof(float) * px, hipMemcpyHostToDevice, s));
+    DFVO_HIP_CHECK(hipMemcpyAsync(t->d_depth, h_depth_cur, sizeof(double) * px, hipMemcpyHostToDevice, s));
+    for (hipEvent_t& e : t->ev_iter)
+        if (!e) DFVO_HIP_CHECK(hipEventCreate(&e));
+    DFVO_HIP_CHECK(hipEventRecord(t->ev_iter[0], s));
+    int rcode = enqueue_scale_recovery_iterative(t->tb, t->rigid, t->d_flow, t->d_diff, t->rigid.depth32, t->d_depth, H, W, rc, sc,
+                                                 t->d_small, t->d_small + 16, prev_scale, kp_src, n_kp_best, s);
+    if (rcode != DFVO_OK) {
+        (void)hipStreamSynchronize(s);  // the uploads read the caller's arrays
+        return rcode;
+    }
+    DFVO_HIP_CHECK(hipEventRecord(t->ev_iter[1], s));
+    unsigned char* hp = t->h_iter;
+    DFVO_HIP_CHECK(hipMemcpyAsync(hp, t->rigid.ctl, sizeof(IterCtl), hipMemcpyDeviceToHost, s));
+    DFVO_HIP_CHECK(hipMemcpyAsync(hp + off_rng, t->tb.mt_state, 625 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    DFVO_HIP_CHECK(hipMemcpyAsync(hp + off_kp, t->rigid.kp + kp_doubles, sizeof(double) * kp_doubles, hipMemcpyDeviceToHost, s));
+    DFVO_HIP_CHECK(hipStreamSynchronize(s));
+    IterCtl ctl;
+    memcpy(&ctl, hp, sizeof(ctl));
+    if (ctl.status == ITER_EMPTY && ctl.sel_round < 0) {
+        set_last_error("dfvo_scale_recovery_iterative: sampling threshold is too small (no rigid-flow keypoint selected)");
+        return DFVO_ERR_EMPTY_SELECTION;
+    }
+    const int n = ctl.n_kp[ctl.sel_round];
+    out->scale = ctl.scale;
+    out->n_iter = ctl.n_iter;
+    out->n_kp = n;
+    out->kp_round = ctl.sel_round;
+    out->status = ctl.status;
+    out->device_ms = 0.f;
+    (void)hipEventElapsedTime(&out->device_ms, t->ev_iter[0], t->ev_iter[1]);
+    for (int r = 0; r < ITER_ROUNDS; r++) {
+        out->scale_in[r] = ctl.scale_in[r];
+        out->scale_out[r] = ctl.scale_out[r];
+        out->n_kp_round[r] = ctl.n_kp[r];
+    }
+    memcpy(h_rng625, hp + off_rng, 625 * sizeof(uint32_t));
+    memcpy(h_kp_ref, hp + off_kp, sizeof(double) * 2 * (size_t)n);
+    memcpy(h_kp_cur, hp + off_kp + sizeof(double) * 2 * (size_t)t->rigid.sel_cap, sizeof(double) * 2 * (size_t)n);
+    if (h_rigid_flow_diff)
+        DFVO_HIP_CHECK(hipMemcpy(h_rigid_flow_diff, t->rigid.rdiff_of(ctl.sel_round, H, W), sizeof(float) * px, hipMemcpyDeviceToHost));
+    if (ctl.status == ITER_EMPTY) {
+        set_last_error("dfvo_scale_recovery_iterative: sampling threshold is too small (no rigid-flow keypoint selected)");
+        return DFVO_ERR_EMPTY_SELECTION;
+    }
+    if (ctl.status == ITER_NO_CONSENSUS) {
+        set_last_error("dfvo_scale_recovery_iterative: RANSAC could not find a valid consensus set");
+        return DFVO_ERR_NO_CONSENSUS;
+    }
+    return DFVO_OK;
 }
 
 int dfvo_ransac_regressor(dfvo_tracker* t, const double* h_x, const double* h_y, int n, const dfvo_scale_cfg* cfg,

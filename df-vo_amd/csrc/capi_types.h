@@ -28,6 +28,8 @@ struct dfvo_tracker {
     dfvo::DevArr<double> d_depth;
     dfvo::DevArr<double> d_small;        // 64 doubles
     dfvo::DevArr<double> d_x1, d_x2, d_X4;
+    hipEvent_t ev_iter[2] = {nullptr, nullptr};  // around the rounds of dfvo_scale_recovery_iterative (created on first use)
+    dfvo::PinnedArr<unsigned char> h_iter;  // results of dfvo_scale_recovery_iterative: IterCtl | RandomState | keypoints
     dfvo::PnpBuffers pnp;
 };
 

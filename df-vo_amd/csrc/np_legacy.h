@@ -173,4 +173,21 @@ SM_HD void rigid_flow_px(const float* Ki, const float* T, const float* K, float 
     *rx = U[0] / den - x;
     *ry = U[1] / den - y;
 }
+
+// scale_recovery_iterative's rigid_flow_pose (E_tracker.py:528-531): inv([R | t * scale]) of the 4x4 row-major E, rounded to
+// the float32 the RigidFlow layer runs in.  The closed form [R^T | -R^T (t * scale)] in float64, plain multiply / add order
+// (built with -ffp-contract=off): after the cast it equals np.linalg.inv(...).astype(float32) on every pose of
+// tests/test_iter_pose_cpu.py.  The last row is copied like the LU inverse leaves it for a rigid pose: 0 0 0 1.
+SM_HD void rigid_pose_inv_f32(const double* E, double scale, float* T /*16*/) {
+    const double tx = E[3] * scale, ty = E[7] * scale, tz = E[11] * scale;
+    for (int r = 0; r < 3; ++r) {
+        const double a = E[r], b = E[4 + r], c = E[8 + r];  // row r of R^T
+        T[r * 4] = (float)a;
+        T[r * 4 + 1] = (float)b;
+        T[r * 4 + 2] = (float)c;
+        T[r * 4 + 3] = (float)(-(a * tx + b * ty + c * tz));
+    }
+    T[12] = T[13] = T[14] = 0.0f;
+    T[15] = 1.0f;
+}
 }  // namespace sm

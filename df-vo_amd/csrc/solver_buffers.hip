@@ -83,10 +83,10 @@ int RigidKpBuffers::ensure(int H, int W, int cells, int n_best, int cap) {
     int rc = DFVO_OK;
     if (px > depth32.n) {
         rdiff.release();
-        rc = depth32.alloc(px) || rdiff.alloc(px) ? DFVO_ERR_HIP : DFVO_OK;
+        rc = depth32.alloc(px) || rdiff.alloc(2 * px) ? DFVO_ERR_HIP : DFVO_OK;
     }
     if (!rc && !mats) {
-        if (mats.alloc(40) || cell_count.alloc(1024) || info.alloc(8) || zero.alloc(2))
+        if (mats.alloc(40) || ctl.alloc(1) || cell_count.alloc(1024) || info.alloc(8) || zero.alloc(2))
             rc = DFVO_ERR_HIP;
         else if (hipError_t e = hipMemset(zero, 0, sizeof(int) * 2)) {
             set_last_error(std::string("RigidKpBuffers::ensure: hipMemset: ") + hipGetErrorString(e));
@@ -105,7 +105,7 @@ int RigidKpBuffers::ensure(int H, int W, int cells, int n_best, int cap) {
 
 void RigidKpBuffers::release() {
     for (DevArr<int>* a : {&cell_count, &cell_sel, &cell_sel_uni, &info, &zero}) a->release();
-    depth32.release(), rdiff.release(), mats.release(), lidx.release(), kp.release();
+    depth32.release(), rdiff.release(), mats.release(), ctl.release(), lidx.release(), kp.release();
     sel_cap = 0;
 }
 

@@ -357,8 +357,10 @@ __global__ __launch_bounds__(256) void k_kp_gather(const int* __restrict__ cell_
                                                     const int* __restrict__ total_good, const int* __restrict__ count_partial,
                                                     int min_total, int min_regions,
                                                     double* __restrict__ kp1, double* __restrict__ kp2,
-                                                    int* __restrict__ info /*[n, good_kp_found, regions]*/) {
+                                                    int* __restrict__ info /*[n, good_kp_found, regions]*/,
+                                                    const int* __restrict__ skip) {
     __shared__ int s_off[1025], s_cnt[1024], s_good;
+    if (skip && *skip) return;  // (the iterative scale loop's rounds behind its last one)
     const int t = threadIdx.x;
     for (int c = t; c < cells; c += 256) s_cnt[c] = cell_count[c];
     __syncthreads();
@@ -409,7 +411,8 @@ __global__ __launch_bounds__(256) void k_kp_gather(const int* __restrict__ cell_
 // torch-CPU oracle.  Kinv: 3x3, T: 4x4, K: 3x3 (its 4th column in the reference is zero).
 __global__ void k_rigid_flow_diff(const float* __restrict__ depth, const float* __restrict__ flow, int H, int W,
                                   const float* __restrict__ mats /*Kinv[9] | T[16] | K[9]*/, float* __restrict__ rdiff,
-                                  float* __restrict__ rflow /*optional [2,H,W]*/) {
+                                  float* __restrict__ rflow /*optional [2,H,W]*/, const int* __restrict__ skip) {
+    if (skip && *skip) return;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= H * W) return;
     const float x = (float)(i % W), y = (float)(i / W);
@@ -425,12 +428,15 @@ __global__ void k_rigid_flow_diff(const float* __restrict__ depth, const float* 
 
 // opt_rigid_flow_kp (kp_selection.py:203-324), one workgroup per grid cell: candidates = pixels of the cell (last row /
 // column dropped) with rigid-flow distance < thr_r AND forward-backward distance < thr_o, in row-major order;
-// "uniform" picks every step-th candidate, "best" the num_to_pick smallest scores in numpy's argpartition order
+// "uniform" picks every step-th candidate, "best" the num_to_pick smallest scores in numpy's argpartition order.
+// uniform_only: the selection of the "best" set is left out and cell_sel is not written (scale_recovery_iterative reads the
+// uniform set alone, E_tracker.py:541-542; the two sets have the same count per cell)
 __global__ __launch_bounds__(256) void k_kp_cell_rigid(const float* __restrict__ odiff, const float* __restrict__ rdiff,
                                                         int H, int W, int num_row, int num_col, float thr_o, float thr_r,
                                                         int score_rigid, int n_best, int cap, int* __restrict__ cell_count,
                                                         int* __restrict__ cell_sel, int* __restrict__ cell_sel_uni,
-                                                        unsigned short* __restrict__ lidx_all, int par) {
+                                                        unsigned short* __restrict__ lidx_all, int par, int uniform_only,
+                                                        const int* __restrict__ skip) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float* vals = reinterpret_cast<float*>(smem_raw) + 4;
     unsigned short* tosort = reinterpret_cast<unsigned short*>(vals + cap + 4);
@@ -439,6 +445,7 @@ __global__ __launch_bounds__(256) void k_kp_cell_rigid(const float* __restrict__
     __shared__ int s_ctl[8], s_wsum[4];
     unsigned short* lidx = lidx_all + (size_t)blockIdx.x * cap;
     __shared__ int s_base, s_wave[4];
+    if (skip && *skip) return;
     const int cell = blockIdx.x;
     const int row = cell / num_col, col = cell - row * num_col;
     int y0, y1, x0, x1;
@@ -484,13 +491,15 @@ __global__ __launch_bounds__(256) void k_kp_cell_rigid(const float* __restrict__
             const int ly = e / tw, lx = e - ly * tw;
             cell_sel_uni[cell * n_best + t] = ((y0 + ly) << 16) | (x0 + lx);
         }
-        if (par) {
+        if (uniform_only) {
+        } else if (par) {
             kp_introselect_block(vals, tosort, cnt, pick - 1, Lpos, Rpos, s_ctl, s_wsum);
         } else if (t == 0) {
             sm::kp_introselect_cp<unsigned short>(vals, tosort, cnt, pick - 1, 0);
         }
     }
     if (t == 0) cell_count[cell] = pick;
+    if (uniform_only) return;
     __syncthreads();
     if (t < pick) {
         const int e = lidx[tosort[t]];
@@ -499,11 +508,9 @@ __global__ __launch_bounds__(256) void k_kp_cell_rigid(const float* __restrict__
     }
 }
 
-// rigid flow of the reference depth under `T` (ref -> cur), its distance to the optical flow (kept in rb.rdiff), then
-// the two keypoint sets: rb.kp = [kp1_best | kp2_best | kp1_uniform | kp2_uniform], each sel_cap x 2 doubles;
-// rb.info[0] = their common count.  d_rdiff_override (optional) replaces the computed distance map.
-int enqueue_rigid_flow_kp(RigidKpBuffers& rb, const float* d_flow, const float* d_odiff, const float* d_depth32, int H,
-                          int W, const RigidKpConfig& cfg, const float* d_rdiff_override, hipStream_t s) {
+// the refusals and the launch geometry shared by enqueue_rigid_flow_kp and the rounds of the iterative scale loop
+int rigid_flow_kp_geometry(int H, int W, const RigidKpConfig& cfg, int* cells_out, int* n_best_out, int* cap_out, size_t* lds_out,
+                           int* par_out) {
     const int cells = cfg.num_row * cfg.num_col;
     DFVO_ARG_CHECK(cells > 0 && cells <= 1024 && H < 65536 && W < 65536, "rigid_flow_kp: grid too large");
     const int n_best = cfg.num_bestN / cells;
@@ -514,6 +521,39 @@ int enqueue_rigid_flow_kp(RigidKpBuffers& rb, const float* d_flow, const float* 
     DFVO_ARG_CHECK(lds <= 158 * 1024, "rigid_flow_kp: cell does not fit in LDS");
     const int par = lds + (size_t)cap * 4 + 16 <= 150 * 1024 ? 1 : 0;
     if (par) lds += (size_t)cap * 4 + 16;
+    *cells_out = cells, *n_best_out = n_best, *cap_out = cap, *lds_out = lds, *par_out = par;
+    return DFVO_OK;
+}
+
+int enqueue_rigid_flow_kp_round(RigidKpBuffers& rb, const float* d_flow, const float* d_odiff, const float* d_depth32, int H,
+                                int W, const RigidKpConfig& cfg, float* d_rdiff_out, const int* d_skip, hipStream_t s) {
+    int cells, n_best, cap, par;
+    size_t lds;
+    if (int rc_g = rigid_flow_kp_geometry(H, W, cfg, &cells, &n_best, &cap, &lds, &par)) return rc_g;
+    // (the caller ensured rb for this size before it enqueued the first round: no allocation between the rounds)
+    DFVO_ARG_CHECK((size_t)H * W <= rb.depth32.n && cells * n_best <= rb.sel_cap && (size_t)cells * cap <= rb.lidx.n,
+                   "rigid_flow_kp round: buffers not ensured for this size");
+    if (int rc_lds = ensure_dyn_lds((const void*)k_kp_cell_rigid, lds)) return rc_lds;
+    hipLaunchKernelGGL(k_rigid_flow_diff, dim3(cdiv(H * W, 256)), dim3(256), 0, s, d_depth32, d_flow, H, W, rb.mats, d_rdiff_out,
+                       (float*)nullptr, d_skip);
+    hipLaunchKernelGGL(k_kp_cell_rigid, dim3(cells), dim3(256), lds, s, d_odiff, (const float*)d_rdiff_out, H, W, cfg.num_row,
+                       cfg.num_col, cfg.opt_thre, cfg.rigid_thre, cfg.score_rigid, n_best, cap, rb.cell_count, rb.cell_sel,
+                       rb.cell_sel_uni, rb.lidx, par, 1, d_skip);
+    const size_t sc = (size_t)rb.sel_cap * 2;
+    hipLaunchKernelGGL(k_kp_gather, dim3(1), dim3(256), 0, s, rb.cell_count, rb.cell_sel_uni, cells, n_best, d_flow, H, W,
+                       rb.zero, (const int*)nullptr, 0, 0, rb.kp + 2 * sc, rb.kp + 3 * sc, rb.info + 4, d_skip);
+    DFVO_HIP_CHECK(hipGetLastError());
+    return DFVO_OK;
+}
+
+// rigid flow of the reference depth under `T` (ref -> cur), its distance to the optical flow (kept in rb.rdiff), then
+// the two keypoint sets: rb.kp = [kp1_best | kp2_best | kp1_uniform | kp2_uniform], each sel_cap x 2 doubles;
+// rb.info[0] = their common count.  d_rdiff_override (optional) replaces the computed distance map.
+int enqueue_rigid_flow_kp(RigidKpBuffers& rb, const float* d_flow, const float* d_odiff, const float* d_depth32, int H,
+                          int W, const RigidKpConfig& cfg, const float* d_rdiff_override, hipStream_t s) {
+    int cells, n_best, cap, par;
+    size_t lds;
+    if (int rc_g = rigid_flow_kp_geometry(H, W, cfg, &cells, &n_best, &cap, &lds, &par)) return rc_g;
     int rc = rb.ensure(H, W, cells, n_best, cap);
     if (rc != DFVO_OK) return rc;
     if (int rc_lds = ensure_dyn_lds((const void*)k_kp_cell_rigid, lds)) return rc_lds;
@@ -526,18 +566,18 @@ int enqueue_rigid_flow_kp(RigidKpBuffers& rb, const float* d_flow, const float* 
         DFVO_HIP_CHECK(hipMemcpyAsync(rb.mats, m, sizeof(m), hipMemcpyHostToDevice, s));
         DFVO_HIP_CHECK(hipStreamSynchronize(s));  // `m` is a stack buffer
         hipLaunchKernelGGL(k_rigid_flow_diff, dim3(cdiv(H * W, 256)), dim3(256), 0, s, d_depth32, d_flow, H, W, rb.mats,
-                           rb.rdiff, (float*)nullptr);
+                           rb.rdiff, (float*)nullptr, (const int*)nullptr);
         rdiff = rb.rdiff;
     }
     hipLaunchKernelGGL(k_kp_cell_rigid, dim3(cells), dim3(256), lds, s, d_odiff, rdiff, H, W, cfg.num_row, cfg.num_col,
                        cfg.opt_thre, cfg.rigid_thre, cfg.score_rigid, n_best, cap, rb.cell_count, rb.cell_sel,
-                       rb.cell_sel_uni, rb.lidx, par);
+                       rb.cell_sel_uni, rb.lidx, par, 0, (const int*)nullptr);
     // both sets in cell order; no "enough keypoints" rules here (the reference asserts a non-empty selection)
     const size_t sc = (size_t)rb.sel_cap * 2;
     hipLaunchKernelGGL(k_kp_gather, dim3(1), dim3(256), 0, s, rb.cell_count, rb.cell_sel, cells, n_best, d_flow, H, W, rb.zero,
-                       (const int*)nullptr, 0, 0, rb.kp, rb.kp + sc, rb.info);
+                       (const int*)nullptr, 0, 0, rb.kp, rb.kp + sc, rb.info, (const int*)nullptr);
     hipLaunchKernelGGL(k_kp_gather, dim3(1), dim3(256), 0, s, rb.cell_count, rb.cell_sel_uni, cells, n_best, d_flow, H, W,
-                       rb.zero, (const int*)nullptr, 0, 0, rb.kp + 2 * sc, rb.kp + 3 * sc, rb.info + 4);
+                       rb.zero, (const int*)nullptr, 0, 0, rb.kp + 2 * sc, rb.kp + 3 * sc, rb.info + 4, (const int*)nullptr);
     DFVO_HIP_CHECK(hipGetLastError());
     return DFVO_OK;
 }
@@ -621,7 +661,8 @@ int enqueue_local_bestn(TrackerBuffers& tb, const float* d_flow, const float* d_
     const int min_total = (int)ceil((double)num_bestN * 0.1);
     const int min_regions = (int)ceil((double)cells * 0.1);
     hipLaunchKernelGGL(k_kp_gather, dim3(1), dim3(256), 0, s, tb.cell_count, tb.cell_sel, cells, n_best, d_flow, H, W,
-                       tb.kp_total + KPT_GOOD, tb.kp_total + KPT_CELL_PARTIAL, min_total, min_regions, tb.kp_ref, tb.kp_cur, tb.kp_info);
+                       tb.kp_total + KPT_GOOD, tb.kp_total + KPT_CELL_PARTIAL, min_total, min_regions, tb.kp_ref, tb.kp_cur, tb.kp_info,
+                       (const int*)nullptr);
     DFVO_HIP_CHECK(hipGetLastError());
     return DFVO_OK;
 }

@@ -1,6 +1,7 @@
 // Depth-ratio scale recovery.  Reference call sites (paths relative to /root/reference):
 //   libs/tracker/E_tracker.py:571-643             find_scale_from_depth (+ libs/geometry/ops_3d.py:15-67)
 //   sklearn RANSACRegressor.fit (third party)     subset draws from the global numpy RandomState
+//   libs/tracker/E_tracker.py:509-569             scale_recovery_iterative (enqueue_scale_recovery_iterative, at the end)
 // See tracker.h on sequential semantics.  Built with -ffp-contract=off.
 #include <atomic>
 #include <cstdio>  // sscanf
@@ -16,7 +17,8 @@ namespace dfvo {
 __global__ void k_scale_triangulate(const int* __restrict__ n_ptr, const double* __restrict__ kp1,
                                     const double* __restrict__ kp2, const double* __restrict__ T21, double cx, double cy,
                                     double fx, double fy, int H, int W, double* __restrict__ z2,
-                                    int* __restrict__ pix, int* __restrict__ winner) {
+                                    int* __restrict__ pix, int* __restrict__ winner, const int* __restrict__ skip) {
+    if (skip && *skip) return;  // (the iterative scale loop's rounds behind its last one)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= *n_ptr) return;
     const double P1[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
@@ -45,10 +47,12 @@ __global__ __launch_bounds__(256) void k_scale_ratios(const int* __restrict__ n_
                                                        const int* __restrict__ pix, const int* __restrict__ winner,
                                                        const double* __restrict__ depth, double* __restrict__ ratios,
                                                        int* __restrict__ n_valid, double* __restrict__ tri_list,
-                                                       double* __restrict__ pred_list, int depth_per_kp) {
+                                                       double* __restrict__ pred_list, int depth_per_kp,
+                                                       const int* __restrict__ skip) {
     // single block: n <= a few thousand.  rank = number of valid entries with a smaller pixel index.
     // depth_per_kp: `depth` holds the depth map's value at keypoint i's pixel, [n], instead of the map (the only pixels read)
     extern __shared__ int s_pix[];
+    if (skip && *skip) return;
     const int n = *n_ptr;
     const int t = threadIdx.x;
     for (int i = t; i < n; i += blockDim.x) {
@@ -90,13 +94,15 @@ __global__ __launch_bounds__(256) void k_scale_ransac(uint32_t* __restrict__ mt_
                                                        int max_trials, double stop_prob, double thr,
                                                        uint8_t* __restrict__ inl_a, uint8_t* __restrict__ inl_b,
                                                        int* __restrict__ scratch, ScaleResult* __restrict__ out,
-                                                       const PoseState* __restrict__ gate, int r2_nan_below_two) {
+                                                       const PoseState* __restrict__ gate, int r2_nan_below_two,
+                                                       const int* __restrict__ skip) {
     __shared__ sm::Mt19937 s;
     __shared__ double s_coef;
     __shared__ int s_cnt[4], s_nz[4];
     __shared__ double s_red[3][4];
     __shared__ int s_ctl;  // 0 continue, 1 stop
     __shared__ int s_best_is_a;
+    if (skip && *skip) return;  // before the RandomState is read: a skipped round draws nothing
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int n = *n_valid;
     // fused pipeline: scale recovery only runs when ||t|| != 0 (dfvo.py:198); a rejected E-tracker pose must not
@@ -276,7 +282,7 @@ int enqueue_ransac_regressor(TrackerBuffers& tb, int n, bool y_is_ones, const Sc
     hipLaunchKernelGGL(k_scale_ransac, dim3(1), dim3(256), 0, s, tb.mt_state, tb.ratios,
                        y_is_ones ? (const double*)nullptr : tb.ratios + tb.kp_cap, tb.kp_total + KPT_SCALE_VALID, -1, cfg.min_samples,
                        cfg.max_trials, cfg.stop_prob, cfg.thre, tb.inl_a, tb.inl_b, tb.scratch, tb.scale_out,
-                       (const PoseState*)nullptr, g_sklearn_r2_nan_below_two.load());
+                       (const PoseState*)nullptr, g_sklearn_r2_nan_below_two.load(), (const int*)nullptr);
     DFVO_HIP_CHECK(hipGetLastError());
     return DFVO_OK;
 }
@@ -297,16 +303,155 @@ int enqueue_find_scale(TrackerBuffers& tb, int n_host, const double* d_T21, cons
     tb.seg_mask &= ~0x700u;
     if (tb.mark(8, s) != DFVO_OK) return DFVO_ERR_HIP;
     hipLaunchKernelGGL(k_scale_triangulate, dim3(nb), dim3(256), 0, s, tb.kp_info, tb.kp_ref, tb.kp_cur, d_T21, cfg.cx,
-                       cfg.cy, cfg.fx, cfg.fy, H, W, tb.z2, tb.pix, tb.winner);
+                       cfg.cy, cfg.fx, cfg.fy, H, W, tb.z2, tb.pix, tb.winner, (const int*)nullptr);
     hipLaunchKernelGGL(k_scale_ratios, dim3(1), dim3(256), sizeof(int) * (size_t)(n_host > 0 ? n_host : 1), s, tb.kp_info,
                        tb.z2, tb.pix, tb.winner, d_depth, tb.ratios, tb.kp_total + KPT_SCALE_VALID, abs_diff ? tb.ratios + tb.kp_cap : nullptr,
-                       abs_diff ? tb.ratios + 2 * (size_t)tb.kp_cap : nullptr, depth_per_kp ? 1 : 0);
+                       abs_diff ? tb.ratios + 2 * (size_t)tb.kp_cap : nullptr, depth_per_kp ? 1 : 0, (const int*)nullptr);
     if (tb.mark(9, s) != DFVO_OK) return DFVO_ERR_HIP;
     hipLaunchKernelGGL(k_scale_ransac, dim3(1), dim3(256), 0, s, tb.mt_state, abs_diff ? tb.ratios + tb.kp_cap : tb.ratios,
                        abs_diff ? tb.ratios + 2 * (size_t)tb.kp_cap : (const double*)nullptr, tb.kp_total + KPT_SCALE_VALID, 10,
                        cfg.min_samples, cfg.max_trials, cfg.stop_prob, cfg.thre, tb.inl_a, tb.inl_b, tb.scratch,
-                       tb.scale_out, d_gate, g_sklearn_r2_nan_below_two.load());
+                       tb.scale_out, d_gate, g_sklearn_r2_nan_below_two.load(), (const int*)nullptr);
     if (tb.mark(10, s) != DFVO_OK) return DFVO_ERR_HIP;
+    DFVO_HIP_CHECK(hipGetLastError());
+    return DFVO_OK;
+}
+
+// ================================================================================================
+// EssTracker.scale_recovery_iterative (E_tracker.py:509-569) as one enqueue
+// ================================================================================================
+struct IterMats {
+    float Kinv[9], K[9];
+};
+
+__global__ void k_iter_init(IterCtl* __restrict__ ctl, double prev_scale) {
+    if (threadIdx.x != 0) return;
+    ctl->scale = prev_scale;
+    ctl->done = 0;
+    ctl->n_iter = 0;
+    ctl->status = ITER_RUNNING;
+    ctl->sel_round = -1;
+    for (int r = 0; r < ITER_ROUNDS; ++r) {
+        ctl->scale_in[r] = 0.0;
+        ctl->scale_out[r] = 0.0;
+        ctl->n_kp[r] = -1;
+    }
+    ctl->pad = 0;
+}
+
+// end of a round (E_tracker.py:557-568; the scale -1 of "too few valid points" gets no special case there either)
+__device__ void iter_end(IterCtl* __restrict__ ctl, int round, const ScaleResult* __restrict__ res) {
+    if (ctl->done) return;
+    if (res->status < 0) {  // sklearn raised inside find_scale_from_depth
+        ctl->done = 1;
+        ctl->status = ITER_NO_CONSENSUS;
+        return;
+    }
+    const double new_scale = res->scale;
+    const double delta = fabs(new_scale - ctl->scale);
+    ctl->scale_out[round] = new_scale;
+    ctl->scale = new_scale;
+    ctl->n_iter = round + 1;
+    if (delta < 0.001) ctl->done = 1;
+}
+
+// start of a round, one lane: closes the round before it, then builds rigid_flow_pose = inv([R | t * scale]) of this round in
+// float32, beside Kinv and K (the matrices come as a kernel argument: no host buffer has to outlive the enqueue)
+__global__ void k_iter_begin(IterCtl* __restrict__ ctl, int round, const ScaleResult* __restrict__ res,
+                             const double* __restrict__ E_pose, IterMats m, float* __restrict__ mats /*Kinv[9] | T[16] | K[9]*/) {
+    if (threadIdx.x != 0) return;
+    if (round > 0) iter_end(ctl, round - 1, res);
+    if (ctl->done) return;
+    const double scale = ctl->scale;
+    ctl->scale_in[round] = scale;
+    for (int i = 0; i < 9; ++i) {
+        mats[i] = m.Kinv[i];
+        mats[25 + i] = m.K[i];
+    }
+    sm::rigid_pose_inv_f32(E_pose, scale, mats + 9);
+}
+
+// behind the selection.  Lane 0 of block 0: the reference asserts a non-empty selection before it looks for the scale.  Every
+// thread: the two fills of the scale stage (see enqueue_scale_prepare).  A block that reads `done` while lane 0 sets it for an
+// empty selection may still clear its part of the map: nothing reads the map before the next call clears all of it.
+__global__ void k_iter_selected(IterCtl* __restrict__ ctl, int round, const int* __restrict__ n_uniform, int* __restrict__ winner,
+                                int px, int* __restrict__ n_valid) {
+    if (ctl->done) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < px) winner[i] = -1;
+    if (i != 0) return;
+    *n_valid = 0;
+    const int n = *n_uniform;
+    ctl->n_kp[round] = n;
+    if (n == 0) {
+        ctl->done = 1;
+        ctl->status = ITER_EMPTY;
+    } else {
+        ctl->sel_round = round;
+    }
+}
+
+// behind the last round, one lane
+__global__ void k_iter_end(IterCtl* __restrict__ ctl, int round, const ScaleResult* __restrict__ res) {
+    if (threadIdx.x == 0) iter_end(ctl, round, res);
+}
+
+int enqueue_scale_recovery_iterative(TrackerBuffers& tb, RigidKpBuffers& rb, const float* d_flow, const float* d_odiff,
+                                     const float* d_depth32_ref, const double* d_depth64_cur, int H, int W,
+                                     const RigidKpConfig& cfg, const ScaleConfig& scfg, const double* d_E_pose,
+                                     const double* d_T21, double prev_scale, int kp_src, int n_kp_best, hipStream_t s) {
+    DFVO_ARG_CHECK(d_flow && d_odiff && d_depth32_ref && d_depth64_cur && d_E_pose && d_T21 && H > 0 && W > 0,
+                   "scale_recovery_iterative: bad argument");
+    DFVO_ARG_CHECK(kp_src == 0 || kp_src == 1, "scale_recovery_iterative: kp_src is 0 (kp_depth) or 1 (kp_best)");
+    DFVO_ARG_CHECK(scfg.min_samples >= 1 && scfg.min_samples <= 8, "scale_recovery_iterative: min_samples in [1,8]");
+    int cells, n_best, cap, par;
+    size_t lds;
+    if (int rc_g = rigid_flow_kp_geometry(H, W, cfg, &cells, &n_best, &cap, &lds, &par)) return rc_g;
+    // the keypoints the scale stage may see: a round's uniform set (at most cells * n_best) or the caller's fixed set
+    const int n_sel = cells * n_best;
+    const int n_scale = kp_src == 0 ? n_sel : n_kp_best;
+    DFVO_ARG_CHECK(n_scale >= 0 && n_scale <= ITER_MAX_KP,
+                   "scale_recovery_iterative: more keypoints than k_scale_ratios holds in 64 KB of LDS (16384)");
+    DFVO_ARG_CHECK(kp_src == 0 || n_kp_best <= tb.kp_cap, "scale_recovery_iterative: kp_best exceeds the keypoint capacity");
+    if (int rc_e = rb.ensure(H, W, cells, n_best, cap)) return rc_e;
+    if (kp_src == 0)
+        if (int rc_k = tb.ensure_kp(n_sel > 16 ? n_sel : 16, 1, 1)) return rc_k;
+    if (int rc_w = tb.grow_winner(H, W)) return rc_w;
+    IterMats m;
+    for (int i = 0; i < 9; ++i) m.Kinv[i] = cfg.Kinv[i], m.K[i] = cfg.K[i];
+    IterCtl* ctl = rb.ctl;
+    const int* skip = &ctl->done;
+    const size_t sc = (size_t)rb.sel_cap * 2;
+    const double* kp1 = kp_src == 0 ? rb.kp + 2 * sc : tb.kp_ref.p;
+    const double* kp2 = kp_src == 0 ? rb.kp + 3 * sc : tb.kp_cur.p;
+    const int* n_ptr = kp_src == 0 ? rb.info + 4 : tb.kp_info.p;  // (kp_best: the caller set tb.kp_info[0] with the keypoints)
+    const int nb = cdiv(n_scale > 0 ? n_scale : 1, 256);
+    const size_t ratios_lds = sizeof(int) * (size_t)(n_scale > 0 ? n_scale : 1);
+    const bool abs_diff = scfg.method == 1;
+    const int px = H * W;
+    tb.seg_mask &= ~0x700u;  // no stage marks between the rounds: dfvo_tracker_stage_ms reports none for the scale stage
+    hipLaunchKernelGGL(k_iter_init, dim3(1), dim3(64), 0, s, ctl, prev_scale);
+    for (int r = 0; r < ITER_ROUNDS; ++r) {
+        hipLaunchKernelGGL(k_iter_begin, dim3(1), dim3(64), 0, s, ctl, r, (const ScaleResult*)tb.scale_out.p, d_E_pose, m,
+                           rb.mats.p);
+        if (int rc_r = enqueue_rigid_flow_kp_round(rb, d_flow, d_odiff, d_depth32_ref, H, W, cfg, rb.rdiff_of(r, H, W), skip, s))
+            return rc_r;
+        hipLaunchKernelGGL(k_iter_selected, dim3(cdiv(px, 256)), dim3(256), 0, s, ctl, r, (const int*)(rb.info + 4), tb.winner.p, px,
+                           tb.kp_total + KPT_SCALE_VALID);
+        hipLaunchKernelGGL(k_scale_triangulate, dim3(nb), dim3(256), 0, s, n_ptr, kp1, kp2, d_T21, scfg.cx, scfg.cy, scfg.fx,
+                           scfg.fy, H, W, tb.z2.p, tb.pix.p, tb.winner.p, skip);
+        hipLaunchKernelGGL(k_scale_ratios, dim3(1), dim3(256), ratios_lds, s, n_ptr, (const double*)tb.z2.p, (const int*)tb.pix.p,
+                           (const int*)tb.winner.p, d_depth64_cur, tb.ratios.p, tb.kp_total + KPT_SCALE_VALID,
+                           abs_diff ? tb.ratios + tb.kp_cap : (double*)nullptr,
+                           abs_diff ? tb.ratios + 2 * (size_t)tb.kp_cap : (double*)nullptr, 0, skip);
+        hipLaunchKernelGGL(k_scale_ransac, dim3(1), dim3(256), 0, s, tb.mt_state,
+                           (const double*)(abs_diff ? tb.ratios + tb.kp_cap : tb.ratios.p),
+                           (const double*)(abs_diff ? tb.ratios + 2 * (size_t)tb.kp_cap : nullptr),
+                           (const int*)(tb.kp_total + KPT_SCALE_VALID), 10, scfg.min_samples, scfg.max_trials, scfg.stop_prob,
+                           scfg.thre, tb.inl_a.p, tb.inl_b.p, tb.scratch.p, tb.scale_out.p, (const PoseState*)nullptr,
+                           g_sklearn_r2_nan_below_two.load(), skip);
+    }
+    hipLaunchKernelGGL(k_iter_end, dim3(1), dim3(64), 0, s, ctl, ITER_ROUNDS - 1, (const ScaleResult*)tb.scale_out.p);
     DFVO_HIP_CHECK(hipGetLastError());
     return DFVO_OK;
 }

@@ -2,7 +2,7 @@
 //   solver_kp.hip               keypoint selection (local_bestN, bestN_flow_kp, rigid-flow and sampled keypoints)
 //   solver_rng.hip              numpy's MT19937 seeding and shuffle on the device
 //   solver_pose2d2d.hip         EssTracker.compute_pose_2d2d: GRIC, the repeated shuffled five-point RANSAC, bookkeeping
-//   solver_scale.hip            depth-ratio scale recovery (find_scale_from_depth)
+//   solver_scale.hip            depth-ratio scale recovery (find_scale_from_depth) and the iterative loop around it as one enqueue
 //   solver_trajectory.hip       update_global_pose over a gathered sequence
 //   solver_buffers.hip          lifetime of every buffer set declared here and in solver.h (host only)
 // Sequential semantics that leak into the results (argpartition order, python-loop summation order, the global
@@ -209,8 +209,26 @@ struct RigidKpConfig {
     int score_rigid;              // 1: score = rigid-flow distance, 0: forward-backward distance
     float K[9], Kinv[9], T[16];   // float32 intrinsics, their inverse, the ref -> cur motion (row-major)
 };
+// scale_recovery_iterative (E_tracker.py:509-569) as one enqueue: the loop's state on the device.  Every kernel of a round
+// reads `done` as its skip flag, so the rounds behind the last executed one draw nothing and overwrite nothing.
+constexpr int ITER_ROUNDS = 5;
+constexpr int ITER_RUNNING = 0;       // status
+constexpr int ITER_EMPTY = 1;         // opt_rigid_flow_kp selected nothing (the reference's assertion) in round n_iter
+constexpr int ITER_NO_CONSENSUS = 2;  // sklearn's "could not find a valid consensus set" in round n_iter
+struct IterCtl {
+    double scale;   // in: prev_scale; out: the last round's scale
+    int done;       // the skip flag of every later kernel
+    int n_iter;     // rounds completed (find_scale_from_depth returned)
+    int status;     // ITER_*
+    int sel_round;  // last round whose selection was not empty (-1: none); its distance map is rdiff_of(sel_round)
+    double scale_in[ITER_ROUNDS], scale_out[ITER_ROUNDS];
+    int n_kp[ITER_ROUNDS];  // uniform keypoints of each round (-1: round not run)
+    int pad;
+};
 struct RigidKpBuffers {
-    DevArr<float> depth32, rdiff, mats;  // depth32, rdiff: one float per pixel
+    DevArr<float> depth32, rdiff, mats;  // depth32: one float per pixel; rdiff: two maps (iterative rounds alternate)
+    DevArr<IterCtl> ctl;
+    float* rdiff_of(int round, int H, int W) const { return rdiff.p + (size_t)(round & 1) * H * W; }
     DevArr<int> cell_count, cell_sel, cell_sel_uni, info, zero;
     DevArr<unsigned short> lidx;
     DevArr<double> kp;            // [4][sel_cap][2]: kp1 best, kp2 best, kp1 uniform, kp2 uniform
@@ -220,6 +238,12 @@ struct RigidKpBuffers {
 };
 int enqueue_rigid_flow_kp(RigidKpBuffers& rb, const float* d_flow, const float* d_odiff, const float* d_depth32, int H,
                           int W, const RigidKpConfig& cfg, const float* d_rdiff_override, hipStream_t s);
+// one round of the iterative loop: rb.mats already holds Kinv | T | K on the device (k_iter_begin), the distance map goes
+// to d_rdiff_out, only the uniform set is selected (rb.kp + 2 * sel_cap * 2, count in rb.info[4]); nothing runs when *d_skip
+int enqueue_rigid_flow_kp_round(RigidKpBuffers& rb, const float* d_flow, const float* d_odiff, const float* d_depth32, int H,
+                                int W, const RigidKpConfig& cfg, float* d_rdiff_out, const int* d_skip, hipStream_t s);
+// launch geometry of the rigid-flow keypoint kernels for this size (the refusals shared by every entry point)
+int rigid_flow_kp_geometry(int H, int W, const RigidKpConfig& cfg, int* cells, int* n_best, int* cap, size_t* lds, int* par);
 // d_info (optional): receives a tracker's kp_info triple [n, 1, 0] (keypoint_sampler.py:96: good_kp_found stays True)
 int enqueue_kp_sampled(const float* d_flow, int H, int W, int y0, int y1, int x0, int x1, const int* d_idx, int n,
                        double* d_kp1, double* d_kp2, hipStream_t s, int* d_info = nullptr);
@@ -248,6 +272,18 @@ int enqueue_find_scale(TrackerBuffers& tb, int n_host, const double* d_T21, cons
                        const ScaleConfig& cfg, hipStream_t s, const PoseState* d_gate = nullptr, bool prepared = false,
                        bool depth_per_kp = false);
 int enqueue_scale_prepare(TrackerBuffers& tb, int H, int W);
+// EssTracker.scale_recovery_iterative, all ITER_ROUNDS rounds enqueued back to back on `s` with no host wait between them.
+// d_E_pose: 16 doubles, cur -> ref with unit translation; d_T21: 16 doubles, its inverse (what find_scale_from_depth takes);
+// cfg.T is not read.  kp_src 0 "kp_depth": the scale of a round is taken from that round's uniform keypoints; 1 "kp_best":
+// from tb.kp_ref / tb.kp_cur (n_kp_best of them).  rb.ctl holds the outcome; the last selected round's uniform keypoints stay
+// in rb.kp, its distance map in rb.rdiff_of(ctl.sel_round).  Consumes tb.mt_state.
+// k_scale_ratios keeps one int per keypoint in dynamic LDS: at most ITER_MAX_KP keypoints (64 KB, the size a kernel gets
+// without asking for more).
+constexpr int ITER_MAX_KP = 16384;
+int enqueue_scale_recovery_iterative(TrackerBuffers& tb, RigidKpBuffers& rb, const float* d_flow, const float* d_odiff,
+                                     const float* d_depth32_ref, const double* d_depth64_cur, int H, int W,
+                                     const RigidKpConfig& cfg, const ScaleConfig& scfg, const double* d_E_pose,
+                                     const double* d_T21, double prev_scale, int kp_src, int n_kp_best, hipStream_t s);
 int enqueue_ransac_regressor(TrackerBuffers& tb, int n, bool y_is_ones, const ScaleConfig& cfg, hipStream_t s);
 int set_sklearn_compat(const char* version);  // "0.20" (the reference's pin, default) | "0.22" and later
 

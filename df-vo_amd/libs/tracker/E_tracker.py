@@ -114,8 +114,84 @@ class EssTracker:
             raise NotImplementedError("scale_recovery.method '%s'" % self.cfg.scale_recovery.method)
         return outputs
 
+    # scale_recovery_iterative runs as one dfvo_scale_recovery_iterative call (all rounds on the device); False: the host loop
+    # around dfvo_kp_rigid_flow / dfvo_find_scale_from_depth_at_kp, with the same results
+    iterative_on_device = True
+
     def scale_recovery_iterative(self, cur_data, ref_data, E_pose):
-        """E_tracker.py:509-569: up to five rounds of (rigid-flow keypoints under the current scale -> depth-ratio scale)"""
+        """E_tracker.py:509-569: up to five rounds of (rigid-flow keypoints under the current scale -> depth-ratio scale).
+        Leaves what the reference leaves: the returned dict, ref_data['rigid_flow_pose' | 'rigid_flow_diff' | 'kp_depth'],
+        cur_data['kp_depth' | 'rigid_flow_mask'], self.prev_scale, np.random's state, and its two exceptions."""
+        c = self.cfg.kp_selection.rigid_flow_kp
+        if not self.iterative_on_device or not c.enable:
+            return self._scale_recovery_iterative_host(cur_data, ref_data, E_pose)
+        rc = self.cfg.scale_recovery.ransac
+        if rc.method not in SCALE_METHODS:
+            raise NotImplementedError("scale_recovery.ransac.method '%s'" % rc.method)
+        h, w = cur_data['depth'].shape
+        flow = np.ascontiguousarray(ref_data['flow'], dtype=np.float32)
+        diff = np.ascontiguousarray(ref_data['flow_diff'], dtype=np.float32).reshape(h, w)
+        raw_depth = np.ascontiguousarray(ref_data['raw_depth'], dtype=np.float32)
+        depth_cur = np.ascontiguousarray(cur_data['depth'], dtype=np.float64)
+        assert flow.shape == (2, h, w) and raw_depth.shape == (h, w)
+        cam = self.cam_intrinsics
+        K, Kinv = np.asarray(cam.mat, dtype=np.float64), np.asarray(cam.inv_mat, dtype=np.float64)
+        score_method = self.cfg.scale_recovery.iterative_kp.score_method
+        kcfg = capi.RigidKpCfg(num_row=int(c.num_row), num_col=int(c.num_col), num_bestN=int(c.num_bestN),
+                               rigid_flow_thre=float(c.rigid_flow_thre), optical_flow_thre=float(c.optical_flow_thre),
+                               score_method=1 if score_method == "rigid_flow" else 0)
+        for i in range(9):
+            kcfg.K[i] = K.flat[i]
+            kcfg.Kinv[i] = Kinv.flat[i]
+        scfg = capi.ScaleCfg(cx=float(cam.cx), cy=float(cam.cy), fx=float(cam.fx), fy=float(cam.fy),
+                             min_samples=int(rc.min_samples), max_trials=int(rc.max_trials),
+                             stop_prob=float(rc.stop_prob), thre=float(rc.thre), method=SCALE_METHODS[rc.method])
+        E = np.ascontiguousarray(E_pose.pose, dtype=np.float64)
+        T_21 = np.ascontiguousarray(E_pose.inv_pose, dtype=np.float64)
+        kp_src = self.cfg.scale_recovery.kp_src
+        best_ref = best_cur = None
+        if kp_src != "kp_depth":  # a fixed set, e.g. the local_bestN keypoints of the *_extend.yml configurations
+            best_ref = np.ascontiguousarray(ref_data[kp_src], dtype=np.float64)
+            best_cur = np.ascontiguousarray(cur_data[kp_src], dtype=np.float64)
+        nmax = int(c.num_bestN)
+        kp_ref, kp_cur = np.zeros((nmax, 2)), np.zeros((nmax, 2))
+        rdiff = np.zeros((h, w), np.float32)
+        out = capi.ScaleIterOut(kp_round=-1)  # (stays when the first round selects nothing: the call then writes no output)
+        rng = _ctx.numpy_rng_words()
+        code = capi.lib().dfvo_scale_recovery_iterative(
+            _ctx.tracker_exclusive(), capi.as_ptr(flow), capi.as_ptr(diff), capi.as_ptr(raw_depth), capi.as_ptr(depth_cur), h, w,
+            C.byref(kcfg), C.byref(scfg), capi.as_ptr(E), capi.as_ptr(T_21), float(self.prev_scale),
+            0 if best_ref is None else 1, capi.as_ptr(best_ref), capi.as_ptr(best_cur),
+            0 if best_ref is None else best_ref.shape[0], capi.as_ptr(rng), C.byref(out), capi.as_ptr(kp_ref),
+            capi.as_ptr(kp_cur), capi.as_ptr(rdiff))
+        if code not in (0, capi.ERR_EMPTY_SELECTION, capi.ERR_NO_CONSENSUS):
+            capi.check(code)
+        self.last_iterative = out  # (diagnostics: rounds taken, per-round counts and scales, device time)
+        first_round_empty = code == capi.ERR_EMPTY_SELECTION and out.kp_round < 0  # (nothing was written)
+        # the pose of the last round that began: completed rounds, plus the one that raised
+        last = 0 if first_round_empty else (out.n_iter - 1 if code == 0 else out.n_iter)
+        scale_in = self.prev_scale if first_round_empty else out.scale_in[last]
+        rigid_flow_pose = copy.deepcopy(E_pose)
+        rigid_flow_pose.t *= scale_in
+        ref_data['rigid_flow_pose'] = SE3(rigid_flow_pose.inv_pose)
+        if not first_round_empty:
+            _ctx.set_numpy_rng(rng)
+            n = out.n_kp
+            ref_data['rigid_flow_diff'] = np.expand_dims(rdiff, 2)
+            ref_data['kp_depth'] = kp_ref[:n].copy()
+            cur_data['kp_depth'] = kp_cur[:n].copy()
+            cur_data['rigid_flow_mask'] = rdiff
+            if out.n_iter > 0:
+                self.prev_scale = -1 if out.scale == -1.0 else out.scale
+        if code == capi.ERR_EMPTY_SELECTION:
+            raise AssertionError("sampling threshold is too small.")
+        if code == capi.ERR_NO_CONSENSUS:
+            raise ValueError("RANSAC could not find a valid consensus set (sklearn RANSACRegressor semantics)")
+        return {'scale': self.prev_scale, 'cur_kp': cur_data['kp_depth'], 'ref_kp': ref_data['kp_depth'],
+                'rigid_flow_mask': cur_data['rigid_flow_mask']}
+
+    def _scale_recovery_iterative_host(self, cur_data, ref_data, E_pose):
+        """the same loop on the host, one dfvo_kp_rigid_flow and one dfvo_find_scale_from_depth_at_kp call per round"""
         outputs = {}
         scale = self.prev_scale
         delta = 0.001

@@ -29,6 +29,8 @@ extern "C" {
 #define DFVO_ERR_ARG (-2)
 #define DFVO_ERR_STATE (-3)
 #define DFVO_ERR_RANGE (-4) /* f16x3 / f16 packing: an activation left f16's range in this call (see dfvo_f16s_overflow_count) */
+#define DFVO_ERR_EMPTY_SELECTION (-5) /* dfvo_scale_recovery_iterative: a round selected no rigid-flow keypoint (the reference asserts) */
+#define DFVO_ERR_NO_CONSENSUS (-6)    /* dfvo_scale_recovery_iterative: sklearn's "RANSAC could not find a valid consensus set" */
 
 const char* dfvo_last_error(void);
 /* number of visible HIP devices (0 when there is none); never fails */
@@ -404,6 +406,44 @@ int dfvo_find_scale_from_depth_at_kp(dfvo_tracker* trk, const double* h_kp1, con
  * consensus set", where sklearn raises ValueError).  cfg->cx .. fy and method are not read. */
 int dfvo_ransac_regressor(dfvo_tracker* trk, const double* h_x, const double* h_y, int n, const dfvo_scale_cfg* cfg,
                           double* coef, int* h_info);
+
+/* EssTracker.scale_recovery_iterative (E_tracker.py:509-569; scale_recovery.method "iterative", ablation_scale_iterative.yml and
+ * the tracking half of the *_extend.yml configurations): up to five rounds of [rigid_flow_pose = inv([R | t * scale]),
+ * kp_selection_good_depth under it (dfvo_kp_rigid_flow, uniform set), find_scale_from_depth], until the scale moves by less
+ * than 0.001.  All five rounds are enqueued at once; a device record carries the scale from round to round and makes the
+ * rounds behind the last one return at once, so the host neither waits nor copies between rounds, and a round that does not
+ * run draws nothing from the RandomState.
+ * Inputs, uploaded once: h_flow float [2,H,W], h_flow_diff float [H,W], h_raw_depth_ref float [H,W] (ref_data['raw_depth']),
+ * h_depth_cur double [H,W] (cur_data['depth']).  cfg: as for dfvo_kp_rigid_flow, T_ref_to_cur is not read.  h_E_pose: 4x4,
+ * cur -> ref with unit translation; h_T21 (optional): its inverse as find_scale_from_depth receives it (NULL: the closed form
+ * [R^T | -R^T t]).  kp_src DFVO_ITER_KP_DEPTH: each round's scale comes from that round's uniform keypoints;
+ * DFVO_ITER_KP_BEST: from the fixed set h_kp_best_ref / h_kp_best_cur [n_kp_best,2] (the other two are then ignored).
+ * h_rng625 (in / out): numpy RandomState words to run under, replaced by the advanced state.
+ * out: the scale, the rounds completed and the per-round records; h_kp_ref / h_kp_cur [num_bestN,2]: the uniform keypoints
+ * of the last round that ran (out->n_kp rows); h_rigid_flow_diff (optional, float [H,W]): that round's distance map.
+ * Returns DFVO_ERR_EMPTY_SELECTION where the reference's "sampling threshold is too small." assertion fires and
+ * DFVO_ERR_NO_CONSENSUS where sklearn raises; the outputs then hold what the reference had written when it raised (the
+ * previous round's keypoints and map for the former, this round's for the latter; out->n_iter rounds completed), and
+ * nothing at all is written when the first round selects nothing.  The tracker stays usable after either. */
+#define DFVO_ITER_KP_DEPTH 0
+#define DFVO_ITER_KP_BEST 1
+typedef struct dfvo_scale_iter_out {
+    double scale;            /* scale of the last completed round (prev_scale when none completed) */
+    int n_iter;              /* rounds completed, 0 .. 5 */
+    int n_kp;                /* rows of h_kp_ref / h_kp_cur */
+    int kp_round;            /* the round those keypoints and the distance map belong to (-1: none) */
+    int status;              /* 0 finished, 1 empty selection, 2 no consensus set */
+    double scale_in[5];      /* scale each round's rigid_flow_pose was built with */
+    double scale_out[5];     /* scale each round found (-1: fewer than 11 valid depth ratios) */
+    int n_kp_round[5];       /* uniform keypoints of each round (-1: the round did not run) */
+    float device_ms;         /* device time of the five enqueued rounds (HIP events around them, uploads and results outside) */
+} dfvo_scale_iter_out;
+int dfvo_scale_recovery_iterative(dfvo_tracker* trk, const float* h_flow, const float* h_flow_diff, const float* h_raw_depth_ref,
+                                  const double* h_depth_cur, int H, int W, const dfvo_rigid_kp_cfg* cfg,
+                                  const dfvo_scale_cfg* scfg, const double* h_E_pose, const double* h_T21, double prev_scale,
+                                  int kp_src, const double* h_kp_best_ref, const double* h_kp_best_cur, int n_kp_best,
+                                  uint32_t* h_rng625, dfvo_scale_iter_out* out, double* h_kp_ref, double* h_kp_cur,
+                                  float* h_rigid_flow_diff);
 
 /* PnpTracker.compute_pose_3d2d (pnp_tracker.py:45-125): masks (kp2 inside the image, depth_1[int(kp1)] != 0 and
  * in (min_depth, max_depth)), unprojection_kp (ops_3d.py:70-94), `repeat` x [np.random.shuffle +
