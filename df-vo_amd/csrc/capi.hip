@@ -3,7 +3,6 @@
 
 #include <cstdlib>
 #include <cstring>
-#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -78,6 +77,17 @@ int dfvo_memcpy_d2h(void* h_dst, const void* d_src, size_t bytes) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// The operator entry points below keep their device temporaries in local DevArrs.  Their rule: between the first enqueue
+// that reads a local array and the end of its scope, every path passes a hipStreamSynchronize of that stream -- finish().
+
+// waits for the stream behind a launch (the caller's temporaries die after it); the launch's error wins over the stream's
+static int finish(int rc, hipStream_t s) {
+    hipError_t e = hipStreamSynchronize(s);
+    if (rc != DFVO_OK) return rc;
+    DFVO_HIP_CHECK(e);
+    return DFVO_OK;
+}
+
 int dfvo_conv2d(const dfvo_conv_desc* d, const float* d_src0, const float* d_src1, const float* h_w,
                 const float* h_bias, const float* d_res, float* d_dst, void* stream) {
     DFVO_ARG_CHECK(d && d_src0 && h_w && d_dst, "dfvo_conv2d: null argument");
@@ -93,13 +103,9 @@ int dfvo_conv2d(const dfvo_conv_desc* d, const float* d_src0, const float* d_src
     std::vector<float> pw((size_t)(ksteps * 4 + 8) * cout_pad * 4), pb(cout_pad);  // slack: see make_conv
     conv_pack_weights(h_w, h_bias, d->cout, d->c0, d->c1, d->kh, d->kw, cout_pad, nullptr, nullptr, pw.data(),
                       pb.data());
-    ConvLayer L;  // every packing of the layer is released by free_conv, on every path
-    struct Release {
-        ConvLayer* l;
-        ~Release() { free_conv(l); }
-    } release{&L};
-    DFVO_HIP_CHECK(hipMalloc((void**)&L.wp, pw.size() * sizeof(float)));
-    DFVO_HIP_CHECK(hipMalloc((void**)&L.bias, pb.size() * sizeof(float)));
+    ConvLayer L;  // (its packings are read by run_conv's launch alone; the stream is waited for behind it, before L goes)
+    API_TRY(L.wp.alloc(pw.size()));
+    API_TRY(L.bias.alloc(pb.size()));
     DFVO_HIP_CHECK(hipMemcpy(L.wp, pw.data(), pw.size() * sizeof(float), hipMemcpyHostToDevice));
     DFVO_HIP_CHECK(hipMemcpy(L.bias, pb.data(), pb.size() * sizeof(float), hipMemcpyHostToDevice));
     API_TRY(make_f16s_weights(h_w, d->cout, d->c0, d->c1, d->kh, d->kw, nullptr, &L));
@@ -111,7 +117,7 @@ int dfvo_conv2d(const dfvo_conv_desc* d, const float* d_src0, const float* d_src
     L.m_hint = M;
     API_TRY(make_wino_weights(h_w, d->cout, d->c0, d->c1, d->kh, d->kw, nullptr,
                               d->stride == 1 && d->pad_h == 1 && d->pad_w == 1 && d->pad_mode == PAD_ZERO && d->up0 == 0, &L));
-    API_TRY(make_head_weights(h_w, d->cout, d->c0, d->c1, d->kh, d->kw, nullptr, &L.wh));
+    API_TRY(make_head_weights(h_w, d->cout, d->c0, d->c1, d->kh, d->kw, nullptr, &L));
     L.cout = d->cout;
     L.cout_pad = cout_pad;
     L.c0 = d->c0;
@@ -122,17 +128,15 @@ int dfvo_conv2d(const dfvo_conv_desc* d, const float* d_src0, const float* d_src
     L.act = d->act;
     L.act_param = d->act_param;
     // split-K workspace + tile tickets (as the nets own one each): process-wide, calls are serialised by the sync below
-    static DevBuf conv2d_ws;
+    // (on the heap and never freed: no object with static storage duration holds a DevArr, see dev_mem.h)
+    static DevArr<float>* const conv2d_ws = new DevArr<float>();
     static std::mutex conv2d_mu;
     std::lock_guard<std::mutex> conv2d_lock(conv2d_mu);
-    if (!conv2d_ws.p && conv2d_ws.alloc((size_t)4 << 20) != DFVO_OK) conv2d_ws.p = nullptr;
+    if (!conv2d_ws->p) (void)conv2d_ws->alloc_zeroed((size_t)4 << 20);
     int rc = run_conv(L, d->N, d->H, d->W, View{d_src0, d->cs0, d->co0}, d->up0, View{d_src1, d->cs1, d->co1}, d_res,
                       d->res_cs, d->res_co, d_dst, d->dst_cs, d->dst_co, d->dst_zero_to, s, nullptr,
-                      conv2d_ws.p ? &conv2d_ws : nullptr);
-    hipError_t e = hipStreamSynchronize(s);  // (before the weights are released)
-    if (rc != DFVO_OK) return rc;
-    DFVO_HIP_CHECK(e);
-    return DFVO_OK;
+                      conv2d_ws->p ? conv2d_ws : nullptr);
+    return finish(rc, s);
 }
 
 int dfvo_set_conv_precision(const char* name) { return conv_set_precision(name); }
@@ -163,6 +167,14 @@ int dfvo_correlation(const float* d_first, const float* d_second, int N, int H, 
                               (hipStream_t)stream);
 }
 
+// host table -> a local array of the caller
+static int upload_table(const float* h, int n, DevArr<float>* d) {
+    DFVO_ARG_CHECK(h && n > 0, "null host table");
+    API_TRY(d->alloc((size_t)n));
+    DFVO_HIP_CHECK(hipMemcpy(d->p, h, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    return DFVO_OK;
+}
+
 static std::vector<float> lin_default(int n) {
     std::vector<float> v(n);
     const float step = n > 1 ? 2.f / (float)(n - 1) : 0.f;
@@ -177,36 +189,12 @@ int dfvo_backward_warp(const float* d_src, const float* d_flow, float mult, int 
     hipStream_t s = (hipStream_t)stream;
     std::vector<float> lx = h_lin_x ? std::vector<float>(h_lin_x, h_lin_x + W) : lin_default(W);
     std::vector<float> ly = h_lin_y ? std::vector<float>(h_lin_y, h_lin_y + H) : lin_default(H);
-    float *dx = nullptr, *dy = nullptr;
-    DFVO_HIP_CHECK(hipMalloc((void**)&dx, W * sizeof(float)));
-    DFVO_HIP_CHECK(hipMalloc((void**)&dy, H * sizeof(float)));
+    DevArr<float> dx, dy;  // (nothing is enqueued before launch_warp: the early returns leave no reader behind)
+    API_TRY(dx.alloc(W));
+    API_TRY(dy.alloc(H));
     DFVO_HIP_CHECK(hipMemcpy(dx, lx.data(), W * sizeof(float), hipMemcpyHostToDevice));
     DFVO_HIP_CHECK(hipMemcpy(dy, ly.data(), H * sizeof(float), hipMemcpyHostToDevice));
-    int rc = launch_warp(d_src, C, 0, 0, d_flow, 2, 0, mult, N, H, W, C, dx, dy, d_dst, C, 0, 0, s);
-    hipError_t e = hipStreamSynchronize(s);
-    (void)hipFree(dx);
-    (void)hipFree(dy);
-    if (rc != DFVO_OK) return rc;
-    DFVO_HIP_CHECK(e);
-    return DFVO_OK;
-}
-
-// host table -> device (freed by the caller)
-static int upload_table(const float* h, int n, float** d) {
-    DFVO_ARG_CHECK(h && n > 0, "null host table");
-    DFVO_HIP_CHECK(hipMalloc((void**)d, (size_t)n * sizeof(float)));
-    DFVO_HIP_CHECK(hipMemcpy(*d, h, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    return DFVO_OK;
-}
-
-// launch, wait for the stream, free the temporaries; the launch's error wins over the stream's
-static int finish(int rc, hipStream_t s, std::initializer_list<void*> temps) {
-    hipError_t e = hipStreamSynchronize(s);
-    for (void* t : temps)
-        if (t) (void)hipFree(t);
-    if (rc != DFVO_OK) return rc;
-    DFVO_HIP_CHECK(e);
-    return DFVO_OK;
+    return finish(launch_warp(d_src, C, 0, 0, d_flow, 2, 0, mult, N, H, W, C, dx, dy, d_dst, C, 0, 0, s), s);
 }
 
 int dfvo_warp_view(const float* d_src, int scs, int sco, int swap, const float* d_flow, int fcs, int fco, float mult, int N,
@@ -215,12 +203,12 @@ int dfvo_warp_view(const float* d_src, int scs, int sco, int swap, const float* 
     DFVO_ARG_CHECK(d_src && d_flow && d_dst && N > 0 && H > 1 && W > 1 && C > 0 && step >= 1, "dfvo_warp_view: bad argument");
     DFVO_ARG_CHECK(sco + C <= scs && fco + 2 <= fcs && dco + C + (append_flow ? 4 : 0) <= dcs, "dfvo_warp_view: view too narrow");
     hipStream_t s = (hipStream_t)stream;
-    float *dx = nullptr, *dy = nullptr;
+    DevArr<float> dx, dy;
     int rc = upload_table(h_lin_x, W, &dx);
     if (rc == DFVO_OK) rc = upload_table(h_lin_y, H, &dy);
     if (rc == DFVO_OK)
         rc = launch_warp(d_src, scs, sco, swap, d_flow, fcs, fco, mult, N, H, W, C, dx, dy, d_dst, dcs, dco, append_flow, s, step);
-    return finish(rc, s, {dx, dy});
+    return finish(rc, s);
 }
 
 int dfvo_correlation_view(const float* d_first, int cs1, int co1, const float* d_second, int cs2, int co2, int swap2, int N,
@@ -230,31 +218,31 @@ int dfvo_correlation_view(const float* d_first, int cs1, int co1, const float* d
     DFVO_ARG_CHECK(co1 + C <= cs1 && co2 + C <= cs2 && dcs >= 49, "dfvo_correlation_view: view too narrow");
     hipStream_t s = (hipStream_t)stream;
     return finish(launch_correlation(d_first, cs1, co1, d_second, cs2, co2, swap2, N, H, W, C, stride, d_out, dcs, slope, s),
-                  s, {});
+                  s);
 }
 
 int dfvo_flow_mean(const float* d_flow, int fcs, int fco, int N, int HW, float* d_mean, void* stream) {
     DFVO_ARG_CHECK(d_flow && d_mean && N > 0 && HW > 0 && fco + 2 <= fcs, "dfvo_flow_mean: bad argument");
     hipStream_t s = (hipStream_t)stream;
     const size_t n = flow_mean_scratch_floats(N);
-    float* scratch = nullptr;
-    DFVO_HIP_CHECK(hipMalloc((void**)&scratch, n * sizeof(float)));
-    hipError_t e = hipMemsetAsync(scratch, 0, n * sizeof(float), s);
-    const int rc = e == hipSuccess ? launch_flow_mean(d_flow, fcs, fco, N, HW, scratch, d_mean, s) : DFVO_OK;
-    const int rf = finish(rc, s, {scratch});
-    DFVO_HIP_CHECK(e);
-    return rf;
+    DevArr<float> scratch;
+    API_TRY(scratch.alloc(n));
+    auto enqueue = [&]() -> int {
+        DFVO_HIP_CHECK(hipMemsetAsync(scratch, 0, n * sizeof(float), s));
+        return launch_flow_mean(d_flow, fcs, fco, N, HW, scratch, d_mean, s);
+    };
+    return finish(enqueue(), s);
 }
 
 int dfvo_reg_prep(const float* d_img, const float* d_flow, int fcs, int fco, float mult, const float* d_mean, int N, int H,
                   int W, const float* h_lin_x, const float* h_lin_y, float* d_dst, void* stream) {
     DFVO_ARG_CHECK(d_img && d_flow && d_mean && d_dst && N > 0 && H > 1 && W > 1 && fco + 2 <= fcs, "dfvo_reg_prep: bad argument");
     hipStream_t s = (hipStream_t)stream;
-    float *dx = nullptr, *dy = nullptr;
+    DevArr<float> dx, dy;
     int rc = upload_table(h_lin_x, W, &dx);
     if (rc == DFVO_OK) rc = upload_table(h_lin_y, H, &dy);
     if (rc == DFVO_OK) rc = launch_reg_prep(d_img, d_flow, fcs, fco, mult, d_mean, N, H, W, dx, dy, d_dst, s);
-    return finish(rc, s, {dx, dy});
+    return finish(rc, s);
 }
 
 int dfvo_reg_head(const float* d_dist, int dist_cs, int k, const float* d_flow, int fcs, int fco, const float* h_wx, float bx,
@@ -262,11 +250,11 @@ int dfvo_reg_head(const float* d_dist, int dist_cs, int k, const float* d_flow, 
     DFVO_ARG_CHECK(d_dist && d_flow && d_dst && N > 0 && H > 0 && W > 0 && (k == 3 || k == 5 || k == 7), "dfvo_reg_head: bad argument");
     DFVO_ARG_CHECK(dist_cs >= k * k && fco + 2 <= fcs && dco + 2 <= dcs, "dfvo_reg_head: view too narrow");
     hipStream_t s = (hipStream_t)stream;
-    float *wx = nullptr, *wy = nullptr;
+    DevArr<float> wx, wy;
     int rc = upload_table(h_wx, k * k, &wx);
     if (rc == DFVO_OK) rc = upload_table(h_wy, k * k, &wy);
     if (rc == DFVO_OK) rc = launch_reg_head(d_dist, dist_cs, k, d_flow, fcs, fco, wx, bx, wy, by, N, H, W, d_dst, dcs, dco, s);
-    return finish(rc, s, {wx, wy});
+    return finish(rc, s);
 }
 
 int dfvo_flow_post(const float* d_netflow, int fcs, int fco, int h, int w, float scale, int H, int W, float* d_fwd,
@@ -274,13 +262,13 @@ int dfvo_flow_post(const float* d_netflow, int fcs, int fco, int h, int w, float
     DFVO_ARG_CHECK(d_netflow && d_fwd && d_bwd && d_diff && h > 0 && w > 0 && H > 1 && W > 1 && fco + 2 <= fcs,
                    "dfvo_flow_post: bad argument");
     hipStream_t s = (hipStream_t)stream;
-    return finish(launch_flow_post(d_netflow, fcs, fco, h, w, scale, H, W, d_fwd, d_bwd, d_diff, s), s, {});
+    return finish(launch_flow_post(d_netflow, fcs, fco, h, w, scale, H, W, d_fwd, d_bwd, d_diff, s), s);
 }
 
 int dfvo_img_u8_to_flow_input(const uint8_t* d_img, int H, int W, float* d_dst, int th, int tw, void* stream) {
     DFVO_ARG_CHECK(d_img && d_dst && H > 0 && W > 0 && th > 0 && tw > 0, "dfvo_img_u8_to_flow_input: bad argument");
     hipStream_t s = (hipStream_t)stream;
-    return finish(launch_img_u8_to_flow_input(d_img, H, W, d_dst, th, tw, s), s, {});
+    return finish(launch_img_u8_to_flow_input(d_img, H, W, d_dst, th, tw, s), s);
 }
 
 int dfvo_maxpool3x3s2(const float* d_src, int N, int H, int W, int C, float* d_dst, void* stream) {
@@ -296,15 +284,10 @@ int dfvo_deconv_dw4x4s2(const float* d_src, int N, int H, int W, int C, int cs, 
                         void* stream) {
     DFVO_ARG_CHECK(d_src && h_weight && d_dst && cs >= C, "dfvo_deconv_dw4x4s2: bad argument");
     hipStream_t s = (hipStream_t)stream;
-    float* dw = nullptr;
-    DFVO_HIP_CHECK(hipMalloc((void**)&dw, (size_t)C * 16 * sizeof(float)));
+    DevArr<float> dw;
+    API_TRY(dw.alloc((size_t)C * 16));
     DFVO_HIP_CHECK(hipMemcpy(dw, h_weight, (size_t)C * 16 * sizeof(float), hipMemcpyHostToDevice));
-    int rc = launch_deconv_dw(d_src, cs, 0, N, H, W, C, dw, d_dst, cs, 0, s);
-    hipError_t e = hipStreamSynchronize(s);
-    (void)hipFree(dw);
-    if (rc != DFVO_OK) return rc;
-    DFVO_HIP_CHECK(e);
-    return DFVO_OK;
+    return finish(launch_deconv_dw(d_src, cs, 0, N, H, W, C, dw, d_dst, cs, 0, s), s);
 }
 
 int dfvo_resize_bilinear(const float* d_src, int N, int H, int W, int C, float* d_dst, int Ho, int Wo,
@@ -340,9 +323,7 @@ int dfvo_flownet_create(int img_h, int img_w, void* stream, dfvo_flownet** out) 
     return DFVO_OK;
 }
 void dfvo_flownet_destroy(dfvo_flownet* n) {
-    if (!n) return;
-    n->net.destroy();
-    delete n;
+    delete n;  // (null is fine; FlowNet's destructor and its arrays do the rest)
 }
 int dfvo_flownet_set_param(dfvo_flownet* n, const char* name, const float* h, int ndim, const int* shape) {
     DFVO_ARG_CHECK(n, "null net");
@@ -429,10 +410,6 @@ int dfvo_depthnet_create(int feed_h, int feed_w, float min_depth, float max_dept
     return DFVO_OK;
 }
 void dfvo_depthnet_destroy(dfvo_depthnet* n) {
-    if (!n) return;
-    n->net.destroy();
-    n->resize.release();
-    if (n->img_full) (void)hipFree(n->img_full);
     delete n;
 }
 int dfvo_depthnet_set_param(dfvo_depthnet* n, const char* name, const float* h, int ndim, const int* shape) {
@@ -471,13 +448,7 @@ int dfvo_depthnet_forward_image_host(dfvo_depthnet* n, const uint8_t* h_img, int
     if (n->resize.H != img_h || n->resize.W != img_w || n->resize.oh != d.H || n->resize.ow != d.W)
         API_TRY(n->resize.init(img_h, img_w, d.H, d.W));
     const size_t bytes = (size_t)img_h * img_w * 3;
-    if (bytes > n->img_full_bytes) {
-        if (n->img_full) (void)hipFree(n->img_full);
-        n->img_full = nullptr;
-        n->img_full_bytes = 0;
-        DFVO_HIP_CHECK(hipMalloc((void**)&n->img_full, bytes));
-        n->img_full_bytes = bytes;
-    }
+    API_TRY(n->img_full.grow(bytes));
     const size_t px = (size_t)d.H * d.W;
     DFVO_HIP_CHECK(hipMemcpyAsync(n->img_full, h_img, bytes, hipMemcpyHostToDevice, d.stream));
     API_TRY(n->resize.enqueue(n->img_full, (uint8_t*)d.u8_in.p, d.stream));
@@ -494,11 +465,7 @@ int dfvo_resize_lanczos_u8(const uint8_t* d_src, int H, int W, uint8_t* d_dst, i
     LanczosResizer r;
     int rc = r.init(H, W, out_h, out_w);
     if (rc == DFVO_OK) rc = r.enqueue(d_src, d_dst, (hipStream_t)stream);
-    hipError_t e = hipStreamSynchronize((hipStream_t)stream);  // the tables die with r
-    r.release();
-    if (rc != DFVO_OK) return rc;
-    DFVO_HIP_CHECK(e);
-    return DFVO_OK;
+    return finish(rc, (hipStream_t)stream);  // the tables die with r, behind the wait
 }
 int dfvo_resize_linear_u8(const uint8_t* d_src, int H, int W, int C, uint8_t* d_dst, int out_h, int out_w, void* stream) {
     return enqueue_resize_linear_u8(d_src, H, W, C, d_dst, out_h, out_w, (hipStream_t)stream);

@@ -322,17 +322,8 @@ int dfvo_kp_sampled(dfvo_tracker* t, const float* h_flow, int H, int W, int y0, 
     return rc;
 }
 
-int dfvo_kp_rigid_flow(dfvo_tracker* t, const float* h_flow, const float* h_flow_diff, const float* h_raw_depth, int H,
-                       int W, const dfvo_rigid_kp_cfg* cfg, const float* h_rigid_diff_override, double* h_kp1_best,
-                       double* h_kp2_best, double* h_kp1_uniform, double* h_kp2_uniform, int* n_out,
-                       float* h_rigid_flow_diff) {
-    DFVO_ARG_CHECK(t && h_flow && h_flow_diff && h_raw_depth && cfg && h_kp1_best && h_kp2_best && h_kp1_uniform &&
-                       h_kp2_uniform && n_out && H > 0 && W > 0,
-                   "dfvo_kp_rigid_flow: bad argument");
-    DFVO_ARG_CHECK(cfg->score_method == 0 || cfg->score_method == 1, "dfvo_kp_rigid_flow: score_method");
-    const size_t px = (size_t)H * W;
-    if (int rc_f = stage_flow(t, px)) return rc_f;
-    RigidKpConfig rc;
+static int rigid_config_from(const dfvo_rigid_kp_cfg* cfg, RigidKpConfig* out) {
+    RigidKpConfig& rc = *out;
     rc.num_row = cfg->num_row;
     rc.num_col = cfg->num_col;
     rc.num_bestN = cfg->num_bestN;
@@ -344,6 +335,38 @@ int dfvo_kp_rigid_flow(dfvo_tracker* t, const float* h_flow, const float* h_flow
         rc.Kinv[i] = (float)cfg->Kinv[i];
     }
     for (int i = 0; i < 16; i++) rc.T[i] = (float)cfg->T_ref_to_cur[i];
+    return DFVO_OK;
+}
+
+// (the caller checks min_samples and method)
+static ScaleConfig scale_config_from(const dfvo_scale_cfg* cfg) {
+    ScaleConfig sc;
+    sc.cx = cfg->cx, sc.cy = cfg->cy, sc.fx = cfg->fx, sc.fy = cfg->fy;
+    sc.min_samples = cfg->min_samples, sc.max_trials = cfg->max_trials;
+    sc.stop_prob = cfg->stop_prob, sc.thre = cfg->thre, sc.method = cfg->method;
+    return sc;
+}
+
+static void scale_info_from(const ScaleResult& sr, int* h_info) {
+    if (!h_info) return;
+    h_info[0] = sr.n_valid;
+    h_info[1] = sr.n_trials;
+    h_info[2] = sr.n_inliers;
+    h_info[3] = sr.status;
+}
+
+int dfvo_kp_rigid_flow(dfvo_tracker* t, const float* h_flow, const float* h_flow_diff, const float* h_raw_depth, int H,
+                       int W, const dfvo_rigid_kp_cfg* cfg, const float* h_rigid_diff_override, double* h_kp1_best,
+                       double* h_kp2_best, double* h_kp1_uniform, double* h_kp2_uniform, int* n_out,
+                       float* h_rigid_flow_diff) {
+    DFVO_ARG_CHECK(t && h_flow && h_flow_diff && h_raw_depth && cfg && h_kp1_best && h_kp2_best && h_kp1_uniform &&
+                       h_kp2_uniform && n_out && H > 0 && W > 0,
+                   "dfvo_kp_rigid_flow: bad argument");
+    DFVO_ARG_CHECK(cfg->score_method == 0 || cfg->score_method == 1, "dfvo_kp_rigid_flow: score_method");
+    const size_t px = (size_t)H * W;
+    if (int rc_f = stage_flow(t, px)) return rc_f;
+    RigidKpConfig rc;
+    rigid_config_from(cfg, &rc);
     DFVO_ARG_CHECK(rc.num_row > 0 && rc.num_col > 0, "dfvo_kp_rigid_flow: grid");
     const int cells = rc.num_row * rc.num_col;
     int rcode = t->rigid.ensure(H, W, cells, rc.num_bestN / cells > 0 ? rc.num_bestN / cells : 1,
@@ -423,18 +446,9 @@ static int find_scale_impl(dfvo_tracker* t, const double* h_kp1, const double* h
     if (!(per_kp && n == 0))  // (a zero-length per-keypoint array has no element to read)
         DFVO_HIP_CHECK(hipMemcpyAsync(t->d_depth, h_depth, sizeof(double) * px, hipMemcpyHostToDevice, t->stream));
     DFVO_HIP_CHECK(hipMemcpyAsync(t->d_small, h_T21, 16 * sizeof(double), hipMemcpyHostToDevice, t->stream));
-    ScaleConfig sc;
-    sc.cx = cfg->cx;
-    sc.cy = cfg->cy;
-    sc.fx = cfg->fx;
-    sc.fy = cfg->fy;
-    sc.min_samples = cfg->min_samples;
-    sc.max_trials = cfg->max_trials;
-    sc.stop_prob = cfg->stop_prob;
-    sc.thre = cfg->thre;
     DFVO_ARG_CHECK(cfg->method == DFVO_SCALE_DEPTH_RATIO || cfg->method == DFVO_SCALE_ABS_DIFF,
                    "dfvo_find_scale_from_depth: unknown method");
-    sc.method = cfg->method;
+    const ScaleConfig sc = scale_config_from(cfg);
     rc = enqueue_find_scale(t->tb, n, t->d_small, t->d_depth, H, W, sc, t->stream, nullptr, false, per_kp);
     if (rc != DFVO_OK) return rc;
     ScaleResult sr;
@@ -443,12 +457,7 @@ static int find_scale_impl(dfvo_tracker* t, const double* h_kp1, const double* h
         DFVO_HIP_CHECK(hipMemcpyAsync(h_rng625, t->tb.mt_state, 625 * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream));
     DFVO_HIP_CHECK(hipStreamSynchronize(t->stream));
     *scale = sr.scale;
-    if (h_info) {
-        h_info[0] = sr.n_valid;
-        h_info[1] = sr.n_trials;
-        h_info[2] = sr.n_inliers;
-        h_info[3] = sr.status;
-    }
+    scale_info_from(sr, h_info);
     return DFVO_OK;
 }
 
@@ -462,22 +471,6 @@ int dfvo_find_scale_from_depth_at_kp(dfvo_tracker* t, const double* h_kp1, const
                                      const double* h_depth_at_kp2, int H, int W, const dfvo_scale_cfg* cfg,
                                      uint32_t* h_rng625, double* scale, int* h_info) {
     return find_scale_impl(t, h_kp1, h_kp2, n, h_T21, h_depth_at_kp2, true, H, W, cfg, h_rng625, scale, h_info);
-}
-
-static int rigid_config_from(const dfvo_rigid_kp_cfg* cfg, RigidKpConfig* out) {
-    RigidKpConfig& rc = *out;
-    rc.num_row = cfg->num_row;
-    rc.num_col = cfg->num_col;
-    rc.num_bestN = cfg->num_bestN;
-    rc.rigid_thre = (float)cfg->rigid_flow_thre;
-    rc.opt_thre = (float)cfg->optical_flow_thre;
-    rc.score_rigid = cfg->score_method;
-    for (int i = 0; i < 9; i++) {
-        rc.K[i] = (float)cfg->K[i];
-        rc.Kinv[i] = (float)cfg->Kinv[i];
-    }
-    for (int i = 0; i < 16; i++) rc.T[i] = (float)cfg->T_ref_to_cur[i];
-    return DFVO_OK;
 }
 
 int dfvo_scale_recovery_iterative(dfvo_tracker* t, const float* h_flow, const float* h_flow_diff, const float* h_raw_depth_ref,
@@ -506,10 +499,7 @@ int dfvo_scale_recovery_iterative(dfvo_tracker* t, const float* h_flow, const fl
     const int n_sel = cells * n_best;
     DFVO_ARG_CHECK((kp_src == DFVO_ITER_KP_DEPTH ? n_sel : n_kp_best) <= ITER_MAX_KP,
                    "dfvo_scale_recovery_iterative: more keypoints than the depth-ratio kernel holds in 64 KB of LDS (16384)");
-    ScaleConfig sc;
-    sc.cx = scfg->cx, sc.cy = scfg->cy, sc.fx = scfg->fx, sc.fy = scfg->fy;
-    sc.min_samples = scfg->min_samples, sc.max_trials = scfg->max_trials;
-    sc.stop_prob = scfg->stop_prob, sc.thre = scfg->thre, sc.method = scfg->method;
+    const ScaleConfig sc = scale_config_from(scfg);
     const size_t px = (size_t)H * W;
     if (int rc_f = stage_flow(t, px)) return rc_f;
     if (int rc_d = stage_depth(t, px)) return rc_d;
@@ -600,12 +590,8 @@ int dfvo_ransac_regressor(dfvo_tracker* t, const double* h_x, const double* h_y,
     DFVO_HIP_CHECK(hipMemcpyAsync(t->tb.ratios, h_x, sizeof(double) * n, hipMemcpyHostToDevice, t->stream));
     if (h_y)
         DFVO_HIP_CHECK(hipMemcpyAsync(t->tb.ratios + t->tb.kp_cap, h_y, sizeof(double) * n, hipMemcpyHostToDevice, t->stream));
-    ScaleConfig sc;
+    ScaleConfig sc = scale_config_from(cfg);  // (no camera; the method follows h_y)
     sc.cx = sc.cy = sc.fx = sc.fy = 0;
-    sc.min_samples = cfg->min_samples;
-    sc.max_trials = cfg->max_trials;
-    sc.stop_prob = cfg->stop_prob;
-    sc.thre = cfg->thre;
     sc.method = h_y ? 1 : 0;
     rc = enqueue_ransac_regressor(t->tb, n, h_y == nullptr, sc, t->stream);
     if (rc != DFVO_OK) return rc;
@@ -613,12 +599,7 @@ int dfvo_ransac_regressor(dfvo_tracker* t, const double* h_x, const double* h_y,
     DFVO_HIP_CHECK(hipMemcpyAsync(&sr, t->tb.scale_out, sizeof(sr), hipMemcpyDeviceToHost, t->stream));
     DFVO_HIP_CHECK(hipStreamSynchronize(t->stream));
     *coef = sr.scale;
-    if (h_info) {
-        h_info[0] = sr.n_valid;
-        h_info[1] = sr.n_trials;
-        h_info[2] = sr.n_inliers;
-        h_info[3] = sr.status;
-    }
+    scale_info_from(sr, h_info);
     return DFVO_OK;
 }
 

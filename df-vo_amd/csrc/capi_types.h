@@ -13,8 +13,7 @@ struct dfvo_flownet {
 struct dfvo_depthnet {
     dfvo::DepthNet net;
     dfvo::LanczosResizer resize;  // dfvo_depthnet_forward_image_host / the session: tables for the last image size seen
-    uint8_t* img_full = nullptr;
-    size_t img_full_bytes = 0;
+    dfvo::DevArr<uint8_t> img_full;  // the full-size frame of dfvo_depthnet_forward_image_host, grown on demand
 };
 struct dfvo_tracker {
     hipStream_t stream = nullptr;

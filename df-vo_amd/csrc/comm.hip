@@ -16,7 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "dfvo_common.h"
+#include "dev_mem.h"
 
 namespace dfvo {
 namespace {
@@ -70,8 +70,7 @@ struct dfvo_comm {
     int world = 1, rank = 0;
     int device = -1;  // the HIP device that was current at dfvo_comm_create: every collective must be issued on it
     hipStream_t stream = nullptr;
-    double *d_send = nullptr, *d_recv = nullptr;
-    size_t cap_rows = 0;  // rows per rank the staging buffers hold
+    dfvo::DevArr<double> d_send, d_recv;  // staging: rows of one rank, rows of every rank
 };
 
 #define DFVO_NCCL_CHECK(expr)                                                                                   \
@@ -131,10 +130,8 @@ int dfvo_comm_destroy(dfvo_comm* c) {
     dfvo::Rccl* R = dfvo::rccl();
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm && R->CommDestroy) (void)R->CommDestroy(c->comm);
-    if (c->d_send) (void)hipFree(c->d_send);
-    if (c->d_recv) (void)hipFree(c->d_recv);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // (the staging arrays)
     return DFVO_OK;
 }
 
@@ -160,14 +157,11 @@ int dfvo_allgather_poses(dfvo_comm* c, const double* h_rows, int n_local, const 
         nmax = counts[r] > nmax ? counts[r] : nmax;
     }
     if (nmax == 0) return DFVO_OK;
-    if ((size_t)nmax > c->cap_rows) {
-        if (c->d_send) (void)hipFree(c->d_send);
-        if (c->d_recv) (void)hipFree(c->d_recv);
-        c->d_send = c->d_recv = nullptr;
-        c->cap_rows = 0;
-        DFVO_HIP_CHECK(hipMalloc(&c->d_send, (size_t)nmax * DFVO_POSE_ROW * sizeof(double)));
-        DFVO_HIP_CHECK(hipMalloc(&c->d_recv, (size_t)nmax * DFVO_POSE_ROW * sizeof(double) * c->world));
-        c->cap_rows = (size_t)nmax;
+    const size_t need = (size_t)nmax * DFVO_POSE_ROW;
+    if (need > c->d_send.n || need * c->world > c->d_recv.n) {
+        c->d_send.release();
+        c->d_recv.release();
+        if (c->d_send.alloc(need) != DFVO_OK || c->d_recv.alloc(need * c->world) != DFVO_OK) return DFVO_ERR_HIP;
     }
     const size_t row_b = DFVO_POSE_ROW * sizeof(double);
     DFVO_HIP_CHECK(hipMemsetAsync(c->d_send, 0, (size_t)nmax * row_b, c->stream));

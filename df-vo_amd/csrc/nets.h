@@ -6,7 +6,13 @@
 #include <string>
 #include <vector>
 
-#include "dfvo_common.h"
+#include "dev_mem.h"
+
+#define DFVO_TRY(expr)                   \
+    do {                                 \
+        int _rc = (expr);                \
+        if (_rc != DFVO_OK) return _rc;  \
+    } while (0)
 
 namespace dfvo {
 
@@ -15,27 +21,19 @@ struct HostTensor {
     std::vector<int> shape;
 };
 
-struct DevBuf {
-    float* p = nullptr;
-    size_t n = 0;
-    int alloc(size_t floats);  // zero-filled
-    void release();
-};
-
 struct ConvLayer {
-    float* wp = nullptr;
-    float* bias = nullptr;
-    unsigned short* wf = nullptr;  // f16 hi/lo planes for conv_win_f16s_kernel (DFVO_CONV_PRECISION=f16x3, 3x3 layers)
+    DevArr<float> wp, bias;
+    DevArr<unsigned short> wf;  // f16 hi/lo planes for conv_win_f16s_kernel (DFVO_CONV_PRECISION=f16x3, 3x3 layers)
     int wf_cout_pad = 0;
-    unsigned short* wg = nullptr;  // f16 hi/lo planes in k-group order for conv_gemm_f16s_kernel (f16x3 mode, every layer)
-    uint32_t* gtab = nullptr;      // its k-group table
-    float* wg32 = nullptr;         // fp32 weights in the same k-group order for conv_gemm_f32g_kernel (fp32 mode, every layer)
+    DevArr<unsigned short> wg;  // f16 hi/lo planes in k-group order for conv_gemm_f16s_kernel (f16x3 mode, every layer)
+    DevArr<uint32_t> gtab;      // its k-group table
+    DevArr<float> wg32;         // fp32 weights in the same k-group order for conv_gemm_f32g_kernel (fp32 mode, every layer)
     int wg_cout_pad = 0, g_steps = 0;
     long long m_hint = 0;          // output pixels the layer was built for (0: unknown, dfvo_conv2d) -- gates optional packings
     int f16_terms = 3;             // 1: packed in "f16" mode (one product per term; the kernels never read the lo planes)
     int wino_mode = 0;    // dfvo_set_fp32_winograd's value when wu was packed: 1 the size rule decides per launch, 2 every applicable launch
-    float* wu = nullptr;  // Winograd U (fp32 mode with dfvo_set_fp32_winograd on, applicable 3x3 layers), see conv_pack_wino_f32.h
-    float* wh = nullptr;  // head layout (cout <= 2, square 3/5/7 kernels), see conv_pack_head_weights
+    DevArr<float> wu;     // Winograd U (fp32 mode with dfvo_set_fp32_winograd on, applicable 3x3 layers), see conv_pack_wino_f32.h
+    DevArr<float> wh;     // head layout (cout <= 2, square 3/5/7 kernels), see conv_pack_head_weights
     int cout = 0, cout_pad = 0, c0 = 0, c1 = 0, kh = 0, kw = 0, ksteps = 0;
     int stride = 1, pad_h = 0, pad_w = 0, pad_mode = PAD_ZERO, act = ACT_NONE;
     float act_param = 0.f;
@@ -47,20 +45,20 @@ struct ParamStore {
     const HostTensor* get(const std::string& name) const;
 };
 
-// builds + uploads a conv layer from OIHW weights; scale/shift fold an eval BatchNorm.  wino_geometry false: the layer will
-// run with a stride, reflection padding or an upsampled source -- no Winograd weights are packed for it
+// The layer packing (net_layers.hip, host only).  make_conv builds + uploads a conv layer from OIHW weights, releasing whatever
+// packing the layer held; scale/shift fold an eval BatchNorm.  wino_geometry false: the layer will run with a stride,
+// reflection padding or an upsampled source -- no Winograd weights are packed for it
 int make_conv(const ParamStore& ps, const std::string& wname, const std::string& bname, int c0, int c1,
               long long M_hint, const float* scale, const float* shift, ConvLayer* out, bool wino_geometry = true);
-void free_conv(ConvLayer* l);
-// uploads the head-layout copy of the weights when the layer qualifies for the direct head kernel (else leaves wh null)
 int make_f16s_weights(const float* w_oihw, int cout, int c0, int c1, int kh, int kw, const float* scale, ConvLayer* L);
 int make_f16g_weights(const float* w_oihw, int cout, int c0, int c1, int kh, int kw, const float* scale, ConvLayer* L);
 int make_wino_weights(const float* w_oihw, int cout, int c0, int c1, int kh, int kw, const float* scale, bool geometry_ok,
                       ConvLayer* L);
-int conv_set_precision(const char* name);  // fp32 | f16x3 | f16: applies to layers packed afterwards
+// uploads the head-layout copy of the weights when the layer qualifies for the direct head kernel (else leaves wh empty)
+int make_head_weights(const float* w_oihw, int cout, int c0, int c1, int kh, int kw, const float* scale, ConvLayer* L);
+int upload_floats(const std::vector<float>& h, DevArr<float>* d);
+int conv_set_precision(const char* name);  // fp32 | f16x3 | f16: applies to layers packed afterwards (nets.hip)
 const char* conv_get_precision();
-int make_head_weights(const float* w_oihw, int cout, int c0, int c1, int kh, int kw, const float* scale, float** wh);
-
 
 struct View {
     const float* p;
@@ -69,7 +67,7 @@ struct View {
 
 int run_conv(const ConvLayer& L, int N, int H, int W, View s0, int up0, View s1, const float* res, int res_cs,
              int res_co, float* dst, int dst_cs, int dst_co, int dst_zero_to, hipStream_t s, double* flops,
-             const DevBuf* splitk_ws = nullptr);
+             const DevArr<float>* splitk_ws = nullptr);
 
 // ------------------------------------------------------------------------------------------------
 // flow-net input size for an image size, exactly as the reference's DeepFlow.get_target_size evaluates (nets.hip)
@@ -85,21 +83,21 @@ struct FlowNet {
 
     // per level l = 1..6 (index l)
     int lh[7], lw[7], lc[7];
-    DevBuf img[7], feat[7];
-    DevBuf lin_x[7], lin_y[7];
+    DevArr<float> img[7], feat[7];
+    DevArr<float> lin_x[7], lin_y[7];
     std::vector<ConvLayer> feat_convs;  // 12 convs of Features
     struct Level {
         ConvLayer m_feat, m_main[4], s_feat, s_main[4], r_feat, r_main[6], r_dist[2];
         bool has_mfeat = false, has_upflow = false, has_upcorr = false, has_rfeat = false, dist_sep = false;
-        DevBuf upflow_w, upcorr_w, scale_wx, scale_wy;
+        DevArr<float> upflow_w, upcorr_w, scale_wx, scale_wy;
         float scale_bx = 0.f, scale_by = 0.f;
         // activations
-        DevBuf mfeat, sfeat, rfeat, flow_up, warped, corr, corr_up, x128, x64, x32, x128b, x64b, x32b, flowM, b1,
+        DevArr<float> mfeat, sfeat, rfeat, flow_up, warped, corr, corr_up, x128, x64, x32, x128b, x64b, x32b, flowM, b1,
             flowS, r0, dist_a, dist_b, flow, mean;
     } lv[7];
-    DevBuf u8_ref, u8_cur;  // staging for the host-pointer entry point
-    DevBuf splitk;          // split-K partial sums of the small-grid convs (own buffer: the nets run on separate streams)
-    DevBuf out_fwd, out_bwd, out_diff;
+    DevArr<float> u8_ref, u8_cur;  // staging for the host-pointer entry point
+    DevArr<float> splitk;          // split-K partial sums of the small-grid convs (own buffer: the nets run on separate streams)
+    DevArr<float> out_fwd, out_bwd, out_diff;
     // counts the forward() calls: every one overwrites the output buffers it is handed (out_fwd / out_bwd / out_diff for the
     // host-array entry points and the frame session).  A holder of device-resident outputs remembers the count of ITS pass
     // and knows them overwritten when it has moved on (session.hip: dfvo_session_vis_sources)
@@ -130,7 +128,8 @@ struct FlowNet {
     int enqueue_carry(const FlowNet& src);
     int enqueue_levels(float* d_fwd, float* d_bwd, float* d_diff);
     int enqueue(float* d_fwd, float* d_bwd, float* d_diff);  // Features of both frames + levels
-    void destroy();
+    void destroy();  // graphs, e_feat and the owned stream (the arrays release themselves); idempotent
+    ~FlowNet() { destroy(); }
 };
 
 struct DepthNet {
@@ -147,9 +146,9 @@ struct DepthNet {
         bool has_ds = false;
     } blocks[8];
     ConvLayer up[5][2], dispconv;
-    DevBuf x0, f0, pool, tmp[4], feat[5], blk_t, blk_ds, blk_o[2], du[5], dx[5], disp, depth;
-    DevBuf u8_in;
-    DevBuf splitk;
+    DevArr<float> x0, pool, feat[5], blk_t, blk_ds, blk_o[2], du[5], dx[5], disp, depth;
+    DevArr<float> u8_in;
+    DevArr<float> splitk;
     unsigned long long out_epoch = 0;  // forward() calls so far (see FlowNet::out_epoch)
     double flops_last = 0.0;
     hipGraph_t graph = nullptr;
@@ -163,7 +162,8 @@ struct DepthNet {
     int finalize();
     int forward(const uint8_t* d_img, float* d_depth);
     int enqueue(const uint8_t* d_img, float* d_depth);
-    void destroy();
+    void destroy();  // the graph and the owned stream; idempotent
+    ~DepthNet() { destroy(); }
 };
 
 }  // namespace dfvo

@@ -16,71 +16,6 @@
 
 namespace dfvo {
 
-int DevBuf::alloc(size_t floats) {
-    release();
-    n = floats;
-    DFVO_HIP_CHECK(hipMalloc((void**)&p, floats * sizeof(float)));
-    DFVO_HIP_CHECK(hipMemset(p, 0, floats * sizeof(float)));
-    return DFVO_OK;
-}
-void DevBuf::release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-}
-
-const HostTensor* ParamStore::get(const std::string& name) const {
-    auto it = t.find(name);
-    return it == t.end() ? nullptr : &it->second;
-}
-
-#define DFVO_TRY(expr)                   \
-    do {                                 \
-        int _rc = (expr);                \
-        if (_rc != DFVO_OK) return _rc;  \
-    } while (0)
-
-static int upload(const std::vector<float>& h, DevBuf* d) {
-    DFVO_TRY(d->alloc(h.size()));
-    DFVO_HIP_CHECK(hipMemcpy(d->p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    return DFVO_OK;
-}
-
-int make_conv(const ParamStore& ps, const std::string& wname, const std::string& bname, int c0, int c1,
-              long long M_hint, const float* scale, const float* shift, ConvLayer* L, bool wino_geometry) {
-    const HostTensor* w = ps.get(wname);
-    if (!w) {
-        set_last_error("missing parameter " + wname);
-        return DFVO_ERR_STATE;
-    }
-    DFVO_ARG_CHECK(w->shape.size() == 4, "conv weight must be 4-D: " + wname);
-    const HostTensor* b = bname.empty() ? nullptr : ps.get(bname);
-    if (!bname.empty() && !b) {
-        set_last_error("missing parameter " + bname);
-        return DFVO_ERR_STATE;
-    }
-    L->cout = w->shape[0];
-    DFVO_ARG_CHECK(w->shape[1] == c0 + c1, "conv weight cin mismatch: " + wname);
-    L->c0 = c0;
-    L->c1 = c1;
-    L->kh = w->shape[2];
-    L->kw = w->shape[3];
-    L->cout_pad = conv_cout_pad(L->cout, M_hint);
-    L->m_hint = M_hint;
-    L->ksteps = conv_ksteps(L->kh, L->kw, c0, c1);
-    std::vector<float> pw((size_t)(L->ksteps * 4 + 8) * L->cout_pad * 4), pb(L->cout_pad);  // +8 k-groups: the window kernel rounds each source up to 4 groups
-    conv_pack_weights(w->data.data(), b ? b->data.data() : nullptr, L->cout, c0, c1, L->kh, L->kw, L->cout_pad,
-                      scale, shift, pw.data(), pb.data());
-    DFVO_HIP_CHECK(hipMalloc((void**)&L->wp, pw.size() * sizeof(float)));
-    DFVO_HIP_CHECK(hipMalloc((void**)&L->bias, pb.size() * sizeof(float)));
-    DFVO_HIP_CHECK(hipMemcpy(L->wp, pw.data(), pw.size() * sizeof(float), hipMemcpyHostToDevice));
-    DFVO_HIP_CHECK(hipMemcpy(L->bias, pb.data(), pb.size() * sizeof(float), hipMemcpyHostToDevice));
-    DFVO_TRY(make_f16s_weights(w->data.data(), L->cout, c0, c1, L->kh, L->kw, scale, L));
-    DFVO_TRY(make_f16g_weights(w->data.data(), L->cout, c0, c1, L->kh, L->kw, scale, L));
-    DFVO_TRY(make_wino_weights(w->data.data(), L->cout, c0, c1, L->kh, L->kw, scale, wino_geometry, L));
-    return make_head_weights(w->data.data(), L->cout, c0, c1, L->kh, L->kw, scale, &L->wh);
-}
-
 static int parse_conv_precision(const char* e) {
     if (!e || !strcmp(e, "fp32")) return 0;
     if (!strcmp(e, "f16x3")) return 4;
@@ -107,96 +42,6 @@ const char* conv_get_precision() {
     return m == 4 ? "f16x3" : m == 5 ? "f16" : "fp32";
 }
 
-int make_f16s_weights(const float* w_oihw, int cout, int c0, int c1, int kh, int kw, const float* scale, ConvLayer* L) {
-    L->f16_terms = conv_split_mode() == 5 ? 1 : 3;
-    if (conv_split_mode() < 4 || kh != 3 || kw != 3) return DFVO_OK;
-    std::vector<unsigned short> wf(conv_pack_weights_f16s(w_oihw, cout, c0, c1, scale, nullptr));
-    conv_pack_weights_f16s(w_oihw, cout, c0, c1, scale, wf.data());
-    DFVO_HIP_CHECK(hipMalloc((void**)&L->wf, wf.size() * sizeof(unsigned short) + 256));
-    DFVO_HIP_CHECK(hipMemcpy(L->wf, wf.data(), wf.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-    L->wf_cout_pad = round_up(cout, 32);
-    return DFVO_OK;
-}
-
-int make_f16g_weights(const float* w_oihw, int cout, int c0, int c1, int kh, int kw, const float* scale, ConvLayer* L) {
-    // exact fp32: the register-ring kernel's fp32 weights + the table -- only for layers launch_conv can send there
-    // (conv_f32g_takes: launches of at most 8192 output pixels, not the one- / two-channel heads).  m_hint is the builder's
-    // pixel count of the layer's INPUT map for the whole batch: a stride-2 Features layer launched one frame at a time has an
-    // eighth of it, hence the factor.  The large-map layers used to carry a second, never-read copy of their weights
-    // (round-4 advisor); dfvo_conv2d (no hint) packs always.
-    if (conv_split_mode() == 0 && kh <= 31 && kw <= 31 && (L->m_hint <= 0 || L->m_hint <= 8 * 8192) && cout > 2) {
-        std::vector<float> wg(conv_pack_weights_f32g(w_oihw, cout, c0, c1, kh, kw, scale, nullptr));
-        conv_pack_weights_f32g(w_oihw, cout, c0, c1, kh, kw, scale, wg.data());
-        std::vector<uint32_t> tab;
-        conv_build_f16g_table(c0, c1, kh, kw, &tab);
-        DFVO_HIP_CHECK(hipMalloc((void**)&L->wg32, wg.size() * sizeof(float) + 256));
-        DFVO_HIP_CHECK(hipMemcpy(L->wg32, wg.data(), wg.size() * sizeof(float), hipMemcpyHostToDevice));
-        DFVO_HIP_CHECK(hipMalloc((void**)&L->gtab, tab.size() * sizeof(uint32_t) + 256));
-        DFVO_HIP_CHECK(hipMemcpy(L->gtab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        L->wg_cout_pad = round_up(cout, 32);
-        L->g_steps = (int)(tab.size() / 4);
-        return DFVO_OK;
-    }
-    if (conv_split_mode() < 4 || kh > 31 || kw > 31) return DFVO_OK;
-    std::vector<unsigned short> wg(conv_pack_weights_f16g(w_oihw, cout, c0, c1, kh, kw, scale, nullptr));
-    conv_pack_weights_f16g(w_oihw, cout, c0, c1, kh, kw, scale, wg.data());
-    std::vector<uint32_t> tab;
-    conv_build_f16g_table(c0, c1, kh, kw, &tab);
-    DFVO_HIP_CHECK(hipMalloc((void**)&L->wg, wg.size() * sizeof(unsigned short) + 256));
-    DFVO_HIP_CHECK(hipMemcpy(L->wg, wg.data(), wg.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-    DFVO_HIP_CHECK(hipMalloc((void**)&L->gtab, tab.size() * sizeof(uint32_t) + 256));
-    DFVO_HIP_CHECK(hipMemcpy(L->gtab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    L->wg_cout_pad = round_up(cout, 32);
-    L->g_steps = (int)(tab.size() / 4);
-    return DFVO_OK;
-}
-
-// fp32 Winograd: U of the 3x3 layers packed in "fp32" while the switch is on.  The decision is the layer's from here on
-// (launch_conv looks at the pointer, never at the switch), so a captured graph replays what was packed.  U is 16 / 9 of the
-// weight bytes: it is not packed for a layer that no launch can hand to the kernel -- geometry_ok false (the builder knows
-// the layer runs with a stride, reflection padding or the upsampled source), or, in mode 1, a width or a map (m_hint pixels
-// at the most) that the size rule never accepts.  launch_conv still declines per launch what the kernel does not compute.
-int make_wino_weights(const float* w_oihw, int cout, int c0, int c1, int kh, int kw, const float* scale, bool geometry_ok,
-                      ConvLayer* L) {
-    L->wino_mode = 0;
-    const int mode = conv_fp32_winograd_mode();
-    if (conv_split_mode() != 0 || mode == 0 || kh != 3 || kw != 3 || cout <= 2 || !geometry_ok) return DFVO_OK;
-    if (mode == 1 && !conv_wino_rule_may_accept(cout, L->m_hint)) return DFVO_OK;
-    std::vector<float> wu(conv_wino_f32_weight_floats(cout, c0, c1));
-    conv_pack_weights_wino_f32(w_oihw, cout, c0, c1, scale, wu.data());
-    DFVO_HIP_CHECK(hipMalloc((void**)&L->wu, wu.size() * sizeof(float)));
-    DFVO_HIP_CHECK(hipMemcpy(L->wu, wu.data(), wu.size() * sizeof(float), hipMemcpyHostToDevice));
-    L->wino_mode = mode;
-    return DFVO_OK;
-}
-
-int make_head_weights(const float* w, int cout, int c0, int c1, int kh, int kw, const float* scale, float** wh) {
-    *wh = nullptr;
-    if (cout > 2 || kh != kw || (kh != 3 && kh != 5 && kh != 7)) return DFVO_OK;
-    std::vector<float> ph(conv_head_weight_floats(cout, c0, c1, kh));
-    conv_pack_head_weights(w, cout, c0, c1, kh, scale, ph.data());
-    DFVO_HIP_CHECK(hipMalloc((void**)wh, ph.size() * sizeof(float)));
-    DFVO_HIP_CHECK(hipMemcpy(*wh, ph.data(), ph.size() * sizeof(float), hipMemcpyHostToDevice));
-    return DFVO_OK;
-}
-
-void free_conv(ConvLayer* l) {
-    if (l->wp) (void)hipFree(l->wp);
-    if (l->bias) (void)hipFree(l->bias);
-    if (l->wh) (void)hipFree(l->wh);
-    if (l->wf) (void)hipFree(l->wf);
-    if (l->wg) (void)hipFree(l->wg);
-    if (l->wg32) (void)hipFree(l->wg32);
-    l->wg32 = nullptr;
-    if (l->wu) (void)hipFree(l->wu);
-    l->wu = nullptr;
-    if (l->gtab) (void)hipFree(l->gtab);
-    l->wf = nullptr;
-    l->wg = nullptr;
-    l->gtab = nullptr;
-    l->wp = l->bias = l->wh = nullptr;
-}
-
 // (A per-layer timing-based autotuner of tile / split-K configurations existed in rounds 1-3, opt-in: ~2 % on the KITTI
 // shapes, at the price of a summation order that varies between runs.  Removed; launch_conv's rule decides.)
 
@@ -204,7 +49,7 @@ constexpr int SPLITK_TICKETS = 4096;  // split-K never runs with 600 or more til
 
 int run_conv(const ConvLayer& L, int N, int H, int W, View s0, int up0, View s1, const float* res, int res_cs,
              int res_co, float* dst, int dst_cs, int dst_co, int dst_zero_to, hipStream_t s, double* flops,
-             const DevBuf* splitk_ws) {
+             const DevArr<float>* splitk_ws) {
     ConvParams p;
     memset(&p, 0, sizeof(p));
     p.N = N;
@@ -337,6 +182,9 @@ static std::string lvl_name(const char* mod, int l, const std::string& rest) {
     return std::string(mod) + "." + std::to_string(l - 2) + "." + rest;
 }
 
+// A failure returns from the middle with `finalized` still false and whatever was built so far in place.  Calling it again
+// is sound: make_conv and alloc_zeroed release what a member holds before they allocate, so the second attempt leaks
+// nothing of the first and succeeds if memory is now available.
 int FlowNet::finalize() {
     if (finalized) return DFVO_OK;
     const int N = 2;
@@ -361,12 +209,12 @@ int FlowNet::finalize() {
     }
     for (int l = 1; l <= 6; ++l) {
         const size_t px = (size_t)N * lh[l] * lw[l];
-        DFVO_TRY(img[l].alloc(px * 4));
-        DFVO_TRY(feat[l].alloc(px * lc[l]));
+        DFVO_TRY(img[l].alloc_zeroed(px * 4));
+        DFVO_TRY(feat[l].alloc_zeroed(px * lc[l]));
         const HostTensor* ox = params.get("aux.linspace_x." + std::to_string(l));
         const HostTensor* oy = params.get("aux.linspace_y." + std::to_string(l));
-        DFVO_TRY(upload(ox && (int)ox->data.size() == lw[l] ? ox->data : linspace_pm1(lw[l]), &lin_x[l]));
-        DFVO_TRY(upload(oy && (int)oy->data.size() == lh[l] ? oy->data : linspace_pm1(lh[l]), &lin_y[l]));
+        DFVO_TRY(upload_floats(ox && (int)ox->data.size() == lw[l] ? ox->data : linspace_pm1(lw[l]), &lin_x[l]));
+        DFVO_TRY(upload_floats(oy && (int)oy->data.size() == lh[l] ? oy->data : linspace_pm1(lh[l]), &lin_y[l]));
     }
     // scratch for the Features chain (reuse level buffers): needs two temporaries per level
     // ---- per level modules
@@ -401,12 +249,12 @@ int FlowNet::finalize() {
                                lvl_name("moduleMatching", l, "moduleFeat.0.bias"), C, 0, M, nullptr, nullptr,
                                &L.m_feat));
             leaky(L.m_feat, 0, 0);
-            DFVO_TRY(L.mfeat.alloc(px * 64));
+            DFVO_TRY(L.mfeat.alloc_zeroed(px * 64));
             DFVO_TRY(make_conv(params, lvl_name("moduleSubpixel", l, "moduleFeat.0.weight"),
                                lvl_name("moduleSubpixel", l, "moduleFeat.0.bias"), C, 0, M, nullptr, nullptr,
                                &L.s_feat));
             leaky(L.s_feat, 0, 0);
-            DFVO_TRY(L.sfeat.alloc(px * 64));
+            DFVO_TRY(L.sfeat.alloc_zeroed(px * 64));
         }
         if (L.has_upflow) {
             const HostTensor* t = params.get(lvl_name("moduleMatching", l, "moduleUpflow.weight"));
@@ -414,9 +262,9 @@ int FlowNet::finalize() {
                 set_last_error("missing/invalid " + lvl_name("moduleMatching", l, "moduleUpflow.weight"));
                 return DFVO_ERR_STATE;
             }
-            DFVO_TRY(upload(t->data, &L.upflow_w));
-            DFVO_TRY(L.flow_up.alloc(px * 4));
-            DFVO_TRY(L.warped.alloc(px * Cm));
+            DFVO_TRY(upload_floats(t->data, &L.upflow_w));
+            DFVO_TRY(L.flow_up.alloc_zeroed(px * 4));
+            DFVO_TRY(L.warped.alloc_zeroed(px * Cm));
         }
         if (L.has_upcorr) {
             const HostTensor* t = params.get(lvl_name("moduleMatching", l, "moduleUpcorr.weight"));
@@ -424,11 +272,11 @@ int FlowNet::finalize() {
                 set_last_error("missing/invalid " + lvl_name("moduleMatching", l, "moduleUpcorr.weight"));
                 return DFVO_ERR_STATE;
             }
-            DFVO_TRY(upload(t->data, &L.upcorr_w));
-            DFVO_TRY(L.corr.alloc((size_t)N * (h / 2) * (w / 2) * 52));
-            DFVO_TRY(L.corr_up.alloc(px * 52));
+            DFVO_TRY(upload_floats(t->data, &L.upcorr_w));
+            DFVO_TRY(L.corr.alloc_zeroed((size_t)N * (h / 2) * (w / 2) * 52));
+            DFVO_TRY(L.corr_up.alloc_zeroed(px * 52));
         } else {
-            DFVO_TRY(L.corr.alloc(px * 52));
+            DFVO_TRY(L.corr.alloc_zeroed(px * 52));
         }
         const int mcin[4] = {49, 128, 64, 32}, scin0[4] = {Cm, 128, 64, 32};
         for (int i = 0; i < 4; ++i) {
@@ -444,22 +292,22 @@ int FlowNet::finalize() {
                                i == 0 ? Cm + 2 : 0, M, nullptr, nullptr, &L.s_main[i]));
             if (i < 3) leaky(L.s_main[i], pp, pp); else linear(L.s_main[i], pp, pp);
         }
-        DFVO_TRY(L.x128.alloc(px * 128));
-        DFVO_TRY(L.x64.alloc(px * 64));
-        DFVO_TRY(L.x32.alloc(px * 32));
-        DFVO_TRY(L.x128b.alloc(px * 128));
-        DFVO_TRY(L.x64b.alloc(px * 64));
-        DFVO_TRY(L.x32b.alloc(px * 32));
-        DFVO_TRY(L.flowM.alloc(px * 4));
-        DFVO_TRY(L.b1.alloc(px * (Cm + 4)));
-        DFVO_TRY(L.flowS.alloc(px * 4));
+        DFVO_TRY(L.x128.alloc_zeroed(px * 128));
+        DFVO_TRY(L.x64.alloc_zeroed(px * 64));
+        DFVO_TRY(L.x32.alloc_zeroed(px * 32));
+        DFVO_TRY(L.x128b.alloc_zeroed(px * 128));
+        DFVO_TRY(L.x64b.alloc_zeroed(px * 64));
+        DFVO_TRY(L.x32b.alloc_zeroed(px * 32));
+        DFVO_TRY(L.flowM.alloc_zeroed(px * 4));
+        DFVO_TRY(L.b1.alloc_zeroed(px * (Cm + 4)));
+        DFVO_TRY(L.flowS.alloc_zeroed(px * 4));
         // Regularization
         if (L.has_rfeat) {
             DFVO_TRY(make_conv(params, lvl_name("moduleRegularization", l, "moduleFeat.0.weight"),
                                lvl_name("moduleRegularization", l, "moduleFeat.0.bias"), C, 0, M, nullptr, nullptr,
                                &L.r_feat));
             leaky(L.r_feat, 0, 0);
-            DFVO_TRY(L.rfeat.alloc(px * 128));
+            DFVO_TRY(L.rfeat.alloc_zeroed(px * 128));
         }
         // (the three level-2 moduleFeat convolutions as one 32 -> 256 launch: measured, no gain -- profiles/r3am_fuse_feat_ab.txt;
         // the feature-only 1x1 convolutions of levels 4-2 on a side stream beside levels 6-5, round 6: as a fork inside the
@@ -494,23 +342,23 @@ int FlowNet::finalize() {
             set_last_error("missing/invalid moduleScaleX/Y for level " + std::to_string(l));
             return DFVO_ERR_STATE;
         }
-        DFVO_TRY(upload(sx->data, &L.scale_wx));
-        DFVO_TRY(upload(sy->data, &L.scale_wy));
+        DFVO_TRY(upload_floats(sx->data, &L.scale_wx));
+        DFVO_TRY(upload_floats(sy->data, &L.scale_wy));
         L.scale_bx = bx->data[0];
         L.scale_by = by->data[0];
-        DFVO_TRY(L.r0.alloc(px * 4));
+        DFVO_TRY(L.r0.alloc_zeroed(px * 4));
         const int kkp = round_up(k * k, 4);
-        DFVO_TRY(L.dist_a.alloc(px * kkp));
-        DFVO_TRY(L.dist_b.alloc(px * kkp));
-        DFVO_TRY(L.flow.alloc(px * 4));
-        DFVO_TRY(L.mean.alloc(4 + flow_mean_scratch_floats(N)));  // [0, 2N): the means; from float 4 on: launch_flow_mean's scratch
+        DFVO_TRY(L.dist_a.alloc_zeroed(px * kkp));
+        DFVO_TRY(L.dist_b.alloc_zeroed(px * kkp));
+        DFVO_TRY(L.flow.alloc_zeroed(px * 4));
+        DFVO_TRY(L.mean.alloc_zeroed(4 + flow_mean_scratch_floats(N)));  // [0, 2N): the means; from float 4 on: launch_flow_mean's scratch
     }
-    DFVO_TRY(out_fwd.alloc((size_t)2 * imgH * imgW));
-    DFVO_TRY(out_bwd.alloc((size_t)2 * imgH * imgW));
-    DFVO_TRY(out_diff.alloc((size_t)imgH * imgW));
-    DFVO_TRY(splitk.alloc((size_t)12 << 20));
-    DFVO_TRY(u8_ref.alloc(((size_t)imgH * imgW * 3 + 3) / 4 + 1));
-    DFVO_TRY(u8_cur.alloc(((size_t)imgH * imgW * 3 + 3) / 4 + 1));
+    DFVO_TRY(out_fwd.alloc_zeroed((size_t)2 * imgH * imgW));
+    DFVO_TRY(out_bwd.alloc_zeroed((size_t)2 * imgH * imgW));
+    DFVO_TRY(out_diff.alloc_zeroed((size_t)imgH * imgW));
+    DFVO_TRY(splitk.alloc_zeroed((size_t)12 << 20));
+    DFVO_TRY(u8_ref.alloc_zeroed(((size_t)imgH * imgW * 3 + 3) / 4 + 1));
+    DFVO_TRY(u8_cur.alloc_zeroed(((size_t)imgH * imgW * 3 + 3) / 4 + 1));
     finalized = true;
     return DFVO_OK;
 }
@@ -788,34 +636,6 @@ void FlowNet::destroy() {
     }
     if (e_feat) (void)hipEventDestroy(e_feat);
     e_feat = nullptr;
-    for (auto& c : feat_convs) free_conv(&c);
-    for (int l = 1; l <= 6; ++l) {
-        img[l].release();
-        feat[l].release();
-        lin_x[l].release();
-        lin_y[l].release();
-    }
-    for (int l = 2; l <= 6; ++l) {
-        Level& L = lv[l];
-        free_conv(&L.m_feat);
-        free_conv(&L.s_feat);
-        free_conv(&L.r_feat);
-        for (auto& c : L.m_main) free_conv(&c);
-        for (auto& c : L.s_main) free_conv(&c);
-        for (auto& c : L.r_main) free_conv(&c);
-        for (auto& c : L.r_dist) free_conv(&c);
-        DevBuf* bufs[] = {&L.upflow_w, &L.upcorr_w, &L.scale_wx, &L.scale_wy, &L.mfeat, &L.sfeat, &L.rfeat, &L.flow_up,
-                          &L.warped,   &L.corr,     &L.corr_up,  &L.x128,     &L.x64,   &L.x32,   &L.x128b, &L.x64b,
-                          &L.x32b,     &L.flowM,    &L.b1,       &L.flowS,    &L.r0,    &L.dist_a, &L.dist_b, &L.flow,
-                          &L.mean};
-        for (DevBuf* b : bufs) b->release();
-    }
-    out_fwd.release();
-    out_bwd.release();
-    out_diff.release();
-    splitk.release();
-    u8_ref.release();
-    u8_cur.release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
     stream = nullptr;
 }
@@ -856,6 +676,7 @@ static int bn_fold(const ParamStore& ps, const std::string& bn, int c, std::vect
     return DFVO_OK;
 }
 
+// (may be called again after a failed attempt, as FlowNet::finalize)
 int DepthNet::finalize() {
     if (finalized) return DFVO_OK;
     std::vector<float> sc, sh;
@@ -927,23 +748,23 @@ int DepthNet::finalize() {
     dispconv.pad_mode = PAD_REFLECT;
     dispconv.act = ACT_SIGMOID;
     // buffers
-    DFVO_TRY(x0.alloc((size_t)N * H * W * 4));
-    DFVO_TRY(feat[0].alloc((size_t)N * (H / 2) * (W / 2) * 64));
-    DFVO_TRY(pool.alloc((size_t)N * (H / 4) * (W / 4) * 64));
-    for (int i = 1; i < 5; ++i) DFVO_TRY(feat[i].alloc((size_t)N * (H >> (i + 1)) * (W >> (i + 1)) * ch[i]));
+    DFVO_TRY(x0.alloc_zeroed((size_t)N * H * W * 4));
+    DFVO_TRY(feat[0].alloc_zeroed((size_t)N * (H / 2) * (W / 2) * 64));
+    DFVO_TRY(pool.alloc_zeroed((size_t)N * (H / 4) * (W / 4) * 64));
+    for (int i = 1; i < 5; ++i) DFVO_TRY(feat[i].alloc_zeroed((size_t)N * (H >> (i + 1)) * (W >> (i + 1)) * ch[i]));
     const size_t big = (size_t)N * (H / 4) * (W / 4) * 64;  // every block tensor is <= this many floats
-    DFVO_TRY(blk_t.alloc(big));
-    DFVO_TRY(blk_ds.alloc(big));
-    DFVO_TRY(blk_o[0].alloc(big));
-    DFVO_TRY(blk_o[1].alloc(big));
+    DFVO_TRY(blk_t.alloc_zeroed(big));
+    DFVO_TRY(blk_ds.alloc_zeroed(big));
+    DFVO_TRY(blk_o[0].alloc_zeroed(big));
+    DFVO_TRY(blk_o[1].alloc_zeroed(big));
     for (int i = 4; i >= 0; --i) {
-        DFVO_TRY(du[i].alloc((size_t)N * (H >> (i + 1)) * (W >> (i + 1)) * dec[i]));
-        DFVO_TRY(dx[i].alloc((size_t)N * (H >> i) * (W >> i) * dec[i]));
+        DFVO_TRY(du[i].alloc_zeroed((size_t)N * (H >> (i + 1)) * (W >> (i + 1)) * dec[i]));
+        DFVO_TRY(dx[i].alloc_zeroed((size_t)N * (H >> i) * (W >> i) * dec[i]));
     }
-    DFVO_TRY(disp.alloc((size_t)N * H * W * 4));
-    DFVO_TRY(depth.alloc((size_t)N * H * W));
-    DFVO_TRY(splitk.alloc((size_t)12 << 20));
-    DFVO_TRY(u8_in.alloc(((size_t)H * W * 3 + 3) / 4 + 1));
+    DFVO_TRY(disp.alloc_zeroed((size_t)N * H * W * 4));
+    DFVO_TRY(depth.alloc_zeroed((size_t)N * H * W));
+    DFVO_TRY(splitk.alloc_zeroed((size_t)12 << 20));
+    DFVO_TRY(u8_in.alloc_zeroed(((size_t)H * W * 3 + 3) / 4 + 1));
     finalized = true;
     return DFVO_OK;
 }
@@ -1041,22 +862,8 @@ int DepthNet::forward(const uint8_t* d_img, float* d_depth) {
 void DepthNet::destroy() {
     if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
     if (graph) (void)hipGraphDestroy(graph);
-    free_conv(&conv1);
-    for (auto& b : blocks) {
-        free_conv(&b.c1);
-        free_conv(&b.c2);
-        free_conv(&b.ds);
-    }
-    for (int i = 0; i < 5; ++i) {
-        free_conv(&up[i][0]);
-        free_conv(&up[i][1]);
-        feat[i].release();
-        du[i].release();
-        dx[i].release();
-    }
-    free_conv(&dispconv);
-    DevBuf* bufs[] = {&x0, &pool, &blk_t, &blk_ds, &blk_o[0], &blk_o[1], &disp, &depth, &u8_in, &splitk};
-    for (DevBuf* b : bufs) b->release();
+    graph_exec = nullptr;
+    graph = nullptr;
     if (own_stream && stream) (void)hipStreamDestroy(stream);
     stream = nullptr;
 }

@@ -277,9 +277,6 @@ int dfvo_pipeline_create(const dfvo_pipeline_cfg* cfg, dfvo_pipeline** out) {
 void dfvo_pipeline_destroy(dfvo_pipeline* p) {
     if (!p) return;
     (void)hipDeviceSynchronize();
-    p->flow.destroy();
-    for (int i = 0; i + 1 < p->flow_instances; ++i) p->flow_x[i].destroy();
-    p->depth.destroy();
     for (int i = DFVO_PIPELINE_SLOTS - 1; i >= 0; i--) {
         Slot& sl = p->slots[i];
         sl.tb.release();  // (the sharing sets before slots[0].tb, whose RandomState and events they borrow)
@@ -288,9 +285,8 @@ void dfvo_pipeline_destroy(dfvo_pipeline* p) {
     }
     for (hipEvent_t e : {p->e_ref, p->e_roll})
         if (e) (void)hipEventDestroy(e);
-    p->feed_resize.release();
     for (hipStream_t s : p->owned) (void)hipStreamDestroy(s);
-    delete p;  // (device and pinned memory: DevArr / PinnedArr members, here and in the buffer sets)
+    delete p;  // (device and pinned memory: DevArr / PinnedArr members, here, in the nets and in the buffer sets; the nets' graphs)
 }
 
 static int pipe_store(ParamStore* ps, const char* name, const float* h, int ndim, const int* shape) {

@@ -1,22 +1,21 @@
 // Pillow-exact 8-bit LANCZOS resize on the device (the depth net's input stage).
 #pragma once
-#include <hip/hip_runtime.h>
-
 #include <cstdint>
+
+#include "dev_mem.h"
 
 namespace dfvo {
 
 // uint8 [H, W, 3] -> uint8 [oh, ow, 3]: horizontal pass into `tmp`, vertical pass into the destination, each with
 // Pillow's 22-bit fixed-point coefficient tables (built on the host at init, resident on the device)
 struct LanczosResizer {
-    int H = 0, W = 0, oh = 0, ow = 0;
+    int H = 0, W = 0, oh = 0, ow = 0;     // all zero unless init succeeded: a failed init is asked for again
     int ksx = 0, ksy = 0;                 // coefficients per output column / row
-    int *bx = nullptr, *kx = nullptr;     // [ow][2] (first input column, count), [ow][ksx]
-    int *by = nullptr, *ky = nullptr;     // [oh][2], [oh][ksy]
-    uint8_t* tmp = nullptr;               // [H][ow][3]
+    DevArr<int> bx, kx;                   // [ow][2] (first input column, count), [ow][ksx]
+    DevArr<int> by, ky;                   // [oh][2], [oh][ksy]
+    DevArr<uint8_t> tmp;                  // [H][ow][3]
     int init(int H, int W, int oh, int ow);
     int enqueue(const uint8_t* d_src, uint8_t* d_dst, hipStream_t s) const;
-    void release();
 };
 
 // cv2.resize(img, (ow, oh)) for uint8 [H, W, C] (INTER_LINEAR, OpenCV 3.4.3's 11-bit fixed point), utils.py:51

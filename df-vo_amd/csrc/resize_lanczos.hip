@@ -99,9 +99,10 @@ __global__ void k_lanczos_pass(const uint8_t* __restrict__ src, uint8_t* __restr
     q[2] = clip8(s2);
 }
 
-int upload(const std::vector<int>& h, int** d) {
-    DFVO_HIP_CHECK(hipMalloc((void**)d, h.size() * sizeof(int)));
-    DFVO_HIP_CHECK(hipMemcpy(*d, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
+int upload(const std::vector<int>& h, DevArr<int>* d) {
+    const int rc = d->alloc(h.size());
+    if (rc != DFVO_OK) return rc;
+    DFVO_HIP_CHECK(hipMemcpy(d->p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
     return DFVO_OK;
 }
 }  // namespace
@@ -117,33 +118,25 @@ int lanczos_coeffs_host(int in_size, int out_size, int* bounds, int* coeffs, int
     return DFVO_OK;
 }
 
+// the geometry is written last: a failed init leaves a released object of size zero, which no caller's size test matches
 int LanczosResizer::init(int H_, int W_, int oh_, int ow_) {
     DFVO_ARG_CHECK(H_ > 0 && W_ > 0 && oh_ > 0 && ow_ > 0, "LanczosResizer: bad size");
-    release();
-    H = H_;
-    W = W_;
-    oh = oh_;
-    ow = ow_;
+    *this = LanczosResizer();
     std::vector<int> b, k;
-    precompute_coeffs(W, ow, &b, &k, &ksx);
+    int ksx_ = 0, ksy_ = 0;
+    precompute_coeffs(W_, ow_, &b, &k, &ksx_);
     int rc = upload(b, &bx);
     if (rc == DFVO_OK) rc = upload(k, &kx);
-    precompute_coeffs(H, oh, &b, &k, &ksy);
+    precompute_coeffs(H_, oh_, &b, &k, &ksy_);
     if (rc == DFVO_OK) rc = upload(b, &by);
     if (rc == DFVO_OK) rc = upload(k, &ky);
-    if (rc != DFVO_OK) return rc;
-    DFVO_HIP_CHECK(hipMalloc((void**)&tmp, (size_t)H * ow * 3));
+    if (rc == DFVO_OK) rc = tmp.alloc((size_t)H_ * ow_ * 3);
+    if (rc != DFVO_OK) {
+        *this = LanczosResizer();
+        return rc;
+    }
+    H = H_, W = W_, oh = oh_, ow = ow_, ksx = ksx_, ksy = ksy_;
     return DFVO_OK;
-}
-
-void LanczosResizer::release() {
-    for (int** p : {&bx, &kx, &by, &ky})
-        if (*p) {
-            (void)hipFree(*p);
-            *p = nullptr;
-        }
-    if (tmp) (void)hipFree(tmp);
-    tmp = nullptr;
 }
 
 int LanczosResizer::enqueue(const uint8_t* d_src, uint8_t* d_dst, hipStream_t s) const {

@@ -47,7 +47,7 @@ struct dfvo_session {
     dfvo_tracker* t = nullptr;
     int H = 0, W = 0;
     hipStream_t s_copy = nullptr, s_pre = nullptr;
-    uint8_t* d_img[2] = {nullptr, nullptr};
+    DevArr<uint8_t> d_img[2];
     long long gen = -1;          // frames pushed so far - 1 = generation of the newest frame
     bool carry_ok = false;       // the flow net's current-frame pyramids are those of frame `gen`
     bool have_flow = false;      // a flow pass of (gen - 1, gen) is enqueued / done
@@ -59,16 +59,15 @@ struct dfvo_session {
     bool have_e = false;         // the RandomState-consuming half of compute_pose_2d2d is enqueued (dfvo_session_pose_ahead)
     uint32_t rng_ahead[625] = {};            // ... under this RandomState
     unsigned char ahead_cfg[sizeof(dfvo_pose2d2d_cfg)] = {};  // ... and this configuration (bytes)
-    uint8_t* h_frame[RING] = {};  // pinned copies of the pushed frames: the upload's source, and what forward_flow's frames are compared with
-    unsigned* h_ovf[RING] = {};   // [0] f16x3 range counter behind the flow net of the generation, [1] behind its depth net
+    PinnedArr<uint8_t> h_frame[RING];  // pinned copies of the pushed frames: the upload's source, and what forward_flow's frames are compared with
+    PinnedArr<unsigned> h_ovf[RING];  // [0] f16x3 range counter behind the flow net of the generation, [1] behind its depth net
     unsigned* d_ovf = nullptr;    // the device counter (conv_f16s_overflow_counter)
     unsigned ovf_seen[2] = {0, 0};  // its value up to which each of the two readers (flow stream, depth stream) has reported
     bool ovf_bad[RING][2] = {};     // the generation of the slot was reported out of range to that reader: every later read is too
-    float* h_depth[RING] = {};
-    float *h_fwd[RING] = {}, *h_bwd[RING] = {}, *h_diff[RING] = {};
-    double *h_kp_ref[RING] = {}, *h_kp_cur[RING] = {};
-    int* h_info[RING] = {};
-    int kp_cap = 0;
+    PinnedArr<float> h_depth[RING];
+    PinnedArr<float> h_fwd[RING], h_bwd[RING], h_diff[RING];
+    PinnedArr<double> h_kp_ref[RING], h_kp_cur[RING];  // [n][2], grown on demand (ensure_kp_host): their `n` is the capacity
+    PinnedArr<int> h_info[RING];
     hipEvent_t e_img = nullptr, e_depth = nullptr, e_net = nullptr, e_flow = nullptr, e_kp = nullptr, e_pose = nullptr;
     dfvo_session_kp_cfg kp_cfg = {};
     dfvo_pose2d2d_cfg pose_cfg = {};
@@ -168,15 +167,10 @@ int dfvo_session_create(dfvo_flownet* f, dfvo_depthnet* d, dfvo_tracker* t, int 
     const size_t px = (size_t)img_h * img_w, dpx = (size_t)d->net.H * d->net.W;
     bool ok = hipStreamCreateWithFlags(&s->s_copy, hipStreamNonBlocking) == hipSuccess &&
               hipStreamCreateWithFlags(&s->s_pre, hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; i < 2 && ok; ++i) ok = hipMalloc((void**)&s->d_img[i], px * 3) == hipSuccess;
+    for (int i = 0; i < 2 && ok; ++i) ok = s->d_img[i].alloc(px * 3) == DFVO_OK;
     for (int i = 0; i < RING && ok; ++i) {
-        ok = hipHostMalloc((void**)&s->h_depth[i], dpx * sizeof(float)) == hipSuccess &&
-             hipHostMalloc((void**)&s->h_fwd[i], 2 * px * sizeof(float)) == hipSuccess &&
-             hipHostMalloc((void**)&s->h_bwd[i], 2 * px * sizeof(float)) == hipSuccess &&
-             hipHostMalloc((void**)&s->h_diff[i], px * sizeof(float)) == hipSuccess &&
-             hipHostMalloc((void**)&s->h_info[i], 4 * sizeof(int)) == hipSuccess &&
-             hipHostMalloc((void**)&s->h_frame[i], px * 3) == hipSuccess &&
-             hipHostMalloc((void**)&s->h_ovf[i], 2 * sizeof(unsigned)) == hipSuccess;
+        ok = !s->h_depth[i].alloc(dpx) && !s->h_fwd[i].alloc(2 * px) && !s->h_bwd[i].alloc(2 * px) && !s->h_diff[i].alloc(px) &&
+             !s->h_info[i].alloc(4) && !s->h_frame[i].alloc(px * 3) && !s->h_ovf[i].alloc(2);
         if (ok) s->h_ovf[i][0] = s->h_ovf[i][1] = 0;
     }
     if (ok) {
@@ -210,15 +204,7 @@ int dfvo_session_create(dfvo_flownet* f, dfvo_depthnet* d, dfvo_tracker* t, int 
 
 void dfvo_session_destroy(dfvo_session* s) {
     if (!s) return;
-    (void)hipDeviceSynchronize();
-    for (int i = 0; i < 2; ++i)
-        if (s->d_img[i]) (void)hipFree(s->d_img[i]);
-    for (int i = 0; i < RING; ++i) {
-        void* hp[9] = {s->h_depth[i], s->h_fwd[i], s->h_bwd[i], s->h_diff[i], s->h_kp_ref[i], s->h_kp_cur[i], s->h_info[i],
-                       s->h_frame[i], s->h_ovf[i]};
-        for (void* q : hp)
-            if (q) (void)hipHostFree(q);
-    }
+    (void)hipDeviceSynchronize();  // (before the arrays go, with `delete s`)
     hipEvent_t evs[6] = {s->e_img, s->e_depth, s->e_net, s->e_flow, s->e_kp, s->e_pose};
     for (hipEvent_t e : evs)
         if (e) (void)hipEventDestroy(e);
@@ -251,17 +237,21 @@ int dfvo_session_quiesce(dfvo_session* s) {
     return DFVO_OK;
 }
 
+// every slot's keypoint arrays hold `cap` keypoints.  A failure leaves the slots before it grown, one or both arrays of its slot
+// empty and the rest as they were: none claims more than it holds, so the next push comes here again and re-grows all of
+// them, or fails again
 static int ensure_kp_host(dfvo_session* s, int cap) {
-    if (cap <= s->kp_cap) return DFVO_OK;
+    const size_t need = (size_t)2 * cap;
+    bool fits = true;
+    for (int i = 0; i < RING; ++i) fits = fits && need <= s->h_kp_ref[i].n && need <= s->h_kp_cur[i].n;
+    if (fits) return DFVO_OK;
     DFVO_HIP_CHECK(hipDeviceSynchronize());  // (a copy into the old buffers may still be in flight)
     for (int i = 0; i < RING; ++i) {
-        if (s->h_kp_ref[i]) (void)hipHostFree(s->h_kp_ref[i]);
-        if (s->h_kp_cur[i]) (void)hipHostFree(s->h_kp_cur[i]);
-        s->h_kp_ref[i] = s->h_kp_cur[i] = nullptr;
-        DFVO_HIP_CHECK(hipHostMalloc((void**)&s->h_kp_ref[i], sizeof(double) * 2 * cap));
-        DFVO_HIP_CHECK(hipHostMalloc((void**)&s->h_kp_cur[i], sizeof(double) * 2 * cap));
+        s->h_kp_ref[i].release();
+        s->h_kp_cur[i].release();
+        S_TRY(s->h_kp_ref[i].alloc(need));
+        S_TRY(s->h_kp_cur[i].alloc(need));
     }
-    s->kp_cap = cap;
     return DFVO_OK;
 }
 
@@ -421,24 +411,16 @@ int dfvo_session_detach_slot(dfvo_session* s, long long generation, void** h_old
     const int i = (int)(generation % RING);
     const size_t px = (size_t)s->H * s->W, dpx = (size_t)s->d->net.H * s->d->net.W;
     DFVO_HIP_CHECK(hipDeviceSynchronize());  // (no copy into the old buffers is in flight any more)
-    float *nd = nullptr, *nf = nullptr, *nb = nullptr, *nx = nullptr;
-    const bool ok = hipHostMalloc((void**)&nd, dpx * sizeof(float)) == hipSuccess && hipHostMalloc((void**)&nf, 2 * px * sizeof(float)) == hipSuccess &&
-                    hipHostMalloc((void**)&nb, 2 * px * sizeof(float)) == hipSuccess && hipHostMalloc((void**)&nx, px * sizeof(float)) == hipSuccess;
-    if (!ok) {
-        void* fresh[4] = {nd, nf, nb, nx};
-        for (void* q : fresh)
-            if (q) (void)hipHostFree(q);
+    PinnedArr<float> fresh[4];  // swapped in only when all four exist: a failure leaves the slot untouched
+    if (fresh[0].alloc(dpx) || fresh[1].alloc(2 * px) || fresh[2].alloc(2 * px) || fresh[3].alloc(px)) {
         dfvo::set_last_error("dfvo_session_detach_slot: pinned allocation failed");
         return DFVO_ERR_HIP;
     }
-    h_old4[0] = s->h_depth[i];
-    h_old4[1] = s->h_fwd[i];
-    h_old4[2] = s->h_bwd[i];
-    h_old4[3] = s->h_diff[i];
-    s->h_depth[i] = nd;
-    s->h_fwd[i] = nf;
-    s->h_bwd[i] = nb;
-    s->h_diff[i] = nx;
+    PinnedArr<float>* held[4] = {&s->h_depth[i], &s->h_fwd[i], &s->h_bwd[i], &s->h_diff[i]};
+    for (int k = 0; k < 4; ++k) {
+        h_old4[k] = held[k]->detach();
+        *held[k] = std::move(fresh[k]);
+    }
     return DFVO_OK;
 }
 
@@ -486,7 +468,7 @@ int dfvo_session_keypoints(dfvo_session* s, long long generation, const dfvo_ses
 static bool h_half_matches(dfvo_session* s, const double* h_kp_ref, const double* h_kp_cur, int n, const dfvo_pose2d2d_cfg* cfg) {
     const int slot = (int)(s->gen % RING);
     // the homography half reads: the keypoints, validity method / threshold, K^-T, K^-1 (enqueue_pose_h_part)
-    return s->h_info[slot][1] != 0 && s->h_info[slot][0] == n && n <= s->kp_cap &&
+    return s->h_info[slot][1] != 0 && s->h_info[slot][0] == n && (size_t)2 * n <= s->h_kp_ref[slot].n && (size_t)2 * n <= s->h_kp_cur[slot].n &&
            memcmp(h_kp_ref, s->h_kp_ref[slot], sizeof(double) * 2 * n) == 0 &&
            memcmp(h_kp_cur, s->h_kp_cur[slot], sizeof(double) * 2 * n) == 0 &&
            cfg->validity_method == s->pose_cfg.validity_method && cfg->validity_thre == s->pose_cfg.validity_thre &&

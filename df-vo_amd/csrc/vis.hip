@@ -392,16 +392,14 @@ int sel_blocks(int n) {
 struct dfvo_vis {
     int win_h = 0, win_w = 0;
     int cell[DFVO_VIS_CELLS][4] = {};  // y0, x0, y1, x1
-    uint8_t* canvas = nullptr;
+    DevArr<uint8_t> canvas;
     hipStream_t stream = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    void* stage[2] = {nullptr, nullptr};  // uploaded maps
-    size_t stage_cap[2] = {0, 0};
-    uint8_t* rgb = nullptr;  // dfvo_vis_flow_rgb
-    size_t rgb_cap = 0;
+    DevArr<unsigned char> stage[2];  // uploaded maps (bytes), grown on demand
+    DevArr<uint8_t> rgb;             // dfvo_vis_flow_rgb, grown on demand
     // scratch: [0..1] flow 0 (max bits, unknown), [2..3] flow 1, [4] NaN count, [6..7] ~min key above, then the histograms
-    unsigned* scratch = nullptr;
-    double* d_vmax = nullptr;
+    DevArr<unsigned> scratch;
+    DevArr<double> d_vmax;
     long long counters[DFVO_VIS_COUNTERS] = {};
     float last_ms = 0.f;
 };
@@ -422,16 +420,6 @@ int tables_to_device() {
     DFVO_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_jet), VIS_TAB_JET, sizeof(VIS_TAB_JET)));
     DFVO_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_wheel), VIS_TAB_WHEEL, sizeof(VIS_TAB_WHEEL)));
     done.insert(dev);
-    return DFVO_OK;
-}
-
-int ensure_bytes(void** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return DFVO_OK;
-    if (*p) DFVO_HIP_CHECK(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    DFVO_HIP_CHECK(hipMalloc(p, bytes));
-    *cap = bytes;
     return DFVO_OK;
 }
 
@@ -508,7 +496,7 @@ int end_draw(dfvo_vis* v) {
 }
 
 int upload(dfvo_vis* v, int slot, const void* h_src, size_t bytes) {
-    int rc = ensure_bytes(&v->stage[slot], &v->stage_cap[slot], bytes);
+    int rc = v->stage[slot].grow(bytes);
     if (rc != DFVO_OK) return rc;
     DFVO_HIP_CHECK(hipMemcpyAsync(v->stage[slot], h_src, bytes, hipMemcpyHostToDevice, v->stream));
     v->counters[5] += (long long)bytes;
@@ -546,9 +534,8 @@ int dfvo_vis_create(int window_h, int window_w, dfvo_vis** out) {
     }
     const size_t bytes = (size_t)window_h * window_w * 3;
     bool ok = hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking) == hipSuccess && hipEventCreate(&v->e0) == hipSuccess &&
-              hipEventCreate(&v->e1) == hipSuccess && hipMalloc((void**)&v->canvas, bytes) == hipSuccess &&
-              hipMalloc((void**)&v->scratch, SCRATCH_WORDS * sizeof(unsigned)) == hipSuccess &&
-              hipMalloc((void**)&v->d_vmax, sizeof(double)) == hipSuccess;
+              hipEventCreate(&v->e1) == hipSuccess && v->canvas.alloc(bytes) == DFVO_OK &&
+              v->scratch.alloc(SCRATCH_WORDS) == DFVO_OK && v->d_vmax.alloc(1) == DFVO_OK;
     ok = ok && hipMemsetAsync(v->canvas, 0, bytes, v->stream) == hipSuccess && hipStreamSynchronize(v->stream) == hipSuccess;
     if (!ok) {
         dfvo_vis_destroy(v);
@@ -562,13 +549,10 @@ int dfvo_vis_create(int window_h, int window_w, dfvo_vis** out) {
 void dfvo_vis_destroy(dfvo_vis* v) {
     if (!v) return;
     if (v->stream) (void)hipStreamSynchronize(v->stream);
-    void* bufs[6] = {v->canvas, v->scratch, v->d_vmax, v->stage[0], v->stage[1], v->rgb};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
     if (v->e0) (void)hipEventDestroy(v->e0);
     if (v->e1) (void)hipEventDestroy(v->e1);
     if (v->stream) (void)hipStreamDestroy(v->stream);
-    delete v;
+    delete v;  // (the arrays)
 }
 
 int dfvo_vis_cell_rect(const dfvo_vis* v, int cell, int* y0x0y1x1) {
@@ -584,7 +568,7 @@ int dfvo_vis_draw_flow(dfvo_vis* v, int cell, const float* h_flow, int H, int W,
     const int n = H * W;
     V_TRY(upload(v, 0, h_flow, sizeof(float) * 2 * n));
     V_TRY(begin_draw(v));
-    V_TRY(enqueue_flow_max(v, (const float*)v->stage[0], n, 0));
+    V_TRY(enqueue_flow_max(v, (const float*)v->stage[0].p, n, 0));
     ps.p[0].kind = VIS_WHEEL;
     ps.p[0].src = v->stage[0];
     ps.p[0].maxrad_bits = v->scratch;
@@ -612,7 +596,7 @@ int dfvo_vis_draw_map(dfvo_vis* v, int cell, const void* h_map, int is_f64, int 
     p.src = v->stage[0];
     p.vmax = vmax_in;
     if (p.kind == VIS_DISP) {
-        V_TRY(is_f64 ? enqueue_percentile<double>(v, (const double*)v->stage[0], n) : enqueue_percentile<float>(v, (const float*)v->stage[0], n));
+        V_TRY(is_f64 ? enqueue_percentile<double>(v, (const double*)v->stage[0].p, n) : enqueue_percentile<float>(v, (const float*)v->stage[0].p, n));
         p.vmax_dev = v->d_vmax;
     }
     V_TRY(enqueue_panels(v, ps, 1));
@@ -751,10 +735,10 @@ int dfvo_vis_flow_rgb(dfvo_vis* v, const float* h_flow, int H, int W, uint8_t* h
     DFVO_ARG_CHECK(v && h_flow && h_rgb && H > 0 && W > 0 && (long long)H * W <= 1280ll * 1920ll, "dfvo_vis_flow_rgb: bad argument");
     const int n = H * W;
     V_TRY(upload(v, 0, h_flow, sizeof(float) * 2 * n));
-    V_TRY(ensure_bytes((void**)&v->rgb, &v->rgb_cap, (size_t)n * 3));
+    V_TRY(v->rgb.grow((size_t)n * 3));
     V_TRY(begin_draw(v));
-    V_TRY(enqueue_flow_max(v, (const float*)v->stage[0], n, 0));
-    hipLaunchKernelGGL(k_vis_flow_rgb, dim3(cdiv(n, 256)), dim3(256), 0, v->stream, (const float*)v->stage[0], n, v->scratch, v->rgb);
+    V_TRY(enqueue_flow_max(v, (const float*)v->stage[0].p, n, 0));
+    hipLaunchKernelGGL(k_vis_flow_rgb, dim3(cdiv(n, 256)), dim3(256), 0, v->stream, (const float*)v->stage[0].p, n, v->scratch, v->rgb);
     DFVO_HIP_CHECK(hipGetLastError());
     DFVO_HIP_CHECK(hipMemcpyAsync(h_rgb, v->rgb, (size_t)n * 3, hipMemcpyDeviceToHost, v->stream));
     V_TRY(end_draw(v));
@@ -765,7 +749,7 @@ int dfvo_vis_disparity_percentile90(dfvo_vis* v, const void* h_depth, int is_f64
     DFVO_ARG_CHECK(v && h_depth && out && n > 0 && n <= 1280 * 1920, "dfvo_vis_disparity_percentile90: bad argument");
     V_TRY(upload(v, 0, h_depth, (is_f64 ? sizeof(double) : sizeof(float)) * (size_t)n));
     V_TRY(begin_draw(v));
-    V_TRY(is_f64 ? enqueue_percentile<double>(v, (const double*)v->stage[0], n) : enqueue_percentile<float>(v, (const float*)v->stage[0], n));
+    V_TRY(is_f64 ? enqueue_percentile<double>(v, (const double*)v->stage[0].p, n) : enqueue_percentile<float>(v, (const float*)v->stage[0].p, n));
     V_TRY(end_draw(v));
     DFVO_HIP_CHECK(hipMemcpy(out, v->d_vmax, sizeof(double), hipMemcpyDeviceToHost));
     return DFVO_OK;

@@ -700,3 +700,73 @@ def test_stream_pool_fallback_is_loud_and_harmless(gpu, tmp_path, monkeypatch, c
         for k in a:
             assert np.array_equal(a[k], b[k]), k
     assert s.stats["flow_resident"] == s.stats["pose_ahead"] == 3, s.stats
+
+
+def _hip_block_bytes(ptr):
+    """size of the hipMalloc / hipHostMalloc block that holds `ptr` (hipMemGetAddressRange of the HIP runtime the process runs on)"""
+    import ctypes as C
+    with open("/proc/self/maps") as f:
+        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
+    hip = C.CDLL(path)
+    base, size = C.c_void_p(), C.c_size_t()
+    assert hip.hipMemGetAddressRange(C.byref(base), C.byref(size), C.c_void_p(ptr)) == 0
+    return int(size.value)
+
+
+def test_session_keypoint_ring_grows_while_live(gpu, tmp_path, monkeypatch):
+    """The session's pinned keypoint ring follows the tracker's keypoint capacity, which only rises.  On a tracker of its own
+    (capacity zero: the suite's shared one has seen num_bestN 2000 long before) three pairs run with a 10 x 10 grid and
+    num_bestN 200, 2000, 200: the ring is allocated for 200, grows for 2000 while its slots hold frames in flight, and stays.
+    Checked on the blocks themselves: the one behind pair 1's keypoints could not hold pair 2's, the one behind pair 2's does.
+    For each pair the keypoints the session hands out are, byte for byte, dfvo_kp_local_bestn on the flow arrays the session
+    returned; the first and the third pair are the same two frames and select the same bytes, before the growth and after."""
+    import ctypes as C
+    monkeypatch.setenv("DFVO_SESSION", "1")
+    capi = importlib.import_module("df-vo_amd.capi")
+    ctx = importlib.import_module("df-vo_amd.libs.tracker._ctx")
+    ks_mod = importlib.import_module("df-vo_amd.libs.matching.keypoint_sampler")
+    monkeypatch.setattr(ctx, "_trk", None)       # a fresh tracker for this test; the shared handle comes back afterwards
+    h, w, seq, cfg = _small_world(tmp_path, n=4)
+    dm = _build_mirrors(cfg, seq["K"])[0]
+    s = dm.session
+    frames = [f.copy() for f in seq["frames"]]
+    depth = np.ones((h, w))
+    picks, blocks = [], []
+    for (a, b), bestn in (((0, 1), 200), ((2, 3), 2000), ((0, 1), 200)):
+        c = copy.deepcopy(cfg)
+        c["kp_selection"]["local_bestN"].update(num_row=10, num_col=10, num_bestN=bestn)
+        sampler = ks_mod.KeypointSampler(c)      # registers its configuration with the session
+        dm.forward_depth(imgs=[frames[a]])
+        dm.forward_depth(imgs=[frames[b]])
+        flows = dm.forward_flow({"id": b, "img": frames[b]}, {"id": a, "img": frames[a]}, True)
+        fwd, diff = flows[(a, b)], flows[(a, b, "diff")]
+        before = dict(s.stats)
+        out = sampler.kp_selection({"depth": depth}, {"flow": fwd, "flow_diff": diff, "depth": depth})
+        assert s.stats["kp_resident"] == before["kp_resident"] + 1 and out["good_kp_found"], s.stats
+        f32 = np.ascontiguousarray(fwd, dtype=np.float32)
+        d32 = np.ascontiguousarray(np.asarray(diff, dtype=np.float32).reshape(h, w))
+        kp1, kp2 = np.zeros((bestn, 2)), np.zeros((bestn, 2))
+        n, good = C.c_int(), C.c_int()
+        capi.check(capi.lib().dfvo_kp_local_bestn(ctx.tracker_exclusive(), capi.as_ptr(f32), capi.as_ptr(d32), h, w, 10, 10, bestn,
+                                                  float(c.kp_selection.local_bestN.thre), capi.as_ptr(kp1), capi.as_ptr(kp2),
+                                                  C.byref(n), C.byref(good)))
+        assert good.value and 0 < n.value <= bestn
+        got1, got2 = np.ascontiguousarray(out["kp1_best"][0]), np.ascontiguousarray(out["kp2_best"][0])
+        assert got1.dtype == np.float64 and got1.shape == (n.value, 2) == got2.shape
+        assert got1.tobytes() == kp1[:n.value].tobytes() and got2.tobytes() == kp2[:n.value].tobytes(), (a, b, bestn)
+        picks.append((got1, got2))
+        # the pinned blocks this pair's keypoints were handed out of
+        pr, pc, nn, gg = C.c_void_p(), C.c_void_p(), C.c_int(), C.c_int()
+        capi.check(capi.lib().dfvo_session_keypoints(s.handle, s.gen, C.byref(sampler._session_kp_cfg), C.byref(pr), C.byref(pc),
+                                                     C.byref(nn), C.byref(gg)))
+        assert nn.value == n.value
+        blocks.append((_hip_block_bytes(pr.value), _hip_block_bytes(pc.value)))
+    need = [16 * len(p[0]) for p in picks]       # bytes of [n][2] float64
+    print("keypoint ring blocks (bytes):", blocks, "needed:", need)
+    assert all(lo >= need[0] for lo in blocks[0]) and all(lo < need[1] for lo in blocks[0]), "pair 1's ring could hold pair 2"
+    assert all(hi >= need[1] for hi in blocks[1]), "the ring did not grow for pair 2"
+    assert blocks[2] == blocks[1], "the ring shrank or was reallocated for a request that fits"
+    assert picks[0][0].tobytes() == picks[2][0].tobytes() and picks[0][1].tobytes() == picks[2][1].tobytes()
+    s.close()
+    ctx.register_session(None)
+    capi.lib().dfvo_tracker_destroy(ctx._trk)    # this test's own tracker

@@ -1,7 +1,7 @@
-"""CPU: the lifetimes of the solver chain's device buffers (df-vo_amd/csrc/dev_mem.h, solver_buffers.hip) -- every buffer
-set under a failure of each of its allocations, growth by dimension, the on-demand arrays, and which side streams and
-events a TrackerBuffers destroys -- through the stand-alone program tests/host_harness/solver_buffers_check.cpp: the
-host-only unit compiled as plain C++ against HIP entry points the program defines itself, with AddressSanitizer and UBSan."""
+"""CPU: the lifetimes of the nets' layer packings (df-vo_amd/csrc/dev_mem.h, net_layers.hip) -- a conv layer under a failure of
+each of its allocations in every precision, packed twice, moved inside a std::vector, and DevArr's alloc_zeroed / detach --
+through the stand-alone program tests/host_harness/net_layers_check.cpp: the host-only unit compiled as plain C++ against HIP
+entry points and weight packers the program defines itself, with AddressSanitizer and UBSan."""
 import glob
 import os
 import subprocess
@@ -10,14 +10,13 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "..", "df-vo_amd", "csrc")
-SRC = os.path.join(HERE, "host_harness", "solver_buffers_check.cpp")
+SRC = os.path.join(HERE, "host_harness", "net_layers_check.cpp")
 STUB = os.path.join(HERE, "host_harness", "hip_stub.h")
-UNIT = os.path.join(CSRC, "solver_buffers.hip")
+UNIT = os.path.join(CSRC, "net_layers.hip")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
-CASES = ["%s_fail_each" % w for w in ("ransac", "pnp", "bestn", "rigid", "tracker_kp")] + \
-        ["parts_fail_releases_all", "fits_no_calls", "grow_one_dimension", "grow_on_demand_fail", "devarr_moves",
-         "streams_init_own", "streams_init_given", "streams_borrowed_aliased", "streams_rebind", "streams_shared"]
+CASES = ["fail_each_fp32", "fail_each_f16x3", "fail_each_fp32_wino2", "repack_frees_first", "vector_of_layers", "alloc_zeroed",
+         "detach"]
 
 
 @pytest.fixture(scope="module")
@@ -26,7 +25,7 @@ def checker():
         pytest.skip("no HIP headers under %s (ROCM_PATH)" % ROCM)
     out_dir = os.path.join(HERE, "host_harness", "build")
     os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "solver_buffers_check")
+    exe = os.path.join(out_dir, "net_layers_check")
     deps = [SRC, STUB, UNIT] + glob.glob(os.path.join(CSRC, "*.h"))
     if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
         subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
@@ -41,7 +40,7 @@ def test_every_case_is_listed(checker):
 
 
 @pytest.mark.parametrize("case", CASES)
-def test_solver_buffers(checker, case):
+def test_net_layers(checker, case):
     r = subprocess.run([checker, case], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=60)
     assert r.returncode == 0, r.stdout
     assert r.stdout.strip().endswith(case + ": ok"), r.stdout
