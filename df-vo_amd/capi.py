@@ -11,14 +11,15 @@ import numpy as np
 from . import LIB_PATH
 
 
+ITER_NOT_RUN = 3   # dfvo_pipeline_get_iterative: status of a pair whose scale loop did not run
 PUSH_NO_FLOW = 1   # dfvo_session_push_frame flags (include/dfvo_hip.h)
 ERR_RANGE = -4     # DFVO_ERR_RANGE: an activation left f16's range under an f16x3 / f16 packing
-ERR_EMPTY_SELECTION = -5  # dfvo_scale_recovery_iterative: the reference's "sampling threshold is too small." assertion
-ERR_NO_CONSENSUS = -6     # dfvo_scale_recovery_iterative: sklearn's "could not find a valid consensus set"
+ERR_EMPTY_SELECTION = -5  # dfvo_scale_recovery_iterative, dfvo_pipeline_track_end: the reference's "sampling threshold is too small." assertion
+ERR_NO_CONSENSUS = -6     # dfvo_scale_recovery_iterative, dfvo_pipeline_track_end: sklearn's "could not find a valid consensus set"
 
 
 class DfvoError(RuntimeError):
-    pass
+    code = None  # the library's return code, where a failed call raised it (check)
 
 
 _lib = None
@@ -83,6 +84,11 @@ class PipelineOpts(C.Structure):
     _fields_ = [("kp_source", C.c_int), ("kp_score_method", C.c_int), ("kp_sampled_num", C.c_int),
                 ("flow_crop", C.c_double * 4), ("validity_method", C.c_int), ("validity_thre", C.c_double),
                 ("scale_method", C.c_int), ("tracking_method", C.c_int)]
+
+
+class PipelineIterOpts(C.Structure):
+    _fields_ = [("enable", C.c_int), ("kp_src", C.c_int), ("num_row", C.c_int), ("num_col", C.c_int), ("num_bestN", C.c_int),
+                ("rigid_flow_thre", C.c_double), ("optical_flow_thre", C.c_double)]
 
 
 class TrackOut(C.Structure):
@@ -226,6 +232,12 @@ SIGNATURES = {
     "dfvo_pipeline_seed": (_i, [_vp, C.c_uint32]),
     "dfvo_pipeline_set_options": (_i, [_vp, C.POINTER(PipelineOpts)]),
     "dfvo_pipeline_set_graph": (_i, [_vp, _i]),
+    "dfvo_pipeline_set_iterative": (_i, [_vp, C.POINTER(PipelineIterOpts)]),
+    "dfvo_pipeline_get_prev_scale": (_i, [_vp, C.POINTER(_d)]),
+    "dfvo_pipeline_set_prev_scale": (_i, [_vp, _d]),
+    "dfvo_pipeline_set_ref_raw_depth": (_i, [_vp, _vp]),
+    "dfvo_pipeline_set_raw_depth_override": (_i, [_vp, _i, _vp]),
+    "dfvo_pipeline_get_iterative": (_i, [_vp, _i, C.POINTER(ScaleIterOut), _i, _vp, _vp, _vp]),
     "dfvo_pipeline_enqueue_nets": (_i, [_vp, _i, _vp, _vp, _vp]),
     "dfvo_pipeline_track": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(TrackOut)]),
     "dfvo_pipeline_track_begin": (_i, [_vp, _i, _vp, _vp, _vp]),
@@ -234,6 +246,7 @@ SIGNATURES = {
     "dfvo_pipeline_set_ref_image": (_i, [_vp, _vp]),
     "dfvo_pipeline_prefetch_track": (_i, [_vp, _i, _vp, _vp]),
     "dfvo_pipeline_get_flow": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dfvo_pipeline_get_ref_depth": (_i, [_vp, _vp, _vp]),
     "dfvo_pipeline_get_keypoints": (_i, [_vp, _i, _i, _vp, _vp, _vp, _ip]),
     "dfvo_pipeline_get_rng_state": (_i, [_vp, _vp]),
     "dfvo_pipeline_set_rng_state": (_i, [_vp, _vp]),
@@ -283,7 +296,9 @@ def lib():
 def check(rc):
     if rc != 0:
         msg = lib().dfvo_last_error()
-        raise DfvoError("libdfvo_hip call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
+        err = DfvoError("libdfvo_hip call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
+        err.code = rc
+        raise err
 
 
 def check_f16_range(seen, what):

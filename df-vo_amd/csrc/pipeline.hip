@@ -4,7 +4,8 @@
 // (tracking): the host-side glue of the reference (cv2.resize nearest, preprocess_depth, dict passing)
 // becomes device kernels; the pose composition stays on the host (dfvo.py:109-119).
 // dfvo_pipeline_set_options selects the keypoint source (local_bestN | bestN | sampled), the validity and scale-RANSAC methods
-// and hybrid | PnP-only tracking; without it the pipeline runs default_configuration.yml.
+// and hybrid | PnP-only tracking; dfvo_pipeline_set_iterative puts scale_recovery.method "iterative" (the one-call device loop
+// of solver_scale.hip) in the place of find_scale_from_depth; without them the pipeline runs default_configuration.yml.
 #include "../../include/dfvo_hip.h"
 #include <algorithm>
 #include <chrono>
@@ -16,6 +17,7 @@
 
 #include "nets.h"
 #include "ops.h"
+#include "pipeline_iter.h"
 #include "resize_lanczos.h"
 #include "stream_layout.h"
 #include "tracker.h"
@@ -56,6 +58,13 @@ struct Slot {
     Begun begun = IDLE;
     int n = 0;
     const double* depth_override = nullptr;
+    // dfvo_pipeline_set_iterative: the loop's buffers and its record in pinned memory (copied ahead of e_res), the maps the
+    // keypoint stage of the pending pair read, the caller's raw depth for the roll-over (until track_end)
+    RigidKpBuffers rigid;
+    PinnedArr<IterCtl> h_iter;
+    const float* flow_in = nullptr;
+    const float* diff_in = nullptr;
+    const float* raw_override = nullptr;
     // outputs of the nets
     DevArr<float> fwd, bwd, diff, raw_depth;
     DevArr<double> proc_depth;
@@ -81,6 +90,11 @@ struct dfvo_pipeline {
     LanczosResizer feed_resize;  // current frame -> depth-net feed size (when the caller passes no resized frame)
     DevArr<uint8_t> feed_buf;
     DevArr<double> d_T21;
+    // scale_recovery.method iterative: the E-tracker's pose (cur -> ref, unit translation) beside its inverse, and
+    // EssTracker.prev_scale, carried from pair to pair on the device (s_trk orders its readers and writers)
+    DevArr<double> d_E_pose, d_prev_scale;
+    dfvo_pipeline_iter_opts iter = {};
+    RigidKpConfig iter_cfg = {};
     // PnP fallback: processed depth of the reference frame (= the previous pair's current frame)
     PnpBuffers pnp;
     DevArr<double> ref_depth;
@@ -260,8 +274,9 @@ int dfvo_pipeline_create(const dfvo_pipeline_cfg* cfg, dfvo_pipeline** out) {
             sl.raw_depth.alloc(px) || sl.proc_depth.alloc(px))
             return fail(DFVO_ERR_HIP);
     if (p->depth_small.alloc(feed_px) || p->ref_depth.alloc(px) || p->ref_raw.alloc(px) || p->d_T21.alloc(16) ||
-        p->feed_buf.alloc(feed_px * 3))
+        p->feed_buf.alloc(feed_px * 3) || p->d_E_pose.alloc(16) || p->d_prev_scale.alloc(1))
         return fail(DFVO_ERR_HIP);
+    if (hipMemset(p->d_prev_scale, 0, sizeof(double)) != hipSuccess) return fail(DFVO_ERR_HIP);  // EssTracker.prev_scale = 0
     if (p->feed_resize.init(p->H, p->W, p->feedH, p->feedW) != DFVO_OK) return fail(DFVO_ERR_HIP);
     enqueue_mt_seed(p->slots[0].tb, cfg->seed, p->s_trk);
     (void)hipStreamSynchronize(p->s_trk);
@@ -372,6 +387,8 @@ int dfvo_pipeline_set_options(dfvo_pipeline* p, const dfvo_pipeline_opts* o) {
         samples.resize(kp_count);
         generate_kp_samples(crop[0], crop[1], crop[2], crop[3], kp_count, samples.data());
     }
+    DFVO_ARG_CHECK(!(p->iter.enable && p->iter.kp_src == DFVO_ITER_KP_BEST && kp_count > ITER_MAX_KP),
+                   "dfvo_pipeline_set_options: more tracked keypoints than the iterative scale loop takes (16384)");
     p->d_samples.release();
     if (!samples.empty()) {
         P_TRY(p->d_samples.alloc(samples.size()));
@@ -386,6 +403,62 @@ int dfvo_pipeline_set_options(dfvo_pipeline* p, const dfvo_pipeline_opts* o) {
     }
     for (int i = 0; i < 4; ++i) p->sample_crop[i] = crop[i];
     p->opts = *o;
+    return DFVO_OK;
+}
+
+static int pipeline_kp_max(const dfvo_pipeline* p) {
+    const dfvo_pipeline_cfg& c = p->cfg;
+    return tracked_kp_max(p->opts.kp_source, p->opts.kp_sampled_num, c.kp_num_bestN, c.kp_num_row, c.kp_num_col);
+}
+
+int dfvo_pipeline_set_iterative(dfvo_pipeline* p, const dfvo_pipeline_iter_opts* o) {
+    DFVO_ARG_CHECK(p && o, "dfvo_pipeline_set_iterative: null argument");
+    DFVO_ARG_CHECK(!p->started, "dfvo_pipeline_set_iterative: comes before the first dfvo_pipeline_enqueue_nets / _set_ref_*");
+    if (!o->enable) {
+        p->iter = {};
+        return DFVO_OK;
+    }
+    const dfvo_pipeline_cfg& c = p->cfg;
+    if (const char* why = iter_opts_refusal(*o, c.scale_min_samples)) {
+        dfvo::set_last_error(why);
+        return DFVO_ERR_ARG;
+    }
+    const RigidKpConfig rc = iter_rigid_config(*o, c.fx, c.fy, c.cx, c.cy, c.Kinv);
+    int cells, n_best, cap, par;
+    size_t lds;
+    P_TRY(rigid_flow_kp_geometry(p->H, p->W, rc, &cells, &n_best, &cap, &lds, &par));  // the launcher's refusals
+    const int n_sel = cells * n_best, n_trk = pipeline_kp_max(p);
+    DFVO_ARG_CHECK(iter_kp_count_ok(o->kp_src, n_sel, n_trk),
+                   "dfvo_pipeline_set_iterative: more keypoints than the depth-ratio kernel holds in 64 KB of LDS (16384)");
+    // every buffer of the loop at its final size, here: nothing on the per-pair path allocates.  The scale stage's
+    // keypoint-sized buffers hold a round's uniform set as well as the tracked set; local_bestN keeps its selection lists
+    const int kp_need = std::max(std::max(n_sel, n_trk), 16);
+    const bool lb = p->opts.kp_source == DFVO_KP_SOURCE_LOCAL_BESTN;
+    const int lb_cells = lb ? c.kp_num_row * c.kp_num_col : 1, lb_best = lb && lb_cells > 0 ? c.kp_num_bestN / lb_cells : 1;
+    for (Slot& sl : p->slots) {
+        P_TRY(sl.rigid.ensure(p->H, p->W, cells, n_best, cap));
+        P_TRY(sl.tb.ensure_kp(kp_need, lb_cells > 0 ? lb_cells : 1, lb_best > 0 ? lb_best : 1));
+        P_TRY(sl.tb.grow_winner(p->H, p->W));
+        if (!sl.h_iter && sl.h_iter.alloc(1)) return DFVO_ERR_HIP;
+        iter_record_reset(sl.h_iter);
+    }
+    p->iter = *o;
+    p->iter_cfg = rc;
+    return DFVO_OK;
+}
+
+int dfvo_pipeline_get_prev_scale(dfvo_pipeline* p, double* h_scale) {
+    DFVO_ARG_CHECK(p && h_scale, "dfvo_pipeline_get_prev_scale: null argument");
+    DFVO_HIP_CHECK(hipStreamSynchronize(p->s_trk));
+    DFVO_HIP_CHECK(hipMemcpy(h_scale, p->d_prev_scale, sizeof(double), hipMemcpyDeviceToHost));
+    return DFVO_OK;
+}
+
+int dfvo_pipeline_set_prev_scale(dfvo_pipeline* p, double scale) {
+    DFVO_ARG_CHECK(p, "dfvo_pipeline_set_prev_scale: null pipeline");
+    DFVO_ARG_CHECK(p->pending_slot == -1, "dfvo_pipeline_set_prev_scale: a pair is begun and not yet collected");
+    DFVO_HIP_CHECK(hipStreamSynchronize(p->s_trk));
+    DFVO_HIP_CHECK(hipMemcpy(p->d_prev_scale, &scale, sizeof(double), hipMemcpyHostToDevice));
     return DFVO_OK;
 }
 
@@ -467,12 +540,33 @@ int dfvo_pipeline_set_ref_image(dfvo_pipeline* p, const uint8_t* d_img) {
     return dfvo_pipeline_set_ref_depth(p, p->feed_buf, nullptr);
 }
 
-// the current frame's depth becomes the reference depth of the next pair (dfvo.py:  ref_data <- cur_data)
+int dfvo_pipeline_set_ref_raw_depth(dfvo_pipeline* p, const float* d_raw) {
+    DFVO_ARG_CHECK(p && d_raw, "dfvo_pipeline_set_ref_raw_depth: null argument");
+    p->started = true;
+    DFVO_HIP_CHECK(hipMemcpyAsync(p->ref_raw, d_raw, (size_t)p->H * p->W * sizeof(float), hipMemcpyDeviceToDevice, p->s_trk));
+    DFVO_HIP_CHECK(hipStreamSynchronize(p->s_trk));
+    return DFVO_OK;
+}
+
+int dfvo_pipeline_set_raw_depth_override(dfvo_pipeline* p, int slot, const float* d_raw) {
+    DFVO_ARG_CHECK(p && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS), "dfvo_pipeline_set_raw_depth_override: bad argument");
+    p->slots[slot].raw_override = d_raw;
+    return DFVO_OK;
+}
+
+// the current frame's depth becomes the reference depth of the next pair (dfvo.py:  ref_data <- cur_data); with the iterative
+// scale loop on, its raw depth becomes ref_data['raw_depth'] as well, under the same e_roll ordering
 static int roll_ref_depth(dfvo_pipeline* p, int slot, const double* d_depth_override) {
     const size_t px = (size_t)p->H * p->W;
-    DFVO_HIP_CHECK(hipStreamWaitEvent(p->s_trk, p->slots[slot].e_depth, 0));
-    const double* depth = d_depth_override ? d_depth_override : p->slots[slot].proc_depth.p;
+    Slot& sl = p->slots[slot];
+    DFVO_HIP_CHECK(hipStreamWaitEvent(p->s_trk, sl.e_depth, 0));
+    const double* depth = d_depth_override ? d_depth_override : sl.proc_depth.p;
     DFVO_HIP_CHECK(hipMemcpyAsync(p->ref_depth, depth, px * sizeof(double), hipMemcpyDeviceToDevice, p->s_trk));
+    if (p->iter.enable) {
+        const float* raw = sl.raw_override ? sl.raw_override : sl.raw_depth.p;
+        DFVO_HIP_CHECK(hipMemcpyAsync(p->ref_raw, raw, px * sizeof(float), hipMemcpyDeviceToDevice, p->s_trk));
+    }
+    sl.raw_override = nullptr;
     DFVO_HIP_CHECK(hipEventRecord(p->e_roll, p->s_trk));
     p->roll_pending = true;
     p->has_ref_depth = true;
@@ -542,6 +636,8 @@ static int enqueue_pre_part(dfvo_pipeline* p, int slot, const float* d_flow_over
     DFVO_HIP_CHECK(hipStreamWaitEvent(sp, sl.e_flow, 0));
     const float* flow = d_flow_override ? d_flow_override : sl.fwd.p;
     const float* diff = d_diff_override ? d_diff_override : sl.diff.p;
+    sl.flow_in = flow;
+    sl.diff_in = diff;
     // the keypoint stage by source; each leaves tb.kp_ref / tb.kp_cur / tb.kp_info = [n, good_kp_found, ..] behind on sp
     if (o.kp_source == DFVO_KP_SOURCE_BESTN) {
         P_TRY(enqueue_bestn_flow_kp(sl.bestn, flow, diff, p->H, p->W, c.kp_num_bestN, sp, tb.kp_ref, tb.kp_cur, tb.kp_info));
@@ -591,8 +687,10 @@ int dfvo_pipeline_track_begin(dfvo_pipeline* p, int slot, const float* d_flow_ov
     if (trace && !tb.ev_t[0])
         for (int i = 0; i < 4; i++) DFVO_HIP_CHECK(hipEventCreate(&tb.ev_t[i]));
     const bool pnp_only = p->opts.tracking_method == DFVO_TRACKING_PNP;
-    // side stream: the scale stage's fills leave the dependent chain
-    if (!pnp_only) P_TRY(enqueue_scale_prepare(tb, p->H, p->W));
+    const bool iterative = p->iter.enable && !pnp_only;
+    // side stream: the scale stage's fills leave the dependent chain (the iterative loop clears the map itself, every round)
+    if (!pnp_only && !iterative) P_TRY(enqueue_scale_prepare(tb, p->H, p->W));
+    if (iterative) iter_record_reset(sl.h_iter);  // (the slot is idle: its last record was copied long ago)
     // A pre-part nobody prefetched: in the lane layout it goes onto the chain's lane (s), whose next work needs it anyway --
     // the depth lane may already hold later pairs' nets, and it would run behind them
     if (!sl.prefetched)
@@ -622,12 +720,24 @@ int dfvo_pipeline_track_begin(dfvo_pipeline* p, int slot, const float* d_flow_ov
     }
     PoseConfig pc;
     fill_pose_cfg(c, p->opts, &pc);
-    P_TRY(enqueue_pose_e_part(tb, n, pc, s, p->d_T21));  // waits for tb.ev_h (the prefetched half) on the device
+    // waits for tb.ev_h (the prefetched half) on the device
+    P_TRY(enqueue_pose_e_part(tb, n, pc, s, p->d_T21, iterative ? p->d_E_pose.p : nullptr));
     DFVO_HIP_CHECK(hipStreamWaitEvent(s, sl.e_depth, 0));
     ScaleConfig sc;
     fill_scale_cfg(c, p->opts, &sc);
     const double* depth = d_depth_override ? d_depth_override : sl.proc_depth.p;
-    P_TRY(enqueue_find_scale(tb, n, p->d_T21, depth, p->H, p->W, sc, s, tb.pose, true));
+    if (iterative) {
+        // E_tracker.py:509-569, all rounds, gated and started from prev_scale on the device; p->ref_raw is ordered on s by
+        // set_ref_* / the previous pair's roll-over, like the reference depth
+        IterDevice dev;
+        dev.prev_scale = p->d_prev_scale;
+        dev.gate = tb.pose;
+        P_TRY(enqueue_scale_recovery_iterative(tb, sl.rigid, sl.flow_in, sl.diff_in, p->ref_raw, depth, p->H, p->W, p->iter_cfg, sc,
+                                               p->d_E_pose, p->d_T21, 0.0, p->iter.kp_src, n, s, &dev));
+        DFVO_HIP_CHECK(hipMemcpyAsync(sl.h_iter.p, sl.rigid.ctl, sizeof(IterCtl), hipMemcpyDeviceToHost, s));
+    } else {
+        P_TRY(enqueue_find_scale(tb, n, p->d_T21, depth, p->H, p->W, sc, s, tb.pose, true));
+    }
     if (tb.ev_t[3]) DFVO_HIP_CHECK(hipEventRecord(tb.ev_t[3], s));
     DFVO_HIP_CHECK(hipMemcpyAsync(&sl.h_res.p->pose, tb.pose, sizeof(PoseState), hipMemcpyDeviceToHost, s));
     DFVO_HIP_CHECK(hipMemcpyAsync(&sl.h_res.p->scale, tb.scale_out, sizeof(ScaleResult), hipMemcpyDeviceToHost, s));
@@ -689,11 +799,29 @@ int dfvo_pipeline_track_end(dfvo_pipeline* p, int slot, dfvo_track_out* out) {
     out->num_valid = ps.num_valid;
     out->cheirality = ps.cheirality;
     const bool t_zero = ps.t[0] == 0 && ps.t[1] == 0 && ps.t[2] == 0;
-    out->scale = t_zero ? 0.0 : sr.scale;  // dfvo.py:198: scale recovery only when ||t|| != 0
+    double scale = sr.scale;
+    if (p->iter.enable) {
+        const IterCtl ctl = *sl.h_iter.p;
+        scale = ctl.scale;  // the last completed round's
+        if (!t_zero && (ctl.status == ITER_EMPTY || ctl.status == ITER_NO_CONSENSUS)) {
+            // where the reference raises: the pair is over (the slot idle, nothing pending, the depths rolled over), the
+            // RandomState and prev_scale hold what the reference had at the raise, `out` the E-tracker's pose
+            out->scale = ctl.n_iter > 0 ? scale : 0.0;
+            out->status = DFVO_TRACK_E;
+            P_TRY(roll_ref_depth(p, slot, d_depth_override));
+            if (ctl.status == ITER_EMPTY) {
+                dfvo::set_last_error("dfvo_pipeline_track_end: sampling threshold is too small (no rigid-flow keypoint selected)");
+                return DFVO_ERR_EMPTY_SELECTION;
+            }
+            dfvo::set_last_error("dfvo_pipeline_track_end: RANSAC could not find a valid consensus set");
+            return DFVO_ERR_NO_CONSENSUS;
+        }
+    }
+    out->scale = t_zero ? 0.0 : scale;  // dfvo.py:198: scale recovery only when ||t|| != 0
     out->scale_n_valid = sr.n_valid;
     out->scale_n_trials = sr.n_trials;
     out->scale_n_inliers = sr.n_inliers;
-    if (t_zero || sr.scale == -1.0) {  // dfvo.py:225-250: PnP on (ref keypoints + ref depth) -> cur keypoints
+    if (t_zero || scale == -1.0) {  // dfvo.py:225-250: PnP on (ref keypoints + ref depth) -> cur keypoints
         out->status = DFVO_TRACK_NEEDS_PNP;
         if (p->has_ref_depth) {
             PnpConfig pc3;
@@ -741,9 +869,10 @@ int dfvo_pipeline_track(dfvo_pipeline* p, int slot, const float* d_flow_override
                         const double* d_depth_override, dfvo_track_out* out) {
     DFVO_ARG_CHECK(p && out && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS), "dfvo_pipeline_track: bad argument");
     P_TRY(dfvo_pipeline_track_begin(p, slot, d_flow_override, d_diff_override, d_depth_override));
-    P_TRY(dfvo_pipeline_track_end(p, slot, out));
+    const int rc_end = dfvo_pipeline_track_end(p, slot, out);
+    if (rc_end != DFVO_OK && rc_end != DFVO_ERR_EMPTY_SELECTION && rc_end != DFVO_ERR_NO_CONSENSUS) return rc_end;
     DFVO_HIP_CHECK(hipStreamSynchronize(p->s_trk));  // (synchronous, as documented: the roll-over copy included)
-    return DFVO_OK;
+    return rc_end;
 }
 
 int dfvo_pipeline_get_flow(dfvo_pipeline* p, int slot, float* h_fwd, float* h_bwd, float* h_diff, float* h_raw_depth,
@@ -760,6 +889,15 @@ int dfvo_pipeline_get_flow(dfvo_pipeline* p, int slot, float* h_fwd, float* h_bw
     return DFVO_OK;
 }
 
+int dfvo_pipeline_get_ref_depth(dfvo_pipeline* p, float* h_raw_depth, double* h_depth) {
+    DFVO_ARG_CHECK(p, "dfvo_pipeline_get_ref_depth: null pipeline");
+    const size_t px = (size_t)p->H * p->W;
+    DFVO_HIP_CHECK(hipDeviceSynchronize());
+    if (h_raw_depth) DFVO_HIP_CHECK(hipMemcpy(h_raw_depth, p->ref_raw, px * sizeof(float), hipMemcpyDeviceToHost));
+    if (h_depth) DFVO_HIP_CHECK(hipMemcpy(h_depth, p->ref_depth, px * sizeof(double), hipMemcpyDeviceToHost));
+    return DFVO_OK;
+}
+
 int dfvo_pipeline_get_keypoints(dfvo_pipeline* p, int slot, int cap, double* h_kp_ref, double* h_kp_cur,
                                 uint8_t* h_inliers, int* n_out) {
     DFVO_ARG_CHECK(p && n_out && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS) && cap >= 0,
@@ -773,6 +911,36 @@ int dfvo_pipeline_get_keypoints(dfvo_pipeline* p, int slot, int cap, double* h_k
     if (n > 0 && h_kp_ref) DFVO_HIP_CHECK(hipMemcpy(h_kp_ref, tb.kp_ref, sizeof(double) * 2 * n, hipMemcpyDeviceToHost));
     if (n > 0 && h_kp_cur) DFVO_HIP_CHECK(hipMemcpy(h_kp_cur, tb.kp_cur, sizeof(double) * 2 * n, hipMemcpyDeviceToHost));
     if (n > 0 && h_inliers) DFVO_HIP_CHECK(hipMemcpy(h_inliers, tb.best_inliers, n, hipMemcpyDeviceToHost));
+    return DFVO_OK;
+}
+
+int dfvo_pipeline_get_iterative(dfvo_pipeline* p, int slot, dfvo_scale_iter_out* out, int cap, double* h_kp_ref, double* h_kp_cur,
+                                float* h_rigid_flow_diff) {
+    DFVO_ARG_CHECK(p && out && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS) && cap >= 0, "dfvo_pipeline_get_iterative: bad argument");
+    DFVO_ARG_CHECK(p->iter.enable, "dfvo_pipeline_get_iterative: the iterative scale recovery is not on (dfvo_pipeline_set_iterative)");
+    Slot& sl = p->slots[slot];
+    DFVO_ARG_CHECK(sl.begun == IDLE, "dfvo_pipeline_get_iterative: the slot's pair is not collected yet (track_end)");
+    DFVO_HIP_CHECK(hipDeviceSynchronize());
+    const IterCtl ctl = *sl.h_iter.p;
+    const int n = ctl.sel_round >= 0 ? ctl.n_kp[ctl.sel_round] : 0;
+    out->scale = ctl.scale;
+    out->n_iter = ctl.n_iter;
+    out->n_kp = n;
+    out->kp_round = ctl.sel_round;
+    out->status = ctl.status;
+    out->device_ms = 0.f;
+    for (int r = 0; r < ITER_ROUNDS; r++) {
+        out->scale_in[r] = ctl.scale_in[r];
+        out->scale_out[r] = ctl.scale_out[r];
+        out->n_kp_round[r] = ctl.n_kp[r];
+    }
+    const int m = n < cap ? n : cap;
+    const size_t sc = (size_t)sl.rigid.sel_cap * 2;  // rigid.kp: [best ref | best cur | uniform ref | uniform cur], sel_cap x 2 each
+    if (m > 0 && h_kp_ref) DFVO_HIP_CHECK(hipMemcpy(h_kp_ref, sl.rigid.kp + 2 * sc, sizeof(double) * 2 * m, hipMemcpyDeviceToHost));
+    if (m > 0 && h_kp_cur) DFVO_HIP_CHECK(hipMemcpy(h_kp_cur, sl.rigid.kp + 3 * sc, sizeof(double) * 2 * m, hipMemcpyDeviceToHost));
+    if (ctl.sel_round >= 0 && h_rigid_flow_diff)
+        DFVO_HIP_CHECK(hipMemcpy(h_rigid_flow_diff, sl.rigid.rdiff_of(ctl.sel_round, p->H, p->W), sizeof(float) * (size_t)p->H * p->W,
+                                 hipMemcpyDeviceToHost));
     return DFVO_OK;
 }
 

@@ -372,7 +372,18 @@ int enqueue_pose_h_part(TrackerBuffers& tb, int n_bound, const PoseConfig& cfg, 
 
 // RNG-consuming half: `repeat` x (shuffle, findEssentialMat, GRIC-E) as one batch on tb.s_rep[0] (after tb.ev_start),
 // then on s (after tb.ev_h): validity bookkeeping, recoverPose, pose / T21.  n_host = the keypoint count.
-int enqueue_pose_e_part(TrackerBuffers& tb, int n_host, const PoseConfig& cfg, hipStream_t s, double* d_T21) {
+// one lane: the accepted pose as a 4 x 4 (E_pose.pose of dfvo.py:172), for the iterative scale loop
+__global__ void k_pose_matrix(const PoseState* __restrict__ ps, double* __restrict__ E) {
+    if (threadIdx.x != 0) return;
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) E[r * 4 + c] = ps->R[r * 3 + c];
+        E[r * 4 + 3] = ps->t[r];
+    }
+    E[12] = E[13] = E[14] = 0;
+    E[15] = 1;
+}
+
+int enqueue_pose_e_part(TrackerBuffers& tb, int n_host, const PoseConfig& cfg, hipStream_t s, double* d_T21, double* d_E_pose) {
     DFVO_ARG_CHECK(n_host >= 0 && n_host <= tb.kp_cap, "compute_pose_2d2d: keypoint capacity");
     DFVO_ARG_CHECK(cfg.repeat >= 1 && cfg.repeat <= MAX_REP, "compute_pose_2d2d: repeat out of range");
     DFVO_HIP_CHECK(hipStreamWaitEvent(s, tb.ev_h, 0));
@@ -449,6 +460,7 @@ int enqueue_pose_e_part(TrackerBuffers& tb, int n_host, const PoseConfig& cfg, h
         rc = enqueue_recover_pose(tb.ws_rep[0], (const double*)((const char*)tb.pose.p + offsetof(PoseState, best_E)),
                                   tb.kp_cur, tb.kp_ref, n_host, cfg.fx, cfg.cx, cfg.cy, s, fin);
         if (rc != DFVO_OK) return rc;
+        if (d_E_pose) hipLaunchKernelGGL(k_pose_matrix, dim3(1), dim3(64), 0, s, (const PoseState*)tb.pose.p, d_E_pose);
         if (tb.ev_t[2]) DFVO_HIP_CHECK(hipEventRecord(tb.ev_t[2], s));
         if (tb.mark(7, s) != DFVO_OK) return DFVO_ERR_HIP;
     }

@@ -324,12 +324,16 @@ struct IterMats {
     float Kinv[9], K[9];
 };
 
-__global__ void k_iter_init(IterCtl* __restrict__ ctl, double prev_scale) {
+// d_prev_scale (optional): the carried scale on the device, read instead of the host value; gate (optional): the E-tracker's
+// pose -- scale recovery runs only when ||t|| != 0 (dfvo.py:182)
+__global__ void k_iter_init(IterCtl* __restrict__ ctl, double prev_scale, const double* __restrict__ d_prev_scale,
+                            const PoseState* __restrict__ gate) {
     if (threadIdx.x != 0) return;
-    ctl->scale = prev_scale;
-    ctl->done = 0;
+    const bool gated = gate && gate->t[0] == 0 && gate->t[1] == 0 && gate->t[2] == 0;
+    ctl->scale = d_prev_scale ? *d_prev_scale : prev_scale;
+    ctl->done = gated ? 1 : 0;
     ctl->n_iter = 0;
-    ctl->status = ITER_RUNNING;
+    ctl->status = gated ? ITER_NOT_RUN : ITER_RUNNING;
     ctl->sel_round = -1;
     for (int r = 0; r < ITER_ROUNDS; ++r) {
         ctl->scale_in[r] = 0.0;
@@ -396,10 +400,17 @@ __global__ void k_iter_end(IterCtl* __restrict__ ctl, int round, const ScaleResu
     if (threadIdx.x == 0) iter_end(ctl, round, res);
 }
 
+// behind k_iter_end, one lane: self.prev_scale = new_scale of the last completed round (E_tracker.py:559); a call that
+// completed no round (gated, an empty first selection, no consensus set in round 0) leaves it as it was
+__global__ void k_iter_store_prev(const IterCtl* __restrict__ ctl, double* __restrict__ d_prev_scale) {
+    if (threadIdx.x == 0 && ctl->n_iter > 0) *d_prev_scale = ctl->scale;
+}
+
 int enqueue_scale_recovery_iterative(TrackerBuffers& tb, RigidKpBuffers& rb, const float* d_flow, const float* d_odiff,
                                      const float* d_depth32_ref, const double* d_depth64_cur, int H, int W,
                                      const RigidKpConfig& cfg, const ScaleConfig& scfg, const double* d_E_pose,
-                                     const double* d_T21, double prev_scale, int kp_src, int n_kp_best, hipStream_t s) {
+                                     const double* d_T21, double prev_scale, int kp_src, int n_kp_best, hipStream_t s,
+                                     const IterDevice* dev) {
     DFVO_ARG_CHECK(d_flow && d_odiff && d_depth32_ref && d_depth64_cur && d_E_pose && d_T21 && H > 0 && W > 0,
                    "scale_recovery_iterative: bad argument");
     DFVO_ARG_CHECK(kp_src == 0 || kp_src == 1, "scale_recovery_iterative: kp_src is 0 (kp_depth) or 1 (kp_best)");
@@ -430,7 +441,8 @@ int enqueue_scale_recovery_iterative(TrackerBuffers& tb, RigidKpBuffers& rb, con
     const bool abs_diff = scfg.method == 1;
     const int px = H * W;
     tb.seg_mask &= ~0x700u;  // no stage marks between the rounds: dfvo_tracker_stage_ms reports none for the scale stage
-    hipLaunchKernelGGL(k_iter_init, dim3(1), dim3(64), 0, s, ctl, prev_scale);
+    hipLaunchKernelGGL(k_iter_init, dim3(1), dim3(64), 0, s, ctl, prev_scale, (const double*)(dev ? dev->prev_scale : nullptr),
+                       dev ? dev->gate : (const PoseState*)nullptr);
     for (int r = 0; r < ITER_ROUNDS; ++r) {
         hipLaunchKernelGGL(k_iter_begin, dim3(1), dim3(64), 0, s, ctl, r, (const ScaleResult*)tb.scale_out.p, d_E_pose, m,
                            rb.mats.p);
@@ -452,6 +464,8 @@ int enqueue_scale_recovery_iterative(TrackerBuffers& tb, RigidKpBuffers& rb, con
                            g_sklearn_r2_nan_below_two.load(), skip);
     }
     hipLaunchKernelGGL(k_iter_end, dim3(1), dim3(64), 0, s, ctl, ITER_ROUNDS - 1, (const ScaleResult*)tb.scale_out.p);
+    if (dev && dev->prev_scale)
+        hipLaunchKernelGGL(k_iter_store_prev, dim3(1), dim3(64), 0, s, (const IterCtl*)ctl, dev->prev_scale);
     DFVO_HIP_CHECK(hipGetLastError());
     return DFVO_OK;
 }

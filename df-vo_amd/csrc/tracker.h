@@ -215,6 +215,7 @@ constexpr int ITER_ROUNDS = 5;
 constexpr int ITER_RUNNING = 0;       // status
 constexpr int ITER_EMPTY = 1;         // opt_rigid_flow_kp selected nothing (the reference's assertion) in round n_iter
 constexpr int ITER_NO_CONSENSUS = 2;  // sklearn's "could not find a valid consensus set" in round n_iter
+constexpr int ITER_NOT_RUN = 3;       // the gate was closed (IterDevice::gate: ||t|| == 0, dfvo.py:182): no round, no draw, no write
 struct IterCtl {
     double scale;   // in: prev_scale; out: the last round's scale
     int done;       // the skip flag of every later kernel
@@ -256,7 +257,10 @@ int enqueue_compute_pose_2d2d(TrackerBuffers& tb, int n_host, const PoseConfig& 
 // update_global_pose over a gathered sequence in one launch (rows [n][17] -> poses [n+1][16]); d_bad[0] = first status-2 row or -1
 int enqueue_compose_trajectory(const double* d_rows, int n, const double* d_first, double* d_poses, int* d_bad, hipStream_t s);
 int enqueue_pose_h_part(TrackerBuffers& tb, int n_bound, const PoseConfig& cfg, hipStream_t sh);
-int enqueue_pose_e_part(TrackerBuffers& tb, int n_host, const PoseConfig& cfg, hipStream_t s, double* d_T21);
+// d_E_pose (optional): 16 doubles that receive the accepted pose itself, [R t; 0 0 0 1] (cur -> ref, unit translation: the
+// E_pose of scale_recovery_iterative), from a one-lane kernel behind recoverPose
+int enqueue_pose_e_part(TrackerBuffers& tb, int n_host, const PoseConfig& cfg, hipStream_t s, double* d_T21,
+                        double* d_E_pose = nullptr);
 // snap (optional): mt_snapshots(tb.mt_state) -- the state before the first and behind every shuffle
 int enqueue_mt_shuffle(uint32_t* mt_state, const int* d_n, int n_host, int repeat, int perm_stride, int* perm,
                        hipStream_t s, uint32_t* snap = nullptr);
@@ -280,10 +284,19 @@ int enqueue_scale_prepare(TrackerBuffers& tb, int H, int W);
 // k_scale_ratios keeps one int per keypoint in dynamic LDS: at most ITER_MAX_KP keypoints (64 KB, the size a kernel gets
 // without asking for more).
 constexpr int ITER_MAX_KP = 16384;
+// dev (the fused pipeline): the loop starts and ends on the device.  prev_scale: a device double read by the loop's first
+// kernel in place of the host value and written back behind the last round when at least one round completed (self.prev_scale,
+// E_tracker.py:559; the scale -1 included); gate: the E-tracker's PoseState -- a zero translation ends the call in its first
+// kernel with ITER_NOT_RUN, and every later kernel returns through the skip pointer.
+struct IterDevice {
+    double* prev_scale = nullptr;
+    const PoseState* gate = nullptr;
+};
 int enqueue_scale_recovery_iterative(TrackerBuffers& tb, RigidKpBuffers& rb, const float* d_flow, const float* d_odiff,
                                      const float* d_depth32_ref, const double* d_depth64_cur, int H, int W,
                                      const RigidKpConfig& cfg, const ScaleConfig& scfg, const double* d_E_pose,
-                                     const double* d_T21, double prev_scale, int kp_src, int n_kp_best, hipStream_t s);
+                                     const double* d_T21, double prev_scale, int kp_src, int n_kp_best, hipStream_t s,
+                                     const IterDevice* dev = nullptr);
 int enqueue_ransac_regressor(TrackerBuffers& tb, int n, bool y_is_ones, const ScaleConfig& cfg, hipStream_t s);
 int set_sklearn_compat(const char* version);  // "0.20" (the reference's pin, default) | "0.22" and later
 

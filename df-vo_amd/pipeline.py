@@ -1,8 +1,9 @@
 """Host driver of the fused per-pair pipeline (dfvo_pipeline_*): configuration marshalling, the
 double-buffered net/solver software pipeline, and pose accumulation as in
 the reference's libs/dfvo.py:109-119 (update_global_pose) and :121-262 (tracking: the hybrid path of
-default_configuration.yml, and through the option keys below the keypoint sources, validity / scale methods and the
-PnP-only tracking of the shipped ablation files; options_from_cfg maps the reference's configuration object to them)."""
+default_configuration.yml, and through the option keys below the keypoint sources, validity / scale methods, the
+PnP-only tracking and the iterative scale recovery of the shipped ablation files; options_from_cfg maps the reference's
+configuration object to them)."""
 import ctypes as C
 
 import numpy as np
@@ -27,6 +28,14 @@ _KP_SCORE = {"flow": 0, "flow_ratio": 1}
 _VALIDITY = {"GRIC": 0, "flow": 1, "homo_ratio": 2}
 _SCALE_METHOD = {"depth_ratio": 0, "abs_diff": 1}
 _TRACKING = {"hybrid": 0, "PnP": 1}
+
+# dfvo_pipeline_set_iterative: scale_recovery.method and the kp_selection.rigid_flow_kp block (ablation_scale_iterative.yml).
+# Kept apart from OPTION_DEFAULTS, whose keys are the fields of capi.PipelineOpts
+ITER_DEFAULTS = dict(scale_recovery="simple", iter_kp_src="kp_best", rigid_num_bestN=2000, rigid_num_row=10, rigid_num_col=10,
+                     rigid_flow_thre=5.0, optical_flow_thre=0.1)
+_SCALE_RECOVERY = {"simple": 0, "iterative": 1}
+_ITER_KP_SRC = {"kp_depth": 0, "kp_best": 1}
+ITER_STATUS = {0: "finished", 1: "empty_selection", 2: "no_consensus", 3: "not_run"}
 
 
 def _choice(o, key, table):
@@ -62,6 +71,25 @@ def check_options(o):
     return f
 
 
+def check_iter_options(o):
+    """the iterative-scale keys of `o` (ITER_DEFAULTS filled in) as the fields of capi.PipelineIterOpts; ValueError on a bad value"""
+    f = dict(enable=_choice(o, "scale_recovery", _SCALE_RECOVERY), kp_src=_choice(o, "iter_kp_src", _ITER_KP_SRC))
+    for key, field in (("rigid_num_bestN", "num_bestN"), ("rigid_num_row", "num_row"), ("rigid_num_col", "num_col")):
+        v = o[key]
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or v < 1:
+            raise ValueError("%s = %r: a positive integer" % (key, v))
+        f[field] = int(v)
+    for key in ("rigid_flow_thre", "optical_flow_thre"):
+        v = o[key]
+        if v is None or isinstance(v, (bool, str)) or not np.isfinite(float(v)):
+            raise ValueError("%s = %r: a finite threshold" % (key, v))
+        f[key] = float(v)
+    if f["num_bestN"] < f["num_row"] * f["num_col"]:
+        raise ValueError("rigid_num_bestN = %r: fewer than one keypoint per cell of the %d x %d grid (rigid_num_row, rigid_num_col)"
+                         % (o["rigid_num_bestN"], f["num_row"], f["num_col"]))
+    return f
+
+
 def options_from_cfg(cfg):
     """The reference's configuration object (default_cfg.Cfg / EasyDict of options/examples/*.yml) as the override dict of
     TrackingPipeline -- only the keys that differ from DEFAULTS / OPTION_DEFAULTS, so default_configuration.yml maps to {}.
@@ -74,14 +102,24 @@ def options_from_cfg(cfg):
             node = node[k]
         return node
 
+    method = get("scale_recovery.method", "simple")
+    if method not in _SCALE_RECOVERY:
+        raise NotImplementedError("scale_recovery.method: %s: not run by the fused pipeline" % method)
+    iterative = method == "iterative"
     for path in ("e_tracker.iterative_kp.enable", "scale_recovery.iterative_kp.enable", "pnp_tracker.iterative_kp.enable",
                  "kp_selection.rigid_flow_kp.enable", "kp_selection.depth_consistency.enable", "deep_pose.enable",
                  "online_finetune.enable"):
-        if get(path, False):
+        if get(path, False) and not (iterative and path == "kp_selection.rigid_flow_kp.enable"):
             raise NotImplementedError("%s: not run by the fused pipeline" % path)
-    if get("scale_recovery.method", "simple") != "simple":
-        raise NotImplementedError("scale_recovery.method: %s: not run by the fused pipeline" % get("scale_recovery.method"))
+    if iterative and not get("kp_selection.rigid_flow_kp.enable", False):
+        # (kp_selection_good_depth returns nothing then, and the loop dies on its missing key: E_tracker.py:541,671)
+        raise NotImplementedError("kp_selection.rigid_flow_kp.enable: False under scale_recovery.method: iterative: the loop "
+                                  "selects its keypoints there")
     srcs = {k: get(k + ".kp_src", "kp_best") for k in ("e_tracker", "scale_recovery", "pnp_tracker")}
+    iter_kp_src = "kp_best"
+    if iterative and srcs["scale_recovery"] == "kp_depth":  # each round's scale from that round's rigid-flow keypoints
+        iter_kp_src = "kp_depth"
+        srcs["scale_recovery"] = srcs["e_tracker"]
     for k, v in srcs.items():
         if v == "kp_depth":
             raise NotImplementedError("%s.kp_src: kp_depth: not run by the fused pipeline" % k)
@@ -128,12 +166,21 @@ def options_from_cfg(cfg):
         fc = get("crop.flow_crop")
         if fc is not None:
             full["flow_crop"] = tuple(tuple(float(v) for v in r) for r in fc)
+    if iterative:
+        rk = "kp_selection.rigid_flow_kp."
+        full.update(scale_recovery="iterative", iter_kp_src=iter_kp_src, rigid_num_bestN=get(rk + "num_bestN", 2000),
+                    rigid_num_row=get(rk + "num_row", 10), rigid_num_col=get(rk + "num_col", 10),
+                    rigid_flow_thre=get(rk + "rigid_flow_thre", 5), optical_flow_thre=get(rk + "optical_flow_thre", 0.1))
     base = dict(DEFAULTS)
     base.update(OPTION_DEFAULTS)
+    base.update(ITER_DEFAULTS)
     out = {k: v for k, v in full.items() if base.get(k) != v}
     check = dict(OPTION_DEFAULTS)
     check.update({k: v for k, v in out.items() if k in OPTION_DEFAULTS})
     check_options(check)
+    check = dict(ITER_DEFAULTS)
+    check.update({k: v for k, v in out.items() if k in ITER_DEFAULTS})
+    check_iter_options(check)
     return out
 
 
@@ -141,11 +188,16 @@ class TrackingPipeline:
     def __init__(self, img_h, img_w, feed_h, feed_w, K, flow_sd, depth_sd, **overrides):
         o = dict(DEFAULTS)
         o.update(OPTION_DEFAULTS)
+        io = dict(ITER_DEFAULTS)
+        io.update({k: overrides.pop(k) for k in list(overrides) if k in ITER_DEFAULTS})
         o.update(overrides)
         fields = check_options(o)  # (before anything touches the device: a bad value is a ValueError)
+        iter_fields = check_iter_options(io)
         capi.require_gpu()
         self.lib = capi.lib()
         self.opts = o
+        self.iter_opts = io
+        self.iterative = io["scale_recovery"] == "iterative"
         self.H, self.W, self.feed_h, self.feed_w = img_h, img_w, feed_h, feed_w
         K = np.asarray(K, np.float64)
         self.K = K
@@ -176,6 +228,12 @@ class TrackingPipeline:
                 po.flow_crop[i] = v
             try:
                 capi.check(self.lib.dfvo_pipeline_set_options(h, C.byref(po)))
+            except capi.DfvoError:
+                self.close()
+                raise
+        if self.iterative:  # (behind set_options: the bound on the tracked keypoints depends on the keypoint source)
+            try:
+                capi.check(self.lib.dfvo_pipeline_set_iterative(h, C.byref(capi.PipelineIterOpts(**iter_fields))))
             except capi.DfvoError:
                 self.close()
                 raise
@@ -230,16 +288,22 @@ class TrackingPipeline:
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         capi.check(self.lib.dfvo_pipeline_prefetch_track(self.h, slot, p(flow), p(diff)))
 
-    def track(self, slot, flow=None, diff=None, depth=None):
+    def track(self, slot, flow=None, diff=None, depth=None, raw_depth=None):
+        """raw_depth (iterative scale recovery, with `depth`): the raw float32 depth of the current frame, which becomes the
+        next pair's ref_data['raw_depth'] in place of the depth net's"""
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        if raw_depth is not None:
+            self.set_raw_depth_override(slot, raw_depth)
         out = capi.TrackOut()
         capi.check(self.lib.dfvo_pipeline_track(self.h, slot, p(flow), p(diff), p(depth), C.byref(out)))
         return out
 
-    def track_begin(self, slot, flow=None, diff=None, depth=None):
+    def track_begin(self, slot, flow=None, diff=None, depth=None, raw_depth=None):
         """first half of track(): enqueues the RandomState-ordered chain of `slot` and returns; the host can feed the nets of
         the pairs ahead while it runs.  Pair k + 1 must not be begun before track_end(k) returned."""
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        if raw_depth is not None:
+            self.set_raw_depth_override(slot, raw_depth)
         capi.check(self.lib.dfvo_pipeline_track_begin(self.h, slot, p(flow), p(diff), p(depth)))
 
     def track_end(self, slot):
@@ -247,10 +311,42 @@ class TrackingPipeline:
         capi.check(self.lib.dfvo_pipeline_track_end(self.h, slot, C.byref(out)))
         return out
 
-    def set_ref_depth(self, d_feed=None, depth=None):
-        """depth of the first reference frame: the uint8 feed image (runs the depth net) or a processed depth map"""
+    def set_ref_depth(self, d_feed=None, depth=None, raw_depth=None):
+        """depth of the first reference frame: the uint8 feed image (runs the depth net) or a processed depth map; raw_depth
+        (with `depth`, iterative scale recovery): its raw float32 depth, ref_data['raw_depth'] of the first pair"""
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         capi.check(self.lib.dfvo_pipeline_set_ref_depth(self.h, p(d_feed), p(depth)))
+        if raw_depth is not None:
+            capi.check(self.lib.dfvo_pipeline_set_ref_raw_depth(self.h, p(raw_depth)))
+
+    def set_raw_depth_override(self, slot, raw_depth):
+        """the raw float32 depth [H,W] of `slot`'s current frame for the roll-over, until the slot's track_end (None withdraws)"""
+        capi.check(self.lib.dfvo_pipeline_set_raw_depth_override(
+            self.h, slot, C.c_void_p(raw_depth.data_ptr()) if raw_depth is not None else None))
+
+    def get_prev_scale(self):
+        """EssTracker.prev_scale as the pipeline carries it on the device (iterative scale recovery)"""
+        v = C.c_double(0.0)
+        capi.check(self.lib.dfvo_pipeline_get_prev_scale(self.h, C.byref(v)))
+        return v.value
+
+    def set_prev_scale(self, scale):
+        capi.check(self.lib.dfvo_pipeline_set_prev_scale(self.h, float(scale)))
+
+    def get_iterative(self, slot, want_map=False):
+        """the iterative scale loop's record of the pair last collected from `slot`: dict(status "finished" | "empty_selection"
+        | "no_consensus" | "not_run", scale, n_iter, kp_round, scale_in [5], scale_out [5], n_kp_round [5], ref_kp / cur_kp [n,2]:
+        the uniform keypoints of the last round that selected any, rigid_flow_diff [H,W] f32 with want_map)"""
+        cap = max(1, self.iter_opts["rigid_num_bestN"])
+        out = capi.ScaleIterOut()
+        kr, kc = np.zeros((cap, 2)), np.zeros((cap, 2))
+        m = np.zeros((self.H, self.W), np.float32) if want_map else None
+        capi.check(self.lib.dfvo_pipeline_get_iterative(self.h, slot, C.byref(out), cap, capi.as_ptr(kr), capi.as_ptr(kc),
+                                                        capi.as_ptr(m)))
+        assert out.n_kp <= cap
+        return dict(status=ITER_STATUS[out.status], scale=out.scale, n_iter=out.n_iter, kp_round=out.kp_round,
+                    scale_in=list(out.scale_in), scale_out=list(out.scale_out), n_kp_round=list(out.n_kp_round),
+                    ref_kp=kr[:out.n_kp], cur_kp=kc[:out.n_kp], rigid_flow_diff=m if out.kp_round >= 0 else None)
 
     def set_ref_image(self, d_img):
         """depth of the first reference frame from the full-size uint8 frame (device LANCZOS resize + depth net)"""
@@ -284,6 +380,13 @@ class TrackingPipeline:
         capi.check(self.lib.dfvo_pipeline_get_flow(self.h, slot, capi.as_ptr(fwd), capi.as_ptr(bwd), capi.as_ptr(diff),
                                                    capi.as_ptr(raw), capi.as_ptr(dep)))
         return fwd, bwd, diff, raw, dep
+
+    def get_ref_depth(self):
+        """(raw [H,W] f32, processed [H,W] f64): the reference frame's depths as the next pair will read them"""
+        raw = np.zeros((self.H, self.W), np.float32)
+        dep = np.zeros((self.H, self.W), np.float64)
+        capi.check(self.lib.dfvo_pipeline_get_ref_depth(self.h, capi.as_ptr(raw), capi.as_ptr(dep)))
+        return raw, dep
 
     def get_keypoints(self, slot, cap=None):
         """the tracked keypoints of the reference / current frame [n,2] f64 and the E-tracker's inlier mask [n] bool for `slot`"""

@@ -6,7 +6,8 @@ Pair j = (frame j, frame j+1).  A chunk [lo, hi) of pairs needs frames lo .. hi:
 is recomputed by the rank that owns the chunk -- no activation exchange between ranks).  The nets run `ahead` pairs
 ahead of the solver stage; nothing but the relative poses leaves the device.  The driver reads nothing but the status word
 and the pose of a pair, so it runs a pipeline of any tracking configuration (pipeline.TrackingPipeline's kp_source / validity /
-scale_method / tracking_method keys, TrackingPipeline.from_cfg): with tracking_method "PnP" every row has status 3.
+scale_method / tracking_method / scale_recovery keys, TrackingPipeline.from_cfg): with tracking_method "PnP" every row has
+status 3; with scale_recovery "iterative" a chunk starts from prev_scale 0 and runs on one rank only.
 
 RandomState modes (SURVEY hard part 2):
   "sequential"  one stream seeded once (np.random.seed(cfg.seed), run.py:81-84) and carried from pair to pair -- the
@@ -38,6 +39,8 @@ def track_chunk(pipe, frames, lo, hi, seed=4869, rng_mode="sequential", ahead=3,
     pipe.set_ref_image(frames[lo])  # halo: depth of the chunk's first reference frame
     if rng_mode == "sequential":
         pipe.seed(seed)
+    if getattr(pipe, "iterative", False):
+        pipe.set_prev_scale(0.0)  # EssTracker.prev_scale of a fresh run
     # carry_features: only the chunk's first pair hands both frames to the flow net; from then on the reference frame's image
     # / feature pyramids are the ones the previous pair computed for it as its current frame (ref = None)
 
@@ -77,6 +80,7 @@ def run_sequence(pipe, frames, n_frames, world=1, rank=0, dist=None, seed=4869, 
         rng_mode = "sequential" if world == 1 else "per_pair"
     if world > 1 and rng_mode == "sequential":
         raise ValueError("the sequential numpy RandomState cannot be reproduced frame-parallel; use rng_mode='per_pair'")
+    _refuse_iterative_multi_rank(pipe, world)
     bounds = [dmod.chunk_bounds(n_frames - 1, world, r) for r in range(world)]
     lo, hi = bounds[rank]
     rel, status = track_chunk(pipe, frames, lo, hi, seed, rng_mode, ahead, collect=collect, carry_features=carry_features)
@@ -104,6 +108,7 @@ def run_sequences(pipe, seqs, world=1, rank=0, dist=None, comm=None, seed=4869, 
         rng_mode = "sequential" if world == 1 else "per_pair"
     if world > 1 and rng_mode == "sequential":
         raise ValueError("the sequential numpy RandomState cannot be reproduced frame-parallel; use rng_mode='per_pair'")
+    _refuse_iterative_multi_rank(pipe, world)
     n_pairs = [max(0, int(n) - 1) for _, _, n in seqs]
     items = dmod.job_items(n_pairs, world)
     rows = []
@@ -130,6 +135,15 @@ def run_sequences(pipe, seqs, world=1, rank=0, dist=None, comm=None, seed=4869, 
             ev.save_traj(os.path.join(out_dir, "%s.txt" % name), poses)
         out[name] = {"poses": poses, "gathered": g, "metrics": metrics}
     return out
+
+
+def _refuse_iterative_multi_rank(pipe, world):
+    """scale_recovery.method iterative starts every pair from prev_scale, the scale of the pair before it (SURVEY.md section 8:
+    a sequential coupling like the RandomState's, with no per-pair substitute): a chunk that starts mid-sequence would not equal
+    the single-rank run"""
+    if world > 1 and getattr(pipe, "iterative", False):
+        raise NotImplementedError("scale_recovery.method iterative carries prev_scale from pair to pair: a sequence cannot be "
+                                  "split over %d ranks" % world)
 
 
 def save_traj(path, poses):

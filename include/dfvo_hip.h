@@ -560,6 +560,42 @@ typedef struct dfvo_pipeline_opts {
 } dfvo_pipeline_opts;
 int dfvo_pipeline_set_options(dfvo_pipeline* p, const dfvo_pipeline_opts* opts);
 int dfvo_pipeline_set_graph(dfvo_pipeline* p, int enable);   /* hipGraph replay of the nets (default on) */
+/* scale_recovery.method "iterative" in the fused pipeline (ablation_scale_iterative.yml, the tracking half of the *_extend.yml
+ * files): EssTracker.scale_recovery_iterative (see dfvo_scale_recovery_iterative) takes the place of find_scale_from_depth in
+ * the chain dfvo_pipeline_track_begin enqueues.  The loop starts and ends on the device: its first kernel reads the E-tracker's
+ * pose (a zero translation ends the call there, dfvo.py:182: status 3 "not run", no RandomState draw, nothing written) and
+ * EssTracker.prev_scale, which the pipeline carries on the device from pair to pair (0 after dfvo_pipeline_create; written
+ * once per completed round, the scale -1 included; a pair that completes no round leaves it as it was).  The flow, the
+ * consistency map and the current frame's processed depth are the ones the pair tracks with; ref_data['raw_depth'] is the
+ * raw depth of the reference frame, which dfvo_pipeline_set_ref_depth (d_feed) / _set_ref_image / _set_ref_raw_depth supply
+ * for the first pair and every pair's roll-over supplies for the next.
+ * kp_src DFVO_ITER_KP_DEPTH: each round's scale comes from that round's uniform rigid-flow keypoints; DFVO_ITER_KP_BEST: from the
+ * pipeline's tracked keypoints, whichever kp_source produced them (at most 16384).  num_row / num_col / num_bestN /
+ * rigid_flow_thre / optical_flow_thre: kp_selection.rigid_flow_kp.  There is no score_method: the loop reads only the uniform
+ * set (E_tracker.py:541-542), which does not depend on the score (kp_selection.py:203-324).
+ * Same state rule as dfvo_pipeline_set_options (call that one first when both are used): before the first
+ * dfvo_pipeline_enqueue_nets / _set_ref_*.  DFVO_ERR_ARG, with a message, for what the rigid-flow keypoint launcher refuses at
+ * the pipeline's img_h x img_w (grid, num_bestN per cell, cell size) and for more than 16384 keypoints in the scale stage.
+ * Allocates every buffer of the loop; enable = 0 switches the method off again.  Nothing changes for a pipeline on which this
+ * is never called: it enqueues exactly what it enqueued before.
+ * dfvo_pipeline_track_end: where the reference raises (the "sampling threshold is too small." assertion, sklearn's "could not
+ * find a valid consensus set") it returns DFVO_ERR_EMPTY_SELECTION / DFVO_ERR_NO_CONSENSUS -- after the pair is over: the slot
+ * is idle, the depths are rolled over, the pipeline stays usable; prev_scale and the RandomState hold what the reference had at
+ * the raise, `out` the E-tracker's pose (status DFVO_TRACK_E, scale of the last completed round or 0).  A scale of -1 takes the
+ * PnP fallback as before. */
+typedef struct dfvo_pipeline_iter_opts {
+    int enable;               /* 1: scale_recovery.method iterative */
+    int kp_src;               /* DFVO_ITER_KP_DEPTH | DFVO_ITER_KP_BEST (scale_recovery.kp_src) */
+    int num_row, num_col;     /* kp_selection.rigid_flow_kp.num_row / num_col */
+    int num_bestN;            /* kp_selection.rigid_flow_kp.num_bestN */
+    double rigid_flow_thre;   /* kp_selection.rigid_flow_kp.rigid_flow_thre */
+    double optical_flow_thre; /* kp_selection.rigid_flow_kp.optical_flow_thre */
+} dfvo_pipeline_iter_opts;
+int dfvo_pipeline_set_iterative(dfvo_pipeline* p, const dfvo_pipeline_iter_opts* opts);
+/* EssTracker.prev_scale as the pipeline carries it (host double in / out; both wait for the chain stream; _set needs no pair
+ * pending) */
+int dfvo_pipeline_get_prev_scale(dfvo_pipeline* p, double* h_scale);
+int dfvo_pipeline_set_prev_scale(dfvo_pipeline* p, double scale);
 /* number of output slots: the host may run the nets this many pairs ahead of the solver stage (the nets of pairs
  * k+1 .. k+3 queue up behind each other on their streams while dfvo_pipeline_track(k) blocks the host) */
 #define DFVO_PIPELINE_SLOTS 4
@@ -584,6 +620,13 @@ int dfvo_pipeline_enqueue_nets(dfvo_pipeline* p, int slot, const uint8_t* d_ref,
 int dfvo_pipeline_set_ref_depth(dfvo_pipeline* p, const uint8_t* d_feed, const double* d_depth_override);
 /* same from the full-size first frame [img_h,img_w,3]: device LANCZOS resize, then the depth net */
 int dfvo_pipeline_set_ref_image(dfvo_pipeline* p, const uint8_t* d_img);
+/* The raw-depth counterparts of the processed-depth overrides, for callers that bring their own depth (iterative scale
+ * recovery only; float [H,W] on the device).  _set_ref_raw_depth: ref_data['raw_depth'] of the first pair (copied; counts as
+ * an enqueue for the state rule of dfvo_pipeline_set_options).  _set_raw_depth_override: the raw depth of `slot`'s current
+ * frame, which rolls over to the reference side in dfvo_pipeline_track_end in place of the depth net's; valid until that call
+ * (NULL withdraws it), the array stays allocated as d_depth_override of dfvo_pipeline_track_begin does. */
+int dfvo_pipeline_set_ref_raw_depth(dfvo_pipeline* p, const float* d_raw);
+int dfvo_pipeline_set_raw_depth_override(dfvo_pipeline* p, int slot, const float* d_raw);
 /* Optional: enqueue the RNG-independent half of the solver stage of `slot` (keypoint selection, homography RANSAC +
  * refinement, GRIC-H) right after dfvo_pipeline_enqueue_nets(slot, ...).  It waits for the slot's flow outputs on the
  * device and runs on its own stream, i.e. under the nets / solver stage of earlier pairs; dfvo_pipeline_track(slot)
@@ -610,11 +653,22 @@ int dfvo_pipeline_track_begin(dfvo_pipeline* p, int slot, const float* d_flow_ov
 int dfvo_pipeline_track_end(dfvo_pipeline* p, int slot, dfvo_track_out* out);
 int dfvo_pipeline_get_flow(dfvo_pipeline* p, int slot, float* h_fwd, float* h_bwd, float* h_diff, float* h_raw_depth,
                            double* h_depth);
+/* inspection: the reference frame's depths as the next pair will read them -- raw (float [H,W]; written by
+ * dfvo_pipeline_set_ref_depth (d_feed) / _set_ref_image / _set_ref_raw_depth, and by the roll-over while the iterative scale
+ * recovery is on) and processed (double [H,W]); either may be NULL.  Waits for the device. */
+int dfvo_pipeline_get_ref_depth(dfvo_pipeline* p, float* h_raw_depth, double* h_depth);
 /* inspection (tests, debugging): keypoints selected for `slot` (kp_best of ref / cur, double [n][2], x,y), the E-tracker's
  * best inlier mask (uint8 [n]; ref_data['inliers'], dfvo.py:179) -- up to `cap` entries, *n_out = the full count -- and the
  * numpy RandomState the pipeline carries from pair to pair (uint32 key[624] + pos, np.random.get_state() layout) */
 int dfvo_pipeline_get_keypoints(dfvo_pipeline* p, int slot, int cap, double* h_kp_ref, double* h_kp_cur,
                                 uint8_t* h_inliers, int* n_out);
+/* the iterative scale loop's record of the pair last collected from `slot` (dfvo_pipeline_set_iterative; until the slot's next
+ * dfvo_pipeline_track_begin): `out` as dfvo_scale_recovery_iterative documents it, with one more status value, 3 "not run", for
+ * a pair whose E-tracker pose had no translation or that never reached the scale stage (n_iter 0, kp_round -1, n_kp 0;
+ * device_ms is not measured here: 0).  h_kp_ref / h_kp_cur (optional, [cap,2]): the uniform keypoints of the last round that
+ * selected any, the first min(out->n_kp, cap) rows; h_rigid_flow_diff (optional, float [H,W]): that round's distance map. */
+int dfvo_pipeline_get_iterative(dfvo_pipeline* p, int slot, dfvo_scale_iter_out* out, int cap, double* h_kp_ref, double* h_kp_cur,
+                                float* h_rigid_flow_diff);
 int dfvo_pipeline_get_rng_state(dfvo_pipeline* p, uint32_t* h_state625);
 int dfvo_pipeline_set_rng_state(dfvo_pipeline* p, const uint32_t* h_state625);
 int dfvo_pipeline_sync(dfvo_pipeline* p);
