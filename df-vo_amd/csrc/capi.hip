@@ -486,6 +486,7 @@ int dfvo_depthnet_sync(dfvo_depthnet* n) {
 int dfvo_depth_postprocess(const float* d_depth, int h, int w, int H, int W, int y0, int y1, int x0, int x1,
                            float min_depth, float max_depth, float* d_raw, double* d_proc, void* stream) {
     DFVO_ARG_CHECK(d_depth && d_raw && d_proc, "dfvo_depth_postprocess: null argument");
+    DFVO_ARG_CHECK(h >= 1 && w >= 1 && H >= 1 && W >= 1, "dfvo_depth_postprocess: empty map");
     return launch_depth_post(d_depth, h, w, H, W, y0, y1, x0, x1, min_depth, max_depth, d_raw, d_proc,
                              (hipStream_t)stream);
 }

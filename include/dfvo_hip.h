@@ -241,7 +241,12 @@ int dfvo_depthnet_forward_image_host(dfvo_depthnet* net, const uint8_t* h_img, i
 double dfvo_depthnet_last_flops(const dfvo_depthnet* net);
 int dfvo_depthnet_sync(dfvo_depthnet* net);
 /* dfvo.py:314-319 + utils.py:89-114: nearest resize to (H,W), crop rows/cols, range mask.
- * d_depth float [h,w] -> d_raw float [H,W], d_proc double [H,W] */
+ * d_depth float [h,w] -> d_raw float [H,W], d_proc double [H,W].  The resize is cv2.resize's INTER_NEAREST: source column
+ * min(floor(x * (1.0 / ((double)W / w))), w - 1), rows alike.  d_raw holds the resized map bit for bit; d_proc is
+ * (double)d_raw inside rows [y0, y1), columns [x0, x1) where min_depth < d_raw < max_depth (both strict, compared in
+ * float), else 0.0.  One deliberate difference from the reference: a NaN or infinite depth fails the range test and
+ * gives d_proc = 0.0 (d_raw passes its bits through), where utils.py's depth * mask gives NaN -- the solvers read
+ * d_proc and treat 0 as "no depth".  h, w, H, W >= 1, else DFVO_ERR_ARG.  Asynchronous on `stream`. */
 int dfvo_depth_postprocess(const float* d_depth, int h, int w, int H, int W, int y0, int y1, int x0, int x1,
                            float min_depth, float max_depth, float* d_raw, double* d_proc, void* stream);
 

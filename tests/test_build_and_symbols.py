@@ -56,6 +56,20 @@ def test_comm_entry_points_check_their_arguments():
     assert lib.dfvo_tracker_stage_ms(None, capi.as_ptr(ms)) == -2
 
 
+def test_depth_postprocess_refuses_empty_maps(capi):
+    """dfvo_depth_postprocess: a size below 1 is an argument error, reported before anything is launched (no GPU needed; the
+    pointers are never read)"""
+    import numpy as np
+    lib = capi.lib()
+    d, raw, proc = np.ones(4, np.float32), np.ones(4, np.float32), np.ones(4)
+    p = [capi.as_ptr(a) for a in (d, raw, proc)]
+    for h, w, H, W in [(0, 2, 2, 2), (2, 0, 2, 2), (2, 2, 0, 2), (2, 2, 2, 0), (-1, 2, 2, 2), (2, 2, 2, -3), (0, 0, 0, 0)]:
+        rc = lib.dfvo_depth_postprocess(p[0], h, w, H, W, 0, max(H, 0), 0, max(W, 0), 0.0, 50.0, p[1], p[2], None)
+        assert rc == -2 and b"dfvo_depth_postprocess" in lib.dfvo_last_error(), (h, w, H, W, rc)  # DFVO_ERR_ARG
+    assert lib.dfvo_depth_postprocess(None, 2, 2, 2, 2, 0, 2, 0, 2, 0.0, 50.0, p[1], p[2], None) == -2
+    assert (raw == 1).all() and (proc == 1).all()
+
+
 def test_missing_rccl_is_an_error_not_a_crash():
     """include/dfvo_hip.h: RCCL is bound with dlopen at first use and "its absence is an error, there is no fallback" -- an error
     CODE with a message, that is (round-4 advisor: the message was built from a second dlerror() call, which returns NULL)."""

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from oracle import cv2_shim as cv2
+from resample_cases import depth_input
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "opencv343_cases.npz")
 
@@ -75,3 +76,7 @@ def test_oracle_equals_opencv_343_on_the_dumped_cases():
         assert np.array_equal(cv2.resize(img, (ow, oh)), fx["r%d_linear" % ri]), "resize case %d: 8-bit INTER_LINEAR" % ri
         assert np.array_equal(cv2.resize(img[..., 0].astype(np.float32), (ow, oh), interpolation=cv2.INTER_NEAREST),
                               fx["r%d_nearest" % ri]), "resize case %d: INTER_NEAREST" % ri
+        if ("r%d_nearest_distinct" % ri) in fx.files:  # a distinct value per source pixel: every source index shows
+            got = cv2.resize(depth_input(h, w), (ow, oh), interpolation=cv2.INTER_NEAREST)
+            assert np.array_equal(got.view(np.uint32), fx["r%d_nearest_distinct" % ri].view(np.uint32)), \
+                "resize case %d: INTER_NEAREST source indices" % ri

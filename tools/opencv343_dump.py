@@ -69,8 +69,18 @@ def planar_view(n, seed, tilt, noise=0.2, w=1241, h=376):
 PLANAR_CASES = [(400, 41, 0.0), (400, 42, 0.25), (60, 43, 0.1)]
 
 
+# (seed, h, w, oh, ow).  1-5: the frame's direction (down to the configured size).  6-7: the depth map's direction (feed size
+# up to KITTI's frames, dfvo.py:314-317).  8-10: small sizes at which cv::resize's double inverse scale, floor(x * (1.0 /
+# (W / w))), picks other source indices than float32 or exact integer arithmetic would.
 RESIZE_CASES = [(1, 376, 1241, 192, 640), (2, 370, 1226, 192, 640), (3, 96, 128, 48, 64), (4, 60, 80, 130, 210),
-                (5, 480, 640, 256, 320)]
+                (5, 480, 640, 256, 320), (6, 192, 640, 376, 1241), (7, 192, 640, 370, 1226), (8, 14, 12, 18, 34),
+                (9, 28, 30, 36, 85), (10, 21, 18, 27, 51)]
+
+
+def distinct_depth(h, w):
+    """a distinct float32 value in every pixel (identical to tests/resample_cases.py:depth_input): a wrong source index of the
+    nearest resize changes the output, which one uint8 channel's 256 values do not show reliably"""
+    return (1.0 + np.arange(h * w, dtype=np.float64) * 2.0 ** -12).astype(np.float32).reshape(h, w)
 
 
 def main(out_path):
@@ -153,6 +163,7 @@ def main(out_path):
         out["r%d_img" % ri] = img
         out["r%d_linear" % ri] = cv2.resize(img, (ow, oh))
         out["r%d_nearest" % ri] = cv2.resize(img[..., 0].astype(np.float32), (ow, oh), interpolation=cv2.INTER_NEAREST)
+        out["r%d_nearest_distinct" % ri] = cv2.resize(distinct_depth(h, w), (ow, oh), interpolation=cv2.INTER_NEAREST)
     # cv::RNG: not exposed in Python; findEssentialMat's subset stream is exercised through the masks above
     np.savez_compressed(out_path, **out)
     print("wrote", out_path, "with OpenCV", cv2.__version__)
