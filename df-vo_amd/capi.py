@@ -91,6 +91,13 @@ class PipelineIterOpts(C.Structure):
                 ("rigid_flow_thre", C.c_double), ("optical_flow_thre", C.c_double)]
 
 
+DEPTH_NET, DEPTH_EXTERNAL = 0, 1  # dfvo_pipeline_depth_src.source
+
+
+class PipelineDepthSrc(C.Structure):
+    _fields_ = [("source", C.c_int), ("scale", C.c_double), ("src_h", C.c_int), ("src_w", C.c_int)]
+
+
 class TrackOut(C.Structure):
     _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("scale", C.c_double), ("status", C.c_int),
                 ("n_kp", C.c_int), ("good_kp_found", C.c_int), ("best_inlier_cnt", C.c_int), ("num_valid", C.c_int),
@@ -209,6 +216,7 @@ SIGNATURES = {
     "dfvo_depthnet_last_flops": (_d, [_vp]),
     "dfvo_depthnet_sync": (_i, [_vp]),
     "dfvo_depth_postprocess": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
+    "dfvo_read_depth_u16": (_i, [_vp, _i, _i, _d, _i, _i, _i, _i, _i, _i, _d, _d, _vp, _vp, _vp]),
     "dfvo_tracker_create": (_i, [_vp, C.POINTER(_vp)]),
     "dfvo_tracker_destroy": (None, [_vp]),
     "dfvo_find_essential_mat": (_i, [_vp, _vp, _vp, _i, _d, _d, _d, _d, _d, _i, _vp, _vp, _vp]),
@@ -238,6 +246,9 @@ SIGNATURES = {
     "dfvo_pipeline_set_ref_raw_depth": (_i, [_vp, _vp]),
     "dfvo_pipeline_set_raw_depth_override": (_i, [_vp, _i, _vp]),
     "dfvo_pipeline_get_iterative": (_i, [_vp, _i, C.POINTER(ScaleIterOut), _i, _vp, _vp, _vp]),
+    "dfvo_pipeline_set_depth_source": (_i, [_vp, C.POINTER(PipelineDepthSrc)]),
+    "dfvo_pipeline_enqueue_nets_depth": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "dfvo_pipeline_set_ref_depth_u16": (_i, [_vp, _vp]),
     "dfvo_pipeline_enqueue_nets": (_i, [_vp, _i, _vp, _vp, _vp]),
     "dfvo_pipeline_track": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(TrackOut)]),
     "dfvo_pipeline_track_begin": (_i, [_vp, _i, _vp, _vp, _vp]),

@@ -490,5 +490,14 @@ int dfvo_depth_postprocess(const float* d_depth, int h, int w, int H, int W, int
     return launch_depth_post(d_depth, h, w, H, W, y0, y1, x0, x1, min_depth, max_depth, d_raw, d_proc,
                              (hipStream_t)stream);
 }
+int dfvo_read_depth_u16(const uint16_t* d_src_u16, int src_h, int src_w, double scale, int H, int W, int y0, int y1, int x0, int x1,
+                        double min_depth, double max_depth, float* d_raw_f32, double* d_proc_f64, void* stream) {
+    DFVO_ARG_CHECK(d_src_u16 && d_raw_f32 && d_proc_f64, "dfvo_read_depth_u16: null argument");
+    DFVO_ARG_CHECK(src_h >= 1 && src_w >= 1 && H >= 1 && W >= 1, "dfvo_read_depth_u16: empty map");
+    DFVO_ARG_CHECK(scale > 0.0 && scale <= 1.7976931348623157e308, "dfvo_read_depth_u16: scale must be finite and > 0");
+    DFVO_ARG_CHECK(0 <= y0 && y0 <= y1 && y1 <= H && 0 <= x0 && x0 <= x1 && x1 <= W, "dfvo_read_depth_u16: crop outside the image");
+    return launch_read_depth_u16(d_src_u16, src_h, src_w, scale, H, W, y0, y1, x0, x1, min_depth, max_depth, d_raw_f32, d_proc_f64,
+                                 (hipStream_t)stream);
+}
 
 }  // extern "C"

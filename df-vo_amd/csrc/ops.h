@@ -61,5 +61,9 @@ int launch_disp_to_depth(const float* disp, int dcs, int dco, int n, float min_d
 // dfvo.py:314-319: nearest resize (cv2.INTER_NEAREST) to (H,W) -> raw f32 and preprocessed f64 map.
 int launch_depth_post(const float* depth, int h, int w, int H, int W, int y0, int y1, int x0, int x1,
                       float min_depth, float max_depth, float* raw, double* proc, hipStream_t s);
+// read_depth (utils.py:55-73: uint16 / scale_factor, cv2.INTER_NEAREST to (H,W)) + preprocess_depth of an external 16-bit depth
+// image: raw = (float)(u16 / scale), proc = the float64 quotient inside the crop and strictly inside (min_depth, max_depth).
+int launch_read_depth_u16(const uint16_t* src, int h, int w, double scale, int H, int W, int y0, int y1, int x0, int x1,
+                          double min_depth, double max_depth, float* raw, double* proc, hipStream_t s);
 
 }  // namespace dfvo

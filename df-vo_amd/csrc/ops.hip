@@ -1002,4 +1002,70 @@ int launch_depth_post(const float* depth, int h, int w, int H, int W, int y0, in
     return DFVO_OK;
 }
 
+// read_depth (utils.py:55-73) behind the decoder + preprocess_depth, for depth.depth_src gt: 16-bit sensor depth -> the raw /
+// processed pair.  2 B in, 12 B out per pixel.  A lane owns one 16-byte-aligned quad of the flat output, clipped to ONE row
+// (row starts are unaligned when W is no multiple of 4: the quad that straddles two rows is shared by the last lane of one
+// row and the first of the next, each storing its own pixels one by one); a whole quad goes out as one 16-byte store of raw
+// and two of proc.  The source is gathered pixel by pixel with 2-byte loads: a nearest resize reads it at arbitrary columns,
+// and its rows start at any 2-byte offset.
+struct alignas(16) RdF4 {
+    float v[4];
+};
+struct alignas(16) RdD2 {
+    double v[2];
+};
+
+__global__ void __launch_bounds__(256) k_read_depth_u16(const uint16_t* __restrict__ src, int h, int w, double scale, int H, int W,
+                                                        int G, double ify, double ifx, int y0, int y1, int x0, int x1,
+                                                        double min_depth, double max_depth, int wide, float* __restrict__ raw,
+                                                        double* __restrict__ proc) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long long)H * G) return;
+    const int y = (int)(t / G), g = (int)(t - (long long)y * G);
+    const long long r0 = (long long)y * W;          // flat index of the row's first pixel
+    const long long q0 = ((r0 >> 2) + g) << 2;      // the lane's quad
+    const long long lo = q0 > r0 ? q0 : r0, hi = q0 + 4 < r0 + W ? q0 + 4 : r0 + W;
+    if (lo >= hi) return;
+    // cv::resize INTER_NEAREST: sx = min(cvFloor(x * ifx), w - 1)
+    int sy = (int)floor(y * ify);
+    sy = sy < h - 1 ? sy : h - 1;
+    const uint16_t* row = src + (size_t)sy * w;
+    const bool row_in = y >= y0 && y < y1;
+    float r[4];
+    double p[4];
+    const int n = (int)(hi - lo), xa = (int)(lo - r0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int x = xa + i < W ? xa + i : W - 1;  // (lanes of a clipped quad: the surplus slots are not stored)
+        int sx = (int)floor(x * ifx);
+        sx = sx < w - 1 ? sx : w - 1;
+        const double v = (double)row[sx] / scale;  // IEEE float64 division, as numpy's
+        r[i] = (float)v;
+        p[i] = (row_in && x >= x0 && x < x1 && v < max_depth && v > min_depth) ? v : 0.0;
+    }
+    if (n == 4 && wide) {
+        *reinterpret_cast<RdF4*>(raw + lo) = RdF4{{r[0], r[1], r[2], r[3]}};
+        *reinterpret_cast<RdD2*>(proc + lo) = RdD2{{p[0], p[1]}};
+        *reinterpret_cast<RdD2*>(proc + lo + 2) = RdD2{{p[2], p[3]}};
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (i < n) {
+                raw[lo + i] = r[i];
+                proc[lo + i] = p[i];
+            }
+    }
+}
+
+int launch_read_depth_u16(const uint16_t* src, int h, int w, double scale, int H, int W, int y0, int y1, int x0, int x1,
+                          double min_depth, double max_depth, float* raw, double* proc, hipStream_t s) {
+    const double ify = 1.0 / ((double)H / (double)h), ifx = 1.0 / ((double)W / (double)w);
+    const int G = (W + 3) / 4 + 1;  // quads a row can touch
+    const int wide = (((uintptr_t)raw | (uintptr_t)proc) & 15) == 0;  // (hipMalloc'ed maps are; a view at an odd offset is not)
+    hipLaunchKernelGGL(k_read_depth_u16, dim3(grid1d((long long)H * G, 256)), dim3(256), 0, s, src, h, w, scale, H, W, G, ify, ifx, y0,
+                       y1, x0, x1, min_depth, max_depth, wide, raw, proc);
+    DFVO_HIP_CHECK(hipGetLastError());
+    return DFVO_OK;
+}
+
 }  // namespace dfvo

@@ -5,7 +5,9 @@
 // becomes device kernels; the pose composition stays on the host (dfvo.py:109-119).
 // dfvo_pipeline_set_options selects the keypoint source (local_bestN | bestN | sampled), the validity and scale-RANSAC methods
 // and hybrid | PnP-only tracking; dfvo_pipeline_set_iterative puts scale_recovery.method "iterative" (the one-call device loop
-// of solver_scale.hip) in the place of find_scale_from_depth; without them the pipeline runs default_configuration.yml.
+// of solver_scale.hip) in the place of find_scale_from_depth; dfvo_pipeline_set_depth_source puts a 16-bit depth image per
+// frame (depth.depth_src gt, dfvo.py:296-319) in the place of the depth net; without them the pipeline runs
+// default_configuration.yml.
 #include "../../include/dfvo_hip.h"
 #include <algorithm>
 #include <chrono>
@@ -103,6 +105,8 @@ struct dfvo_pipeline {
     dfvo_pipeline_cfg cfg;
     // dfvo_pipeline_set_options: the tracking configuration beyond default_configuration.yml (all zero = that configuration)
     dfvo_pipeline_opts opts = {};
+    // dfvo_pipeline_set_depth_source: all zero = the depth net; EXTERNAL = 16-bit depth images (depth.depth_src gt), no depth net
+    dfvo_pipeline_depth_src dsrc = {};
     bool started = false;                   // a pair or a reference depth was enqueued: the options are final
     DevArr<int> d_samples;                  // kp_source sampled: generate_kp_samples' index list, uploaded once
     int sample_crop[4] = {0, 0, 0, 0};      // y0 y1 x0 x1 [px] of cfg.crop.flow_crop
@@ -330,7 +334,7 @@ int dfvo_pipeline_finalize(dfvo_pipeline* p) {
     DFVO_ARG_CHECK(p, "null pipeline");
     P_TRY(p->flow.finalize());
     for (int i = 0; i + 1 < p->flow_instances; ++i) P_TRY(p->flow_x[i].finalize());
-    P_TRY(p->depth.finalize());
+    if (p->dsrc.source != DFVO_DEPTH_EXTERNAL) P_TRY(p->depth.finalize());  // (external depth: no parameters, no graph)
     p->nets_ready = true;
     return DFVO_OK;
 }
@@ -406,6 +410,22 @@ int dfvo_pipeline_set_options(dfvo_pipeline* p, const dfvo_pipeline_opts* o) {
     return DFVO_OK;
 }
 
+int dfvo_pipeline_set_depth_source(dfvo_pipeline* p, const dfvo_pipeline_depth_src* d) {
+    DFVO_ARG_CHECK(p && d, "dfvo_pipeline_set_depth_source: null argument");
+    DFVO_ARG_CHECK(!p->started && !p->nets_ready,
+                   "dfvo_pipeline_set_depth_source: comes before dfvo_pipeline_finalize and the first dfvo_pipeline_enqueue_nets / _set_ref_*");
+    DFVO_ARG_CHECK(d->source == DFVO_DEPTH_NET || d->source == DFVO_DEPTH_EXTERNAL,
+                   "dfvo_pipeline_set_depth_source: source is DFVO_DEPTH_NET or DFVO_DEPTH_EXTERNAL");
+    if (d->source == DFVO_DEPTH_NET) {
+        p->dsrc = {};
+        return DFVO_OK;
+    }
+    DFVO_ARG_CHECK(d->scale > 0.0 && d->scale <= 1.7976931348623157e308, "dfvo_pipeline_set_depth_source: scale must be finite and > 0");
+    DFVO_ARG_CHECK(d->src_h >= 1 && d->src_w >= 1, "dfvo_pipeline_set_depth_source: src_h, src_w >= 1");
+    p->dsrc = *d;
+    return DFVO_OK;
+}
+
 static int pipeline_kp_max(const dfvo_pipeline* p) {
     const dfvo_pipeline_cfg& c = p->cfg;
     return tracked_kp_max(p->opts.kp_source, p->opts.kp_sampled_num, c.kp_num_bestN, c.kp_num_row, c.kp_num_col);
@@ -475,15 +495,28 @@ static int enqueue_depth_post(dfvo_pipeline* p, float* raw, double* proc) {
                              raw, proc, p->s_depth);
 }
 
+// the same pair from a 16-bit depth image (read_depth + preprocess_depth, dfvo_read_depth_u16), under the same ordering
+static int enqueue_read_depth(dfvo_pipeline* p, const uint16_t* d_u16, float* raw, double* proc) {
+    const dfvo_pipeline_cfg& c = p->cfg;
+    const int y0 = (int)(p->H * c.depth_crop[0]), y1 = (int)(p->H * c.depth_crop[1]);
+    const int x0 = (int)(p->W * c.depth_crop[2]), x1 = (int)(p->W * c.depth_crop[3]);
+    if (p->roll_pending) DFVO_HIP_CHECK(hipStreamWaitEvent(p->s_depth, p->e_roll, 0));
+    return dfvo_read_depth_u16(d_u16, p->dsrc.src_h, p->dsrc.src_w, p->dsrc.scale, p->H, p->W, y0, y1, x0, x1, c.min_depth, c.max_depth, raw,
+                               proc, p->s_depth);
+}
+
+static int enqueue_flow_half(dfvo_pipeline* p, int slot, const uint8_t* d_ref, const uint8_t* d_cur);
+
 int dfvo_pipeline_enqueue_nets(dfvo_pipeline* p, int slot, const uint8_t* d_ref, const uint8_t* d_cur,
                                const uint8_t* d_cur_feed) {
     DFVO_ARG_CHECK(p && p->nets_ready && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS) && d_cur,
                    "dfvo_pipeline_enqueue_nets: bad argument");
+    DFVO_ARG_CHECK(p->dsrc.source == DFVO_DEPTH_NET, "dfvo_pipeline_enqueue_nets: the depth source is DFVO_DEPTH_EXTERNAL (no depth net): "
+                                                     "dfvo_pipeline_enqueue_nets_depth takes the pair's depth image");
     DFVO_ARG_CHECK(d_ref || p->last_flow, "dfvo_pipeline_enqueue_nets: d_ref == NULL (reference frame = the previous call's "
                                           "current frame) needs a previous call");
     p->started = true;
     Slot& sl = p->slots[slot];
-    const size_t px = (size_t)p->H * p->W;
     // depth of the current frame (dfvo.py:305-319); without a caller-resized frame the LANCZOS resize of
     // deep_models.py:195-199 runs here, ahead of the net on its stream
     if (!d_cur_feed) {
@@ -493,6 +526,27 @@ int dfvo_pipeline_enqueue_nets(dfvo_pipeline* p, int slot, const uint8_t* d_ref,
     P_TRY(p->depth.forward(d_cur_feed, p->depth_small));
     P_TRY(enqueue_depth_post(p, sl.raw_depth, sl.proc_depth));
     DFVO_HIP_CHECK(hipEventRecord(sl.e_depth, p->s_depth));
+    return enqueue_flow_half(p, slot, d_ref, d_cur);
+}
+
+int dfvo_pipeline_enqueue_nets_depth(dfvo_pipeline* p, int slot, const uint8_t* d_ref, const uint8_t* d_cur, const uint16_t* d_depth_u16) {
+    DFVO_ARG_CHECK(p && p->nets_ready && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS) && d_cur && d_depth_u16,
+                   "dfvo_pipeline_enqueue_nets_depth: bad argument");
+    DFVO_ARG_CHECK(p->dsrc.source == DFVO_DEPTH_EXTERNAL, "dfvo_pipeline_enqueue_nets_depth: the depth source is DFVO_DEPTH_NET "
+                                                          "(dfvo_pipeline_set_depth_source): dfvo_pipeline_enqueue_nets runs the depth net");
+    DFVO_ARG_CHECK(d_ref || p->last_flow, "dfvo_pipeline_enqueue_nets_depth: d_ref == NULL (reference frame = the previous call's "
+                                          "current frame) needs a previous call");
+    p->started = true;
+    Slot& sl = p->slots[slot];
+    // depth of the current frame: the sensor's image where dfvo.py:305-319 runs the depth net
+    P_TRY(enqueue_read_depth(p, d_depth_u16, sl.raw_depth, sl.proc_depth));
+    DFVO_HIP_CHECK(hipEventRecord(sl.e_depth, p->s_depth));
+    return enqueue_flow_half(p, slot, d_ref, d_cur);
+}
+
+static int enqueue_flow_half(dfvo_pipeline* p, int slot, const uint8_t* d_ref, const uint8_t* d_cur) {
+    Slot& sl = p->slots[slot];
+    const size_t px = (size_t)p->H * p->W;
     // forward/backward flow (dfvo.py:321-335)
     const int inst = slot % p->flow_instances;
     FlowNet& fn = inst == 0 ? p->flow : p->flow_x[inst - 1];
@@ -517,6 +571,8 @@ int dfvo_pipeline_enqueue_nets(dfvo_pipeline* p, int slot, const uint8_t* d_ref,
 int dfvo_pipeline_set_ref_depth(dfvo_pipeline* p, const uint8_t* d_feed, const double* d_depth_override) {
     DFVO_ARG_CHECK(p && p->nets_ready && ((d_feed != nullptr) != (d_depth_override != nullptr)),
                    "dfvo_pipeline_set_ref_depth: exactly one of d_feed / d_depth_override");
+    DFVO_ARG_CHECK(!d_feed || p->dsrc.source == DFVO_DEPTH_NET, "dfvo_pipeline_set_ref_depth: d_feed with the depth source DFVO_DEPTH_EXTERNAL "
+                                                                "(no depth net): dfvo_pipeline_set_ref_depth_u16 or d_depth_override");
     p->started = true;
     const size_t px = (size_t)p->H * p->W;
     if (d_depth_override) {
@@ -536,8 +592,23 @@ int dfvo_pipeline_set_ref_depth(dfvo_pipeline* p, const uint8_t* d_feed, const d
 
 int dfvo_pipeline_set_ref_image(dfvo_pipeline* p, const uint8_t* d_img) {
     DFVO_ARG_CHECK(p && p->nets_ready && d_img, "dfvo_pipeline_set_ref_image: bad argument");
+    DFVO_ARG_CHECK(p->dsrc.source == DFVO_DEPTH_NET, "dfvo_pipeline_set_ref_image: the depth source is DFVO_DEPTH_EXTERNAL (no depth net): "
+                                                     "dfvo_pipeline_set_ref_depth_u16 takes the first frame's depth image");
     P_TRY(p->feed_resize.enqueue(d_img, p->feed_buf, p->s_depth));
     return dfvo_pipeline_set_ref_depth(p, p->feed_buf, nullptr);
+}
+
+int dfvo_pipeline_set_ref_depth_u16(dfvo_pipeline* p, const uint16_t* d_depth_u16) {
+    DFVO_ARG_CHECK(p && p->nets_ready && d_depth_u16, "dfvo_pipeline_set_ref_depth_u16: bad argument");
+    DFVO_ARG_CHECK(p->dsrc.source == DFVO_DEPTH_EXTERNAL, "dfvo_pipeline_set_ref_depth_u16: the depth source is DFVO_DEPTH_NET "
+                                                          "(dfvo_pipeline_set_depth_source): dfvo_pipeline_set_ref_image / _set_ref_depth");
+    p->started = true;
+    P_TRY(enqueue_read_depth(p, d_depth_u16, p->ref_raw, p->ref_depth));
+    // (ordered as the depth net's reference depth is: the solver stream behind it on the device, no host wait)
+    DFVO_HIP_CHECK(hipEventRecord(p->e_ref, p->s_depth));
+    DFVO_HIP_CHECK(hipStreamWaitEvent(p->s_trk, p->e_ref, 0));
+    p->has_ref_depth = true;
+    return DFVO_OK;
 }
 
 int dfvo_pipeline_set_ref_raw_depth(dfvo_pipeline* p, const float* d_raw) {
@@ -991,6 +1062,9 @@ int dfvo_pipeline_stream_layout(dfvo_pipeline* p, char* buf, int n) {
     return DFVO_OK;
 }
 
-double dfvo_pipeline_net_flops(const dfvo_pipeline* p) { return p ? p->flow.flops_last + p->depth.flops_last : 0.0; }
+double dfvo_pipeline_net_flops(const dfvo_pipeline* p) {
+    if (!p) return 0.0;
+    return p->dsrc.source == DFVO_DEPTH_EXTERNAL ? p->flow.flops_last : p->flow.flops_last + p->depth.flops_last;
+}
 
 }  // extern "C"

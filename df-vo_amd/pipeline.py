@@ -2,8 +2,8 @@
 double-buffered net/solver software pipeline, and pose accumulation as in
 the reference's libs/dfvo.py:109-119 (update_global_pose) and :121-262 (tracking: the hybrid path of
 default_configuration.yml, and through the option keys below the keypoint sources, validity / scale methods, the
-PnP-only tracking and the iterative scale recovery of the shipped ablation files; options_from_cfg maps the reference's
-configuration object to them)."""
+PnP-only tracking and the iterative scale recovery of the shipped ablation files, and depth.depth_src gt: 16-bit depth images in
+the place of the depth net; options_from_cfg maps the reference's configuration object to them)."""
 import ctypes as C
 
 import numpy as np
@@ -36,6 +36,13 @@ ITER_DEFAULTS = dict(scale_recovery="simple", iter_kp_src="kp_best", rigid_num_b
 _SCALE_RECOVERY = {"simple": 0, "iterative": 1}
 _ITER_KP_SRC = {"kp_depth": 0, "kp_best": 1}
 ITER_STATUS = {0: "finished", 1: "empty_selection", 2: "no_consensus", 3: "not_run"}
+
+# dfvo_pipeline_set_depth_source: depth.depth_src.  "external" (depth_src: gt) tracks on a 16-bit depth image per frame in the
+# place of the depth net; depth_scale is the loader's scale_factor of read_depth (500 kitti.py, 5000 tum.py / kinect.py: not in
+# the reference's YAML), depth_size the (height, width) of those images, None = the image size.  A third table, apart from the
+# other two
+DEPTH_DEFAULTS = dict(depth_source="net", depth_scale=None, depth_size=None)
+_DEPTH_SOURCE = {"net": capi.DEPTH_NET, "external": capi.DEPTH_EXTERNAL}
 
 
 def _choice(o, key, table):
@@ -87,6 +94,31 @@ def check_iter_options(o):
     if f["num_bestN"] < f["num_row"] * f["num_col"]:
         raise ValueError("rigid_num_bestN = %r: fewer than one keypoint per cell of the %d x %d grid (rigid_num_row, rigid_num_col)"
                          % (o["rigid_num_bestN"], f["num_row"], f["num_col"]))
+    return f
+
+
+def check_depth_options(o, img_h=None, img_w=None):
+    """the depth-source keys of `o` (DEPTH_DEFAULTS filled in) as the fields of capi.PipelineDepthSrc; ValueError on a bad value"""
+    f = dict(source=_choice(o, "depth_source", _DEPTH_SOURCE), scale=0.0, src_h=0, src_w=0)
+    size = o["depth_size"]
+    if size is not None:
+        try:
+            sh, sw = size
+        except (TypeError, ValueError):
+            raise ValueError("depth_size = %r: (height, width) of the depth images, or None for the image size" % (size,))
+        for v in (sh, sw):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or v < 1:
+                raise ValueError("depth_size = %r: two positive integers" % (size,))
+        f["src_h"], f["src_w"] = int(sh), int(sw)
+    elif img_h is not None:
+        f["src_h"], f["src_w"] = int(img_h), int(img_w)
+    if o["depth_source"] == "external":
+        v = o["depth_scale"]
+        if v is None or isinstance(v, (bool, str)) or not isinstance(v, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(float(v)) or v <= 0:
+            raise ValueError("depth_scale = %r: depth_source 'external' needs the depth images' scale factor, finite and > 0 "
+                             "(read_depth: 500 for KITTI, 5000 for TUM)" % (v,))
+        f["scale"] = float(v)
     return f
 
 
@@ -171,9 +203,16 @@ def options_from_cfg(cfg):
         full.update(scale_recovery="iterative", iter_kp_src=iter_kp_src, rigid_num_bestN=get(rk + "num_bestN", 2000),
                     rigid_num_row=get(rk + "num_row", 10), rigid_num_col=get(rk + "num_col", 10),
                     rigid_flow_thre=get(rk + "rigid_flow_thre", 5), optical_flow_thre=get(rk + "optical_flow_thre", 0.1))
+    depth_src = get("depth.depth_src")
+    if depth_src == "gt":  # dfvo.py:296-319: read_depth's image in the place of the depth net (depth_scale: the loader's, an override)
+        full["depth_source"] = "external"
+    elif depth_src is not None:
+        raise NotImplementedError("depth.depth_src: %s: not run by the fused pipeline (None: the depth net, gt: 16-bit depth images)"
+                                  % (depth_src,))
     base = dict(DEFAULTS)
     base.update(OPTION_DEFAULTS)
     base.update(ITER_DEFAULTS)
+    base.update(DEPTH_DEFAULTS)
     out = {k: v for k, v in full.items() if base.get(k) != v}
     check = dict(OPTION_DEFAULTS)
     check.update({k: v for k, v in out.items() if k in OPTION_DEFAULTS})
@@ -190,13 +229,22 @@ class TrackingPipeline:
         o.update(OPTION_DEFAULTS)
         io = dict(ITER_DEFAULTS)
         io.update({k: overrides.pop(k) for k in list(overrides) if k in ITER_DEFAULTS})
+        do = dict(DEPTH_DEFAULTS)
+        do.update({k: overrides.pop(k) for k in list(overrides) if k in DEPTH_DEFAULTS})
         o.update(overrides)
         fields = check_options(o)  # (before anything touches the device: a bad value is a ValueError)
         iter_fields = check_iter_options(io)
+        depth_fields = check_depth_options(do, img_h, img_w)
+        self.external_depth = do["depth_source"] == "external"
+        if depth_sd is None and not self.external_depth:
+            raise ValueError("depth_sd = None: depth_source 'net' runs the depth net and needs its weights (depth_source "
+                             "'external' tracks on 16-bit depth images and takes none)")
         capi.require_gpu()
         self.lib = capi.lib()
         self.opts = o
         self.iter_opts = io
+        self.depth_opts = do
+        self.depth_size = (depth_fields["src_h"], depth_fields["src_w"])
         self.iterative = io["scale_recovery"] == "iterative"
         self.H, self.W, self.feed_h, self.feed_w = img_h, img_w, feed_h, feed_w
         K = np.asarray(K, np.float64)
@@ -221,6 +269,12 @@ class TrackingPipeline:
         h = C.c_void_p()
         capi.check(self.lib.dfvo_pipeline_create(C.byref(cfg), C.byref(h)))
         self.h = h
+        if self.external_depth:  # (a pipeline of the depth net makes no call here: it enqueues what it always did)
+            try:
+                capi.check(self.lib.dfvo_pipeline_set_depth_source(h, C.byref(capi.PipelineDepthSrc(**depth_fields))))
+            except capi.DfvoError:
+                self.close()
+                raise
         if any(o[k] != v for k, v in OPTION_DEFAULTS.items()):
             crop = fields.pop("flow_crop")
             po = capi.PipelineOpts(**fields)
@@ -246,15 +300,16 @@ class TrackingPipeline:
             params["aux.linspace_x.%d" % l] = torch.linspace(-1.0, 1.0, nw >> (l - 1)).numpy()
             params["aux.linspace_y.%d" % l] = torch.linspace(-1.0, 1.0, nh >> (l - 1)).numpy()
         capi.set_params(self.lib.dfvo_pipeline_set_flow_param, h, params)
-        dparams = {k: v.detach().cpu().float().numpy() for k, v in depth_sd.items()
-                   if hasattr(v, "detach") and v.dim() > 0 and "num_batches_tracked" not in k}
-        capi.set_params(self.lib.dfvo_pipeline_set_depth_param, h, dparams)
+        if not self.external_depth:
+            dparams = {k: v.detach().cpu().float().numpy() for k, v in depth_sd.items()
+                       if hasattr(v, "detach") and v.dim() > 0 and "num_batches_tracked" not in k}
+            capi.set_params(self.lib.dfvo_pipeline_set_depth_param, h, dparams)
         capi.check(self.lib.dfvo_pipeline_finalize(h))
 
     @classmethod
     def from_cfg(cls, cfg, K, flow_sd, depth_sd, feed_h, feed_w, **overrides):
         """a pipeline for the reference's configuration object `cfg` (image size from cfg.image); `overrides` win"""
-        o = options_from_cfg(cfg)
+        o = options_from_cfg(cfg)  # (depth.depth_src gt: depth_scale, the loader's scale factor, comes with `overrides`)
         o.update(overrides)
         return cls(int(cfg["image"]["height"]), int(cfg["image"]["width"]), feed_h, feed_w, K, flow_sd, depth_sd, **o)
 
@@ -274,12 +329,31 @@ class TrackingPipeline:
     def set_graph(self, enable):
         capi.check(self.lib.dfvo_pipeline_set_graph(self.h, int(enable)))
 
-    def enqueue_nets(self, slot, d_ref, d_cur, d_feed=None):
+    def _depth_image(self, depth, what):
+        """host-side check of a 16-bit depth image (contiguous device uint16 [src_h, src_w]); its device pointer.  Which mode
+        takes one is the library's decision (DFVO_ERR_ARG naming the call and the mode)"""
+        ok = isinstance(depth, torch.Tensor) and depth.dtype == torch.uint16 and tuple(depth.shape) == self.depth_size \
+            and depth.is_cuda and depth.is_contiguous()
+        if not ok:
+            got = "%s %s on %s" % (depth.dtype, list(depth.shape), depth.device) if isinstance(depth, torch.Tensor) else repr(type(depth))
+            raise capi.DfvoError("%s: the depth image is a contiguous device uint16 tensor %s, got %s" % (what, list(self.depth_size), got))
+        return C.c_void_p(depth.data_ptr())
+
+    def enqueue_nets(self, slot, d_ref, d_cur, d_feed=None, depth=None):
         """device uint8 tensors (torch.cuda): ref/cur [H,W,3]; feed [feed_h,feed_w,3] = the LANCZOS-resized current
         frame, or None to have the pipeline resize d_cur on the device.
         d_ref=None: the reference frame is the current frame of the previous enqueue_nets call -- the flow net carries that
-        frame's image / feature pyramids over instead of running Features on it again (sequences)."""
+        frame's image / feature pyramids over instead of running Features on it again (sequences).
+        depth (depth_source "external": required there, refused otherwise): the current frame's 16-bit depth image, a device
+        uint16 tensor [src_h, src_w] (depth_size), under the frames' contract: complete when handed over, unchanged until
+        the slot's track / track_end has returned.  d_feed has no reader then and is refused."""
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        if depth is not None:
+            dp = self._depth_image(depth, "enqueue_nets")
+            if d_feed is not None:
+                raise capi.DfvoError("enqueue_nets: d_feed beside a depth image: the depth net it would feed does not run")
+            capi.check(self.lib.dfvo_pipeline_enqueue_nets_depth(self.h, slot, p(d_ref), p(d_cur), dp))
+            return
         capi.check(self.lib.dfvo_pipeline_enqueue_nets(self.h, slot, p(d_ref), p(d_cur), p(d_feed)))
 
     def prefetch_track(self, slot, flow=None, diff=None):
@@ -347,6 +421,11 @@ class TrackingPipeline:
         return dict(status=ITER_STATUS[out.status], scale=out.scale, n_iter=out.n_iter, kp_round=out.kp_round,
                     scale_in=list(out.scale_in), scale_out=list(out.scale_out), n_kp_round=list(out.n_kp_round),
                     ref_kp=kr[:out.n_kp], cur_kp=kc[:out.n_kp], rigid_flow_diff=m if out.kp_round >= 0 else None)
+
+    def set_ref_depth_image(self, d_depth_u16):
+        """depth of the first reference frame from its 16-bit depth image (depth_source "external"; device uint16
+        [src_h, src_w]): raw and processed reference depth in one launch, nothing else to set for the iterative scale loop"""
+        capi.check(self.lib.dfvo_pipeline_set_ref_depth_u16(self.h, self._depth_image(d_depth_u16, "set_ref_depth_image")))
 
     def set_ref_image(self, d_img):
         """depth of the first reference frame from the full-size uint8 frame (device LANCZOS resize + depth net)"""

@@ -25,8 +25,10 @@ SLOTS = 4  # DFVO_PIPELINE_SLOTS
 
 
 def track_chunk(pipe, frames, lo, hi, seed=4869, rng_mode="sequential", ahead=3, first_chunk=None, collect=None,
-                carry_features=True):
+                carry_features=True, depths=None):
     """track pairs lo .. hi-1 of `frames` (sequence of device uint8 tensors [H,W,3], indexable by frame number).
+    depths (a pipeline of depth_source "external", depth.depth_src gt): the frames' 16-bit depth images, device uint16 tensors
+    indexable like `frames` (depth_to_device); the halo's depth is depths[lo], pair j tracks on depths[j + 1].
     Returns (rel [n,4,4] cur->ref motions, status [n]); status-1 rows (constant motion) hold the identity and are resolved
     by dist.compose_trajectory once the previous pair's motion is known."""
     assert rng_mode in ("sequential", "per_pair")
@@ -36,7 +38,10 @@ def track_chunk(pipe, frames, lo, hi, seed=4869, rng_mode="sequential", ahead=3,
     if n <= 0:
         return rel, status
     ahead = max(1, min(ahead, SLOTS - 1))
-    pipe.set_ref_image(frames[lo])  # halo: depth of the chunk's first reference frame
+    if depths is None:
+        pipe.set_ref_image(frames[lo])  # halo: depth of the chunk's first reference frame
+    else:
+        pipe.set_ref_depth_image(depths[lo])
     if rng_mode == "sequential":
         pipe.seed(seed)
     if getattr(pipe, "iterative", False):
@@ -45,7 +50,11 @@ def track_chunk(pipe, frames, lo, hi, seed=4869, rng_mode="sequential", ahead=3,
     # / feature pyramids are the ones the previous pair computed for it as its current frame (ref = None)
 
     def feed(j):
-        pipe.enqueue_nets(j % SLOTS, None if (carry_features and j > lo) else frames[j], frames[j + 1])
+        d_ref = None if (carry_features and j > lo) else frames[j]
+        if depths is None:
+            pipe.enqueue_nets(j % SLOTS, d_ref, frames[j + 1])
+        else:
+            pipe.enqueue_nets(j % SLOTS, d_ref, frames[j + 1], depth=depths[j + 1])
         pipe.prefetch_track(j % SLOTS)
 
     for j in range(lo, min(lo + ahead, hi)):
@@ -69,12 +78,14 @@ def track_chunk(pipe, frames, lo, hi, seed=4869, rng_mode="sequential", ahead=3,
 
 
 def run_sequence(pipe, frames, n_frames, world=1, rank=0, dist=None, seed=4869, rng_mode=None, ahead=3, collect=None,
-                 compose="host", carry_features=True, comm=None):
+                 compose="host", carry_features=True, comm=None, depths=None):
     """data-parallel tracking of an n_frames sequence: contiguous chunk per rank (dist.chunk_bounds), ONE all-gather of
     the relative poses + status words (RCCL when `dist` runs the nccl backend), then the sequential prefix composition
     that reproduces DFVO.update_global_pose incl. the constant-motion rule (dfvo.py:109-119,157-161).
     compose: "host" = the numpy recurrence of dist.compose_trajectory (the reference's own operations), "device" = the same
     recurrence in one launch (dist.compose_trajectory_device; agrees to rounding).
+    depths: the frames' 16-bit depth images for a pipeline of depth_source "external" (track_chunk); every rank reads its own
+    chunk's, the halo's included.
     Returns (global poses [n_frames,4,4] camera-to-world, gathered [n_frames-1,17])."""
     if rng_mode is None:
         rng_mode = "sequential" if world == 1 else "per_pair"
@@ -83,7 +94,8 @@ def run_sequence(pipe, frames, n_frames, world=1, rank=0, dist=None, seed=4869, 
     _refuse_iterative_multi_rank(pipe, world)
     bounds = [dmod.chunk_bounds(n_frames - 1, world, r) for r in range(world)]
     lo, hi = bounds[rank]
-    rel, status = track_chunk(pipe, frames, lo, hi, seed, rng_mode, ahead, collect=collect, carry_features=carry_features)
+    rel, status = track_chunk(pipe, frames, lo, hi, seed, rng_mode, ahead, collect=collect, carry_features=carry_features,
+                              depths=depths)
     gathered = dmod.allgather_poses(rel, status, world, rank, dist, counts=[b - a for a, b in bounds], comm=comm)
     traj = dmod.compose_trajectory_device(gathered) if compose == "device" else dmod.compose_trajectory(gathered)
     return traj, gathered
@@ -95,7 +107,8 @@ def run_sequences(pipe, seqs, world=1, rank=0, dist=None, comm=None, seed=4869, 
     runs of apis/run.py, one `--seq` each (DFVO.main, /root/reference/libs/dfvo.py:347-425; trajectory written by
     save_traj, libs/general/utils.py:329-355; evaluated by tools/evaluation/odometry/eval_odom.py).
 
-    seqs: list of (name, frames, n_frames) -- `frames` indexable by frame number -> device uint8 [H,W,3].
+    seqs: list of (name, frames, n_frames) or (name, frames, n_frames, depths) -- `frames` indexable by frame number -> device
+    uint8 [H,W,3]; `depths` (depth_source "external") alike -> device uint16 [src_h,src_w].
     The pairs of all sequences form one work list balanced over the ranks by frame count (dist.job_items); every item
     starts from its own 1-frame halo; ONE all-gather for the whole job (row counts are deterministic, nothing else is
     exchanged); then every sequence is composed separately from the identity (a fresh DFVO per sequence), written to
@@ -109,20 +122,22 @@ def run_sequences(pipe, seqs, world=1, rank=0, dist=None, comm=None, seed=4869, 
     if world > 1 and rng_mode == "sequential":
         raise ValueError("the sequential numpy RandomState cannot be reproduced frame-parallel; use rng_mode='per_pair'")
     _refuse_iterative_multi_rank(pipe, world)
-    n_pairs = [max(0, int(n) - 1) for _, _, n in seqs]
+    n_pairs = [max(0, int(q[2]) - 1) for q in seqs]
     items = dmod.job_items(n_pairs, world)
     rows = []
     for s, lo, hi in items[rank]:
-        name, frames, _ = seqs[s]
+        name, frames = seqs[s][:2]
+        depths = seqs[s][3] if len(seqs[s]) > 3 else None
         rel, status = track_chunk(pipe, frames, lo, hi, seed, rng_mode, ahead, carry_features=carry_features,
-                                  collect=None if collect is None else (lambda j, out, _n=name: collect(_n, j, out)))
+                                  collect=None if collect is None else (lambda j, out, _n=name: collect(_n, j, out)),
+                                  depths=depths)
         rows.append(dmod.pack_rows(rel, status))
     mine = np.concatenate(rows, 0) if rows else np.zeros((0, 17))
     counts = [sum(hi - lo for _, lo, hi in it) for it in items]
     gathered = dmod.allgather_rows(mine, counts, world, rank, dist, comm)
     out = {}
     off = 0
-    for (name, _, n), npair in zip(seqs, n_pairs):
+    for (name, *_), npair in zip(seqs, n_pairs):
         g = gathered[off:off + npair]
         off += npair
         poses = dmod.compose_trajectory_device(g) if compose == "device" else dmod.compose_trajectory(g)
@@ -179,4 +194,16 @@ def image_to_device(img_u8, h, w, crop=None, bgr=False):
     # before it is handed over.  The upload + resize are therefore drained here (frames_to_device's .cuda() copy is
     # synchronous for pageable host memory already).
     stream.synchronize()
+    return dst
+
+
+def depth_to_device(depth_u16):
+    """the decoded 16-bit depth image of depth.depth_src gt (cv2.imread(path, -1), utils.py:62) as the device uint16 tensor
+    [src_h, src_w] that TrackingPipeline.enqueue_nets(depth=) / set_ref_depth_image take: an upload, drained as image_to_device
+    drains its own (the same ordering contract).  The PNG decode stays on the host; read_depth's division and resize and
+    preprocess_depth run in the pipeline (dfvo_read_depth_u16)."""
+    d = np.ascontiguousarray(depth_u16)
+    assert d.ndim == 2 and d.dtype == np.uint16
+    dst = torch.from_numpy(d).cuda()
+    torch.cuda.current_stream().synchronize()
     return dst

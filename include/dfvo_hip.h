@@ -249,6 +249,17 @@ int dfvo_depthnet_sync(dfvo_depthnet* net);
  * d_proc and treat 0 as "no depth".  h, w, H, W >= 1, else DFVO_ERR_ARG.  Asynchronous on `stream`. */
 int dfvo_depth_postprocess(const float* d_depth, int h, int w, int H, int W, int y0, int y1, int x0, int x1,
                            float min_depth, float max_depth, float* d_raw, double* d_proc, void* stream);
+/* depth.depth_src gt: read_depth behind the decoder (utils.py:55-73: cv2.imread(path, -1) / scale_factor, cv2.resize
+ * INTER_NEAREST to the image size; scale_factor 500 in kitti.py, 5000 in tum.py / kinect.py) and preprocess_depth
+ * (utils.py:89-114) in one launch.  d_src_u16 uint16 [src_h,src_w] (the decoded depth image; rows need no alignment beyond
+ * 2 bytes) -> d_raw_f32 float [H,W], d_proc_f64 double [H,W].  Source pixel: the INTER_NEAREST index of
+ * dfvo_depth_postprocess.  v = (double)u16 / scale, an IEEE float64 division; d_raw_f32 = (float)v; d_proc_f64 = v inside rows
+ * [y0, y1), columns [x0, x1) where min_depth < v < max_depth (both strict, compared in float64, as the reference compares a
+ * float64 array), else 0.0 -- a sensor hole (u16 == 0) gives 0.  DFVO_ERR_ARG, before anything is launched, for a null pointer,
+ * a size below 1, a scale that is not finite or not > 0, or a crop that is not 0 <= y0 <= y1 <= H, 0 <= x0 <= x1 <= W.
+ * Asynchronous on `stream`. */
+int dfvo_read_depth_u16(const uint16_t* d_src_u16, int src_h, int src_w, double scale, int H, int W, int y0, int y1, int x0,
+                        int x1, double min_depth, double max_depth, float* d_raw_f32, double* d_proc_f64, void* stream);
 
 /* =====================================================================================
  * Pose solvers (wavefront-parallel RANSAC, f64).  Host arrays in / out, synchronous: these are the
@@ -601,6 +612,25 @@ int dfvo_pipeline_set_iterative(dfvo_pipeline* p, const dfvo_pipeline_iter_opts*
  * pending) */
 int dfvo_pipeline_get_prev_scale(dfvo_pipeline* p, double* h_scale);
 int dfvo_pipeline_set_prev_scale(dfvo_pipeline* p, double scale);
+/* depth.depth_src (dfvo.py:296-319): where the depth of a frame comes from.  DFVO_DEPTH_NET (all zero, the default: a pipeline
+ * on which this is never called enqueues exactly what it enqueued before): monodepth2.  DFVO_DEPTH_EXTERNAL (depth_src gt): a
+ * 16-bit depth image per frame, uint16 [src_h,src_w] on the device as the decoder left it, through dfvo_read_depth_u16 with
+ * `scale` (the loader's scale_factor: 500 kitti.py, 5000 tum.py / kinect.py), the crop and the depth range of
+ * dfvo_pipeline_cfg; the pipeline then has no depth net: dfvo_pipeline_finalize needs no depth parameters and neither builds
+ * nor captures it, dfvo_pipeline_net_flops counts the flow net only.  Everything behind the slot's raw / processed depth (scale
+ * recovery, the iterative loop and its raw roll-over, the PnP fallback, tracking_method PNP, every depth override) is the same
+ * in both modes.  State rule: after dfvo_pipeline_create, before dfvo_pipeline_finalize and the first
+ * dfvo_pipeline_enqueue_nets / _set_ref_*.  In EXTERNAL mode dfvo_pipeline_enqueue_nets, dfvo_pipeline_set_ref_image and
+ * dfvo_pipeline_set_ref_depth with d_feed return DFVO_ERR_ARG; in NET mode dfvo_pipeline_enqueue_nets_depth and
+ * dfvo_pipeline_set_ref_depth_u16 do. */
+#define DFVO_DEPTH_NET 0
+#define DFVO_DEPTH_EXTERNAL 1
+typedef struct dfvo_pipeline_depth_src {
+    int source;       /* DFVO_DEPTH_NET | DFVO_DEPTH_EXTERNAL */
+    double scale;     /* EXTERNAL: depth [m] = u16 / scale; finite, > 0 */
+    int src_h, src_w; /* EXTERNAL: size of the depth images, >= 1 (any size: resized INTER_NEAREST to img_h x img_w) */
+} dfvo_pipeline_depth_src;
+int dfvo_pipeline_set_depth_source(dfvo_pipeline* p, const dfvo_pipeline_depth_src* src);
 /* number of output slots: the host may run the nets this many pairs ahead of the solver stage (the nets of pairs
  * k+1 .. k+3 queue up behind each other on their streams while dfvo_pipeline_track(k) blocks the host) */
 #define DFVO_PIPELINE_SLOTS 4
@@ -608,7 +638,11 @@ int dfvo_pipeline_set_prev_scale(dfvo_pipeline* p, double scale);
  * the pipeline's own non-blocking HIP streams.  (1) The frame must be complete when the call is made -- work still queued
  * on another stream (e.g. a resize on the caller's stream) is not waited for.  (2) The frame must stay unchanged, and
  * allocated, until dfvo_pipeline_track() of that slot has returned (enqueue_nets) / until dfvo_pipeline_sync() or the
- * first dfvo_pipeline_track() after the call has returned (set_ref_depth, set_ref_image). */
+ * first dfvo_pipeline_track() after the call has returned (set_ref_depth, set_ref_image).
+ * The 16-bit depth image of dfvo_pipeline_enqueue_nets_depth / dfvo_pipeline_set_ref_depth_u16 stands under the same contract
+ * as the frame it belongs to: complete when handed over (its upload drained), unchanged and allocated until the slot's
+ * dfvo_pipeline_track() / dfvo_pipeline_track_end() has returned (enqueue_nets_depth) / until dfvo_pipeline_sync() or the first
+ * dfvo_pipeline_track() after the call has returned (set_ref_depth_u16). */
 /* enqueue both nets for one pair into `slot` (0 .. DFVO_PIPELINE_SLOTS-1); returns at once.  d_* uint8 device images:
  * ref/cur [img_h,img_w,3], cur_feed [feed_h,feed_w,3] (the PIL-LANCZOS resized current frame) or NULL: the current frame
  * is then resized on the device (dfvo_resize_lanczos_u8's arithmetic) ahead of the depth net.
@@ -625,6 +659,15 @@ int dfvo_pipeline_enqueue_nets(dfvo_pipeline* p, int slot, const uint8_t* d_ref,
 int dfvo_pipeline_set_ref_depth(dfvo_pipeline* p, const uint8_t* d_feed, const double* d_depth_override);
 /* same from the full-size first frame [img_h,img_w,3]: device LANCZOS resize, then the depth net */
 int dfvo_pipeline_set_ref_image(dfvo_pipeline* p, const uint8_t* d_img);
+/* DFVO_DEPTH_EXTERNAL (dfvo_pipeline_set_depth_source).  _enqueue_nets_depth is dfvo_pipeline_enqueue_nets with the current
+ * frame's depth image, uint16 [src_h,src_w], in the place of the depth net: one dfvo_read_depth_u16 launch on the depth stream
+ * writes the slot's raw and processed depth, ordered behind a pending roll-over of the reference depth as the depth net's
+ * output stage is; the flow half (d_ref, d_cur, the d_ref == NULL carry-over) is the same.  _set_ref_depth_u16 is the depth
+ * image of the very first reference frame: it writes the reference side's raw and processed depth (so the iterative scale
+ * loop needs no dfvo_pipeline_set_ref_raw_depth) and orders the chain's stream behind it on the device. */
+int dfvo_pipeline_enqueue_nets_depth(dfvo_pipeline* p, int slot, const uint8_t* d_ref, const uint8_t* d_cur,
+                                     const uint16_t* d_depth_u16);
+int dfvo_pipeline_set_ref_depth_u16(dfvo_pipeline* p, const uint16_t* d_depth_u16);
 /* The raw-depth counterparts of the processed-depth overrides, for callers that bring their own depth (iterative scale
  * recovery only; float [H,W] on the device).  _set_ref_raw_depth: ref_data['raw_depth'] of the first pair (copied; counts as
  * an enqueue for the state rule of dfvo_pipeline_set_options).  _set_raw_depth_override: the raw depth of `slot`'s current
