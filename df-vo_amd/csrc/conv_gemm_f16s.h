@@ -369,7 +369,8 @@ static int launch_f16g_cfg(const ConvParams& p, hipStream_t stream, int cfg_id) 
         ConvProfScope prof(p, stream, cfg_id);
         hipLaunchKernelGGL(kernel, grid, dim3(64 * WP * KSP), lds, stream, p);
         DFVO_HIP_CHECK(hipGetLastError());
-        return prof.done((int)grid.x, TC, KSP * 100 + 1);
+        static const std::string variant = conv_variant_name("f16g", {WP, KSP, TC}, RAG ? "rag" : nullptr);
+        return prof.done((int)grid.x, TC, KSP * 100 + 1, variant.c_str(), decltype(np)::value);
     });
 }
 

@@ -248,7 +248,8 @@ static int launch_f32g_cfg(const ConvParams& p, hipStream_t stream) {
     ConvProfScope prof(p, stream, KSP == 1 ? 22 : 23);  // profile rows: 22 streaming (KSP = 1), 23 K-sliced small maps
     hipLaunchKernelGGL((conv_gemm_f32g_kernel<WP, KSP, TC>), grid, dim3(64 * WP * KSP), lds, stream, p);
     DFVO_HIP_CHECK(hipGetLastError());
-    return prof.done((int)grid.x, 0, KSP * 100 + 1);
+    static const std::string variant = conv_variant_name("f32g", {WP, KSP, TC});
+    return prof.done((int)grid.x, 0, KSP * 100 + 1, variant.c_str());
 }
 
 // Shape choice: the rules of launch_f16g (conv_gemm_f16s.h) -- two cout blocks per wave while that leaves enough tiles, K

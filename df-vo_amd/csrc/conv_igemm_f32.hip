@@ -794,6 +794,8 @@ struct ConvProfEntry {
     //   generic kernels (cfg 20-23): gx = the grid, gy = cout blocks per wave TC, gz = 100 KSP + 1 (K slices per workgroup);
     //     the tap-window kernel: gy = 0, gz = 7; the fp32 twin conv_gemm_f32g: gy = 0
     int shape[12];
+    // the instantiation that ran: "igemm<2,2,4,4>", "f16g<4,1,2,rag> np3", "win3<2,2,4,2,3> tickets" (ConvProfScope::done)
+    char variant[48];
 };
 static std::vector<ConvProfEntry>* g_prof = nullptr;
 
@@ -806,7 +808,7 @@ ConvProfScope::~ConvProfScope() {
     if (e0_) (void)hipEventDestroy(e0_);
     if (e1_) (void)hipEventDestroy(e1_);
 }
-int ConvProfScope::done(int gx, int gy, int gz) {
+int ConvProfScope::done(int gx, int gy, int gz, const char* variant, int f16_terms, int splitk) {
     if (err_ != hipSuccess) {  // of the constructor: reported here, where the launcher can return it
         set_last_error(std::string("conv profile events: ") + hipGetErrorString(err_));
         return DFVO_ERR_HIP;
@@ -814,7 +816,10 @@ int ConvProfScope::done(int gx, int gy, int gz) {
     if (!e1_ || !g_prof) return DFVO_OK;  // no profile is running
     DFVO_HIP_CHECK(hipEventRecord(e1_, stream_));
     g_prof->push_back({e0_, e1_, cfg_, p_.useful_flops,
-                       {p_.N, p_.H, p_.W, p_.Ho, p_.Wo, (p_.G0 + p_.G1) * 4, p_.cout, p_.kh, p_.stride, gx, gy, gz}});
+                       {p_.N, p_.H, p_.W, p_.Ho, p_.Wo, (p_.G0 + p_.G1) * 4, p_.cout, p_.kh, p_.stride, gx, gy, gz}, {0}});
+    snprintf(g_prof->back().variant, sizeof(g_prof->back().variant), "%s%s%s", variant,
+             f16_terms == 3 ? " np3" : (f16_terms == 1 ? " np1" : ""),
+             splitk == CONV_SPLITK_TICKETS ? " tickets" : (splitk == CONV_SPLITK_EPILOGUE ? " epilogue" : ""));
     e0_ = e1_ = nullptr;  // conv_profile_end() destroys them
     return DFVO_OK;
 }
@@ -838,19 +843,24 @@ int conv_profile_end(double* ms, double* flops, int* launches, double* bytes) {
         if (bytes) bytes[i] = 0;
     }
     if (!g_prof) return DFVO_OK;
-    // DFVO_CONV_PROFILE_CSV=<path>: one line per launch (tuning aid)
+    // DFVO_CONV_PROFILE_CSV=<path>: one line per launch (tuning aid; tests/test_conv_variants_gpu.py reads the last column).
+    // variant, the last column, names the instantiation that ran from the launcher's own template arguments and contains
+    // commas itself: igemm<WM,WN,TM,TN>, win3<WM,WN,TM,TN,KS>, head<KS,CO,py1|py2>, f16s<WC,WR,TC,TR>, f16s2<WC,WR,TC,TR>,
+    // f16s2mix<WC,WR,TC,TRA,TRB>, f16g<WP,KSP,TC[,rag]>, taps<TH,TC>, f32g<WP,KSP,TC>, wino<WN>; then " np3" / " np1" for the
+    // kernels that come in f16x3 and f16 form, then " tickets" / " epilogue" for a launch whose K slices over grid.z were
+    // finished inside the kernel / by conv_splitk_epilogue
     const char* csv_path = getenv("DFVO_CONV_PROFILE_CSV");
     FILE* csv = csv_path ? fopen(csv_path, "a") : nullptr;
-    if (csv) fprintf(csv, "cfg,N,H,W,Ho,Wo,cin,cout,k,stride,gx,gy,gz,us,tflops\n");
+    if (csv) fprintf(csv, "cfg,N,H,W,Ho,Wo,cin,cout,k,stride,gx,gy,gz,us,tflops,variant\n");
     for (auto& e : *g_prof) {
         float t = 0.f;
         DFVO_HIP_CHECK(hipEventSynchronize(e.e1));
         DFVO_HIP_CHECK(hipEventElapsedTime(&t, e.e0, e.e1));
         ms[e.cfg] += t;
         if (csv)
-            fprintf(csv, "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%.4f,%.4f\n", e.cfg, e.shape[0], e.shape[1], e.shape[2],
+            fprintf(csv, "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%.4f,%.4f,%s\n", e.cfg, e.shape[0], e.shape[1], e.shape[2],
                     e.shape[3], e.shape[4], e.shape[5], e.shape[6], e.shape[7], e.shape[8], e.shape[9], e.shape[10],
-                    e.shape[11], t * 1e3, e.flops / (t * 1e-3) / 1e12);
+                    e.shape[11], t * 1e3, e.flops / (t * 1e-3) / 1e12, e.variant);
         flops[e.cfg] += e.flops;
         launches[e.cfg] += 1;
         if (bytes) {
@@ -886,10 +896,12 @@ static int conv_splitk_slices(const ConvParams& p, long long blocks, int units, 
 
 // grid.z K slices of a contracting kernel: finished inside the kernel when the tiles have tickets (splitk_last_arriver),
 // else by the ordered reduction of conv_splitk_epilogue in a second launch
-static int launch_splitk(void (*kernel)(const ConvParams), dim3 grid, const ConvParams& p, hipStream_t stream) {
+// *finish: which of the two it was (CONV_SPLITK_*), for the profile
+static int launch_splitk(void (*kernel)(const ConvParams), dim3 grid, const ConvParams& p, hipStream_t stream, int* finish) {
     ConvParams pk = p;
     const bool fused = grid.z > 1 && pk.tile_flags && (long long)grid.x * grid.y <= pk.tile_flags_n;
     if (!fused) pk.tile_flags = nullptr;
+    *finish = grid.z > 1 ? (fused ? CONV_SPLITK_TICKETS : CONV_SPLITK_EPILOGUE) : CONV_SPLITK_NONE;
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, pk);
     DFVO_HIP_CHECK(hipGetLastError());
     if (grid.z > 1 && !fused) {
@@ -908,9 +920,11 @@ static int launch_cfg(const ConvParams& p, hipStream_t stream, int cfg_id) {
     dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)(p.cout_pad / BN), 1);
     DFVO_ARG_CHECK((p.G0 + p.G1) * p.kh * p.kw + 4 <= MAX_KGROUPS, "launch_conv: too many k-groups for the LDS table");
     grid.z = (unsigned)conv_splitk_slices(p, (long long)grid.x * grid.y, p.ksteps, 8, 32);
+    static const std::string variant = conv_variant_name("igemm", {WM, WN, TM, TN});
+    int finish = CONV_SPLITK_NONE;
     ConvProfScope prof(p, stream, cfg_id);
-    if (int rc = launch_splitk(conv_igemm_f32_kernel<WM, WN, TM, TN>, grid, p, stream)) return rc;
-    return prof.done((int)grid.x, (int)grid.y, (int)grid.z);
+    if (int rc = launch_splitk(conv_igemm_f32_kernel<WM, WN, TM, TN>, grid, p, stream, &finish)) return rc;
+    return prof.done((int)grid.x, (int)grid.y, (int)grid.z, variant.c_str(), 0, finish);
 }
 
 template <int WM, int WN, int TM, int TN, int KS = 3>
@@ -921,9 +935,11 @@ static int launch_win3(const ConvParams& p, hipStream_t stream, int cfg_id) {
     // split the channel chunks when the tile grid cannot fill the chip
     const int nchunks = ((p.G0 + 3) >> 2) + ((p.G1 + 3) >> 2);
     grid.z = (unsigned)conv_splitk_slices(p, (long long)grid.x * grid.y, nchunks, 2, nchunks);
+    static const std::string variant = conv_variant_name("win3", {WM, WN, TM, TN, KS});
+    int finish = CONV_SPLITK_NONE;
     ConvProfScope prof(p, stream, cfg_id);
-    if (int rc = launch_splitk(conv_win_f32_kernel<WM, WN, TM, TN, KS>, grid, p, stream)) return rc;
-    return prof.done((int)grid.x, (int)grid.y, (int)grid.z);
+    if (int rc = launch_splitk(conv_win_f32_kernel<WM, WN, TM, TN, KS>, grid, p, stream, &finish)) return rc;
+    return prof.done((int)grid.x, (int)grid.y, (int)grid.z, variant.c_str(), 0, finish);
 }
 
 template <int KS, int CO>
@@ -939,7 +955,8 @@ static int launch_head(const ConvParams& p, hipStream_t stream, int cfg_id) {
     else
         hipLaunchKernelGGL((conv_head_f32_kernel<KS, CO, 2>), grid, dim3(256), 0, stream, p);
     DFVO_HIP_CHECK(hipGetLastError());
-    return prof.done((int)grid.x, 1, 1);
+    static const std::string variant1 = conv_variant_name("head", {KS, CO}, "py1"), variant2 = conv_variant_name("head", {KS, CO}, "py2");
+    return prof.done((int)grid.x, 1, 1, (py1 ? variant1 : variant2).c_str());
 }
 
 // the direct kernel serves the square, stride-1, "same"-padded heads with one or two output channels

@@ -240,12 +240,15 @@ bool taps_geom(const ConvParams& p, TapsGeom* g) {
     }
     return false;
 }
+// returns the profile's name of the instantiation it launched
 template <int TH, int TC>
-void taps_launch(const ConvParams& p, hipStream_t stream, int tiles, const TapsGeom& g) {
+const char* taps_launch(const ConvParams& p, hipStream_t stream, int tiles, const TapsGeom& g) {
     with_f16_terms(p, [&](auto np) {
         hipLaunchKernelGGL((conv_taps_f16s_kernel<TH, TC, decltype(np)::value>), dim3(tiles), dim3(64 * TH), g.lds, stream, p, g.G,
                            g.pxd, g.wcols, g.wrows);
     });
+    static const std::string variant = conv_variant_name("taps", {TH, TC});
+    return variant.c_str();
 }
 }  // namespace
 
@@ -269,12 +272,13 @@ int launch_taps_f16s(const ConvParams& p, hipStream_t stream) {
     const int tiles = p.N * ((p.Ho + g.th - 1) / g.th) * ((p.Wo + 31) / 32);
     const bool tc2 = p.wf16g_cout_pad == 64;
     ConvProfScope prof(p, stream, 20);
+    const char* variant;
     if (g.th == 4)
-        tc2 ? taps_launch<4, 2>(p, stream, tiles, g) : taps_launch<4, 1>(p, stream, tiles, g);
+        variant = tc2 ? taps_launch<4, 2>(p, stream, tiles, g) : taps_launch<4, 1>(p, stream, tiles, g);
     else
-        tc2 ? taps_launch<2, 2>(p, stream, tiles, g) : taps_launch<2, 1>(p, stream, tiles, g);
+        variant = tc2 ? taps_launch<2, 2>(p, stream, tiles, g) : taps_launch<2, 1>(p, stream, tiles, g);
     DFVO_HIP_CHECK(hipGetLastError());
-    return prof.done(tiles, 0, 7);
+    return prof.done(tiles, 0, 7, variant, p.f16_terms == 1 ? 1 : 3);
 }
 
 }  // namespace dfvo

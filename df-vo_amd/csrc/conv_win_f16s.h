@@ -247,7 +247,8 @@ static int launch_f16s_cfg(const ConvParams& p, hipStream_t stream, int cfg_id) 
         hipLaunchKernelGGL((conv_win_f16s_kernel<WC, WR, TC, TR, decltype(np)::value>), grid, dim3(64 * WC * WR), 0, stream, p);
     });
     DFVO_HIP_CHECK(hipGetLastError());
-    return prof.done((int)grid.x, (int)grid.y, 1);
+    static const std::string variant = conv_variant_name("f16s", {WC, WR, TC, TR});
+    return prof.done((int)grid.x, (int)grid.y, 1, variant.c_str(), p.f16_terms == 1 ? 1 : 3);
 }
 
 // The first skeleton (two waves per SIMD) takes what the one-wave-per-SIMD skeleton of conv_win_f16s2.h leaves: layers with

@@ -326,7 +326,8 @@ static int launch_f16s2_cfg(const ConvParams& p, hipStream_t stream, int cfg_id)
         hipLaunchKernelGGL((conv_win_f16s2_kernel<WC, WR, TC, TR, decltype(np)::value>), grid, dim3(64 * WC * WR), 0, stream, p);
     });
     DFVO_HIP_CHECK(hipGetLastError());
-    return prof.done((int)grid.x, (int)grid.y, 2);
+    static const std::string variant = conv_variant_name("f16s2", {WC, WR, TC, TR});
+    return prof.done((int)grid.x, (int)grid.y, 2, variant.c_str(), p.f16_terms == 1 ? 1 : 3);
 }
 
 template <int WC, int WR, int TC, int TRA, int TRB>
@@ -342,7 +343,8 @@ static int launch_f16s2_mix(const ConvParams& p, hipStream_t stream, int cfg_id,
                            rows_a, na, na_pad, nb);
     });
     DFVO_HIP_CHECK(hipGetLastError());
-    return prof.done((int)grid.x, (int)grid.y, 2);
+    static const std::string variant = conv_variant_name("f16s2mix", {WC, WR, TC, TRA, TRB});
+    return prof.done((int)grid.x, (int)grid.y, 2, variant.c_str(), p.f16_terms == 1 ? 1 : 3);
 }
 
 // Greedy dispatch of `ca` tiles of cost `wa` followed by `cb` tiles of cost `wb` onto 256 CUs (one workgroup per CU): the time

@@ -278,7 +278,8 @@ static int launch_wino_cfg(const ConvParams& p, hipStream_t stream, int cfg_id) 
         std::lock_guard<std::mutex> lock(g_wino_mu);
         ++g_wino_launches;
     }
-    return prof.done((int)grid.x, (int)grid.y, 1);
+    static const std::string variant = conv_variant_name("wino", {WN});
+    return prof.done((int)grid.x, (int)grid.y, 1, variant.c_str());
 }
 // cfg_id: the window row of the class the launch replaces (12-15), with the direct convolution's FLOP count
 static int launch_wino(const ConvParams& p, hipStream_t stream, int cfg_id) {

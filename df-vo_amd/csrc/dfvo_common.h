@@ -4,6 +4,7 @@
 #pragma once
 #include <cstdlib>
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include <stdint.h>
 #include <string>
 #include <type_traits>
@@ -183,6 +184,26 @@ int launch_conv(const ConvParams& p, hipStream_t stream, bool wino_all = false);
 void conv_profile_begin();
 int conv_profile_end(double* ms, double* flops, int* launches, double* bytes = nullptr);
 
+// "family<a,b,c>" from a launcher's own template arguments, `last` (a word such as "rag" or "py2") appended when given: the
+// variant column of the per-launch profile.  A launcher builds it once per instantiation, into a function-local static.
+static inline std::string conv_variant_name(const char* family, std::initializer_list<int> args, const char* last = nullptr) {
+    std::string s(family);
+    s += '<';
+    bool first = true;
+    for (int a : args) {
+        if (!first) s += ',';
+        s += std::to_string(a);
+        first = false;
+    }
+    if (last) {
+        if (!first) s += ',';
+        s += last;
+    }
+    s += '>';
+    return s;
+}
+enum { CONV_SPLITK_NONE = 0, CONV_SPLITK_TICKETS = 1, CONV_SPLITK_EPILOGUE = 2 };
+
 // One profiled launch (conv_igemm_f32.hip).  Between conv_profile_begin() and conv_profile_end() the constructor creates two
 // events and records the first on the stream, done() records the second and files the entry; a scope that is left without
 // done() -- an error return of the launcher -- destroys its events.  Outside a profile both do nothing.
@@ -192,8 +213,11 @@ class ConvProfScope {
     ~ConvProfScope();
     ConvProfScope(const ConvProfScope&) = delete;
     ConvProfScope& operator=(const ConvProfScope&) = delete;
-    // after the launch(es): DFVO_OK, or DFVO_ERR_HIP if an event call failed.  gx gy gz: see ConvProfEntry
-    int done(int gx, int gy, int gz);
+    // after the launch(es): DFVO_OK, or DFVO_ERR_HIP if an event call failed.  gx gy gz: see ConvProfEntry.  variant: the
+    // instantiation that ran, as conv_variant_name() spells the launcher's template arguments (read only while a profile
+    // runs); f16_terms: 3 / 1 for the kernels that come in f16x3 and f16 form, else 0; splitk: how a launch with K slices
+    // over grid.z was finished (CONV_SPLITK_*)
+    int done(int gx, int gy, int gz, const char* variant, int f16_terms = 0, int splitk = 0);
 
   private:
     const ConvParams& p_;
