@@ -1,7 +1,9 @@
-// Epilogue helpers shared by every convolution kernel of the library (conv_igemm_f32.hip, conv_taps_f16s.hip, conv_gemm_f32g.hip):
-// bias + residual + activation + store of accumulator quads.  See conv_igemm_f32.hip for the accumulator layout.
+// Epilogue helpers shared by every convolution kernel of the library, whichever translation unit it lives in: bias +
+// residual + activation + store of accumulator quads.  See conv_igemm_f32.hip for the accumulator layout.
 #pragma once
-// (included inside namespace dfvo)
+#include "conv.h"
+
+namespace dfvo {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -50,7 +52,6 @@ __device__ __forceinline__ void conv_epilogue_quad(const ConvParams& p, size_t m
 __device__ __forceinline__ bool conv_vec_ok(const ConvParams& p) {
     return (((p.dst_cs | p.dst_co) & 3) == 0) && (!p.res || (((p.res_cs | p.res_co) & 3) == 0));
 }
-
 
 // ---- batched epilogue of the f16x3 kernels --------------------------------------------------------------------------
 // conv_epilogue_quad() interleaves, per quad, a bias (and residual) LOAD with the quad's STORE.  Stores count on vmcnt on
@@ -126,4 +127,4 @@ __device__ __forceinline__ void conv_epi_row(const ConvParams& p, const ConvEpi<
         conv_epi_row_act<false, NQ>(p, c, m, get);
 }
 
-
+}  // namespace dfvo

@@ -1,14 +1,14 @@
 // f16 hi / lo plane split of fp32 operands (see conv_win_f16s.h for the arithmetic) -- shared by the f16x3 kernels.
 #pragma once
-// (included inside namespace dfvo)
+#include "conv_epi.h"  // f32x4
+
+namespace dfvo {
 
 typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr float F16S_LO_SCALE = 2048.0f;          // 2^11
-constexpr float F16S_LO_UNSCALE = 1.0f / 2048.0f;
-constexpr float F16S_MAX = 65504.0f;
+// (F16S_LO_SCALE, F16S_LO_UNSCALE, F16S_MAX: conv.h -- the host packers split the weights by the same constants)
 
 __device__ __forceinline__ void split_f16_planes(f32x4 x, h16x4* hi, h16x4* lo, float& amax) {
     // (spelled as instructions: fmaxf() drags a canonicalising v_max per operand along, 7 instructions instead of 2)
@@ -31,3 +31,4 @@ __device__ __forceinline__ void split_f16_hi(f32x4 x, h16x4* hi, float& amax) {
     for (int e = 0; e < 4; ++e) (*hi)[e] = (_Float16)x[e];
 }
 
+}  // namespace dfvo

@@ -18,13 +18,12 @@
 // offset) of the four k-groups of a step come from a table built once per layer on the host and read through the scalar
 // cache (one s_load_dwordx4 per step).
 #pragma once
-// (included inside namespace dfvo, after conv_pack_f16s.h and conv_win_f16s.h)
+#include "conv_epi.h"
+#include "conv_f16_clamp.h"
 
-// k-group table entry: ky [0,5) | kx [5,10) | valid 10 | source 11 | channel offset inside the source << 16
-static inline uint32_t f16g_entry(int ky, int kx, int valid, int src, int choff) {
-    return (uint32_t)ky | ((uint32_t)kx << 5) | ((uint32_t)valid << 10) | ((uint32_t)src << 11) | ((uint32_t)choff << 16);
-}
+namespace dfvo {
 
+// (k-group table entry: f16g_entry, conv.h)
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(4))) const u32x4 cu32x4;
 
@@ -299,60 +298,7 @@ __global__ __launch_bounds__(64 * WP * KSP) void conv_gemm_f16s_kernel(const Con
     }
 }
 
-// ---- host side ----------------------------------------------------------------------------------------------------
-// weights as f16 hi / lo planes in k-group order: [step][cout_pad / 32][plane][k-block (2)][32 couts][8 k], where the 16 k
-// of a step are k-groups 4 step .. 4 step + 3 (g = tap (G0 + G1) + channel group), 4 channels each.  Returns the number
-// of halves (out may be null)
-size_t conv_pack_weights_f16g(const float* w, int cout, int c0, int c1, int kh, int kw, const float* fold_scale,
-                              unsigned short* out) {
-    const int G0 = cdiv(c0, 4), G1 = cdiv(c1, 4), G = G0 + G1, taps = kh * kw;
-    const int steps = cdiv(taps * G, 4);
-    const int cp = round_up(cout, 32);
-    const size_t total = (size_t)steps * cp * 32;
-    if (!out) return total;
-    memset(out, 0, total * sizeof(unsigned short));
-    const int cin = c0 + c1;
-    for (int tap = 0; tap < taps; ++tap)
-        for (int cg = 0; cg < G; ++cg) {
-            const int g = tap * G + cg, step = g >> 2, gl = g & 3;
-            for (int q = 0; q < 4; ++q) {
-                int ci;
-                if (cg < G0) {
-                    ci = cg * 4 + q;
-                    if (ci >= c0) continue;
-                } else {
-                    ci = (cg - G0) * 4 + q;
-                    if (ci >= c1) continue;
-                    ci += c0;
-                }
-                const int k = gl * 4 + q;
-                for (int co = 0; co < cout; ++co) {
-                    float v = w[((size_t)co * cin + ci) * taps + tap];
-                    if (fold_scale) v *= fold_scale[co];
-                    unsigned short* o = out + ((size_t)step * cp + (co & ~31)) * 32 + ((k >> 3) * 32 + (co & 31)) * 8 + (k & 7);
-                    f16s_split_host(v, o, o + 512);
-                }
-            }
-        }
-    return total;
-}
-
-// the k-group table of a layer: 4 entries per step
-void conv_build_f16g_table(int c0, int c1, int kh, int kw, std::vector<uint32_t>* tab) {
-    const int G0 = cdiv(c0, 4), G1 = cdiv(c1, 4), G = G0 + G1, taps = kh * kw;
-    const int steps = cdiv(taps * G, 4);
-    tab->assign((size_t)steps * 4, f16g_entry(0, 0, 0, 0, 0));
-    for (int tap = 0; tap < taps; ++tap)
-        for (int cg = 0; cg < G; ++cg)
-            (*tab)[(size_t)tap * G + cg] = f16g_entry(tap / kw, tap % kw, 1, cg < G0 ? 0 : 1, cg < G0 ? cg * 4 : (cg - G0) * 4);
-}
-
-static bool conv_f16g_ok(const ConvParams& p) {
-    if (!p.wf16g || !p.f16g_tab) return false;
-    if (p.kh > 31 || p.kw > 31) return false;
-    return true;
-}
-
+// ---- host side (the shape choice launch_f16g: conv_f16.hip; the packer and the k-group table: conv_pack.hip) ----------------
 template <int WP, int KSP, int TC, int PF = 3, bool RAG = false>
 static int launch_f16g_cfg(const ConvParams& p, hipStream_t stream, int cfg_id) {
     const long long M = (long long)p.N * p.Ho * p.Wo;
@@ -374,59 +320,4 @@ static int launch_f16g_cfg(const ConvParams& p, hipStream_t stream, int cfg_id) 
     });
 }
 
-// Shape choice.  TC = 2 (a pixel fragment, whose split costs the VALU work, feeds two cout blocks) whenever the layer has
-// an even number of 32-cout blocks.  The K split fills the chip: ~2 waves per SIMD in total, at least 4 steps per wave.
-// Large maps (thousands of pixel blocks) run KSP = 1 with four pixel blocks per workgroup.
-// multi-tap streaming layers: conv_taps_f16s.hip (its own translation unit; bit-identical to the <4, 1, TC> shape here)
-bool conv_taps_f16s_ok(const ConvParams& p);
-int launch_taps_f16s(const ConvParams& p, hipStream_t stream);  // (p.f16s_clamp_ctr set; profile row 20)
-
-static int launch_f16g(const ConvParams& p, hipStream_t stream) {
-    const long long M = (long long)p.N * p.Ho * p.Wo;
-    const long long mblocks = (M + 31) / 32;
-    const int nblk = p.wf16g_cout_pad / 32;
-    const long long target = 2048;  // waves on the chip: ~2 per SIMD
-    // two cout blocks per wave (a pixel fragment, whose split costs the VALU work, feeds both) only while that still leaves
-    // enough (pixel block, cout pair) tiles to fill the chip with at most eight K slices; tiny maps with many couts (the
-    // depth net's 6 x 20 / 12 x 40 layers: the launch is one pass over megabytes of weights) take one block per wave and up
-    // to 16 slices -- more waves, more loads in flight
-    bool tc2 = (nblk % 2) == 0;
-    if (tc2 && mblocks * (nblk / 2) * 8 * 2 < target && p.f16g_steps >= 64) tc2 = false;
-    const long long tiles = mblocks * (tc2 ? nblk / 2 : nblk);
-    int ksp = 1;
-    // (16 slices only with one cout block per wave: a 1024-thread workgroup leaves 128 registers per lane)
-    while (ksp < (tc2 ? 8 : 16) && tiles * ksp * 2 <= target && p.f16g_steps >= 4 * ksp * 2) ksp *= 2;
-    // Measured and dropped (records under profiles/): an eight-stage ring with twice the waves (r3: K-sliced layers 1.24 vs
-    // 1.10 ms per pair), K divided over workgroups as well (r3af_nz_ab.txt: launches 7 % shorter one at a time, pair rate
-    // -1.3 %), one cout block per wave on the streaming shapes (r3j_stream_tc1_ab.txt: no gain).
-    const int cfg = ksp == 1 ? 20 : 21;  // profile rows: 20 streaming (KSP = 1), 21 K-sliced small maps
-    // multi-tap layers among the streaming shapes: the tap-window kernel (only where this kernel would not slice K: the two
-    // then sum in the same order).  DFVO_TAPS=0 (test hook, tests/test_nets_gpu.py): this file's <4, 1, TC> shape instead
-    // -- the form the tap-window kernel is compared with bit for bit
-    static const bool taps_on = env_flag("DFVO_TAPS", true);
-    if (taps_on && ksp == 1 && conv_taps_f16s_ok(p)) {
-        ConvParams pt = p;
-        pt.f16s_clamp_ctr = f16s_clamp_counter();
-        return launch_taps_f16s(pt, stream);
-    }
-    // ragged cout on a streaming shape: the store-only epilogue (profiles/r4j_rag_ab.txt: the 7 x 1 / 1 x 7 distance layers
-    // 80 -> 68 / 104 -> 98 us, +0.8 % pairs/s, bit-identical)
-    const bool rag = ksp == 1 && (p.cout % (tc2 ? 64 : 32)) != 0 && !p.res && ((p.dst_cs | p.dst_co) & 3) == 0 &&
-                     p.cout_pad >= 4 && (p.act == ACT_NONE || p.act == ACT_LEAKY || p.act == ACT_RELU);
-    if (rag) return tc2 ? launch_f16g_cfg<4, 1, 2, 3, true>(p, stream, cfg) : launch_f16g_cfg<4, 1, 1, 3, true>(p, stream, cfg);
-    if (tc2) {
-        switch (ksp) {
-            case 1: return launch_f16g_cfg<4, 1, 2>(p, stream, cfg);
-            case 2: return launch_f16g_cfg<2, 2, 2>(p, stream, cfg);
-            case 4: return launch_f16g_cfg<1, 4, 2>(p, stream, cfg);
-            default: return launch_f16g_cfg<1, 8, 2>(p, stream, cfg);
-        }
-    }
-    switch (ksp) {
-        case 1: return launch_f16g_cfg<4, 1, 1>(p, stream, cfg);
-        case 2: return launch_f16g_cfg<2, 2, 1>(p, stream, cfg);
-        case 4: return launch_f16g_cfg<1, 4, 1>(p, stream, cfg);
-        case 8: return launch_f16g_cfg<1, 8, 1>(p, stream, cfg);
-        default: return launch_f16g_cfg<1, 16, 1>(p, stream, cfg);
-    }
-}
+}  // namespace dfvo

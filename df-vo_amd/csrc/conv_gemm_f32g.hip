@@ -14,14 +14,10 @@
 //     k-values of the step (the k permutation is the same on both sides).
 // Reference layers: /root/reference/libs/deep_models/flow/lite_flow_net/lite_flow_net.py:39-75,98-129,164-240,
 // depth/monodepth2/resnet_encoder.py:87-98, depth_decoder.py:50-65.
-#include "dfvo_common.h"
-
-#include <cstring>
-#include <vector>
+#include "conv.h"
+#include "conv_epi.h"
 
 namespace dfvo {
-
-#include "conv_epi.h"
 
 typedef float f32x16g __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4g __attribute__((ext_vector_type(4)));
@@ -198,42 +194,7 @@ __global__ __launch_bounds__(64 * WP * KSP) void conv_gemm_f32g_kernel(const Con
     }
 }
 
-// ---- host side ----------------------------------------------------------------------------------------------------
-// fp32 weights in k-group order: [step][cout_pad / 32][k-block (2)][32 couts][8 k]; the 16 k of a step are k-groups
-// 4 step .. 4 step + 3 (g = tap (G0 + G1) + channel group, 4 channels each): the order of conv_build_f16g_table, which this
-// kernel shares with the f16x3 one.  Returns the number of floats (out may be null)
-size_t conv_pack_weights_f32g(const float* w, int cout, int c0, int c1, int kh, int kw, const float* fold_scale, float* out) {
-    const int G0 = cdiv(c0, 4), G1 = cdiv(c1, 4), G = G0 + G1, taps = kh * kw;
-    const int steps = cdiv(taps * G, 4);
-    const int cp = round_up(cout, 32);
-    const size_t total = (size_t)steps * cp * 16;
-    if (!out) return total;
-    memset(out, 0, total * sizeof(float));
-    const int cin = c0 + c1;
-    for (int tap = 0; tap < taps; ++tap)
-        for (int cg = 0; cg < G; ++cg) {
-            const int g = tap * G + cg, step = g >> 2, gl = g & 3;
-            for (int q = 0; q < 4; ++q) {
-                int ci;
-                if (cg < G0) {
-                    ci = cg * 4 + q;
-                    if (ci >= c0) continue;
-                } else {
-                    ci = (cg - G0) * 4 + q;
-                    if (ci >= c1) continue;
-                    ci += c0;
-                }
-                const int k = gl * 4 + q;
-                for (int co = 0; co < cout; ++co) {
-                    float v = w[((size_t)co * cin + ci) * taps + tap];
-                    if (fold_scale) v *= fold_scale[co];
-                    out[((size_t)step * cp + (co & ~31)) * 16 + ((k >> 3) * 32 + (co & 31)) * 8 + (k & 7)] = v;
-                }
-            }
-        }
-    return total;
-}
-
+// ---- host side (the packer conv_pack_weights_f32g: conv_pack.hip) --------------------------------------------------------
 bool conv_f32g_ok(const ConvParams& p) {
     return p.wf32g && p.f16g_tab && p.kh <= 31 && p.kw <= 31;
 }
@@ -252,18 +213,9 @@ static int launch_f32g_cfg(const ConvParams& p, hipStream_t stream) {
     return prof.done((int)grid.x, 0, KSP * 100 + 1, variant.c_str());
 }
 
-// Shape choice: the rules of launch_f16g (conv_gemm_f16s.h) -- two cout blocks per wave while that leaves enough tiles, K
-// sliced over the waves of a workgroup until the chip holds ~2 waves per SIMD
+// Shape choice: ring_shape (conv_dispatch.hip), shared with the f16 ring kernel
 int launch_f32g(const ConvParams& p, hipStream_t stream) {
-    const long long M = (long long)p.N * p.Ho * p.Wo;
-    const long long mblocks = (M + 31) / 32;
-    const int nblk = p.wf16g_cout_pad / 32;
-    const long long target = 2048;
-    bool tc2 = (nblk % 2) == 0;
-    if (tc2 && mblocks * (nblk / 2) * 8 * 2 < target && p.f16g_steps >= 64) tc2 = false;
-    const long long tiles = mblocks * (tc2 ? nblk / 2 : nblk);
-    int ksp = 1;
-    while (ksp < (tc2 ? 8 : 16) && tiles * ksp * 2 <= target && p.f16g_steps >= 4 * ksp * 2) ksp *= 2;
+    const auto [tc2, ksp] = ring_shape((long long)p.N * p.Ho * p.Wo, p.wf16g_cout_pad / 32, p.f16g_steps);
     if (tc2) {
         switch (ksp) {
             case 1: return launch_f32g_cfg<4, 1, 2>(p, stream);

@@ -1,15 +1,7 @@
-// The convolution translation unit: the exact-fp32 kernels of this file, the f16 kernel families it includes, and the
-// dispatcher launch_conv() over all of them.  In order:
-//   1. fp32 device code: split-K hand-off, conv_igemm_f32_kernel (implicit GEMM, described below), conv_win_f32_kernel
-//      (LDS window, k x k / stride 1), conv_splitk_epilogue, conv_head_f32_kernel (direct one- / two-channel heads)
-//   2. the fp32 packers conv_pick_bn, conv_pack_weights, conv_pack_head_weights (between the kernels they serve)
-//   3. the per-launch profile: ConvProfEntry, ConvProfScope (declared in dfvo_common.h: the kernels of conv_gemm_f32g.hip
-//      and conv_taps_f16s.hip, translation units of their own, are profiled through it too), conv_profile_begin / _end
-//   4. the f16 families, included: conv_pack_f16s.h (host packers; pulls in conv_f16_clamp.h, the saturation counter, and
-//      conv_f16_split.h, the plane split), conv_win_f16s.h, conv_gemm_f16s.h, conv_win_f16s2.h -- kernels and launchers each;
-//      conv_wino_f32.h: the opt-in fp32 Winograd F(2x2,3x3) kernel, its switch and launcher (conv_pack_wino_f32.h: its packer)
-//   5. the fp32 launchers (conv_splitk_slices, launch_splitk, launch_cfg, launch_win3, launch_head), the tile rules, and
-//      launch_conv()
+// The exact-fp32 convolution kernels (conv.h lists the other units of the family): the split-K hand-off,
+// conv_igemm_f32_kernel (implicit GEMM, described below), conv_win_f32_kernel (LDS window, k x k / stride 1),
+// conv_splitk_epilogue, conv_head_f32_kernel (direct one- / two-channel heads); then their launchers and the three entry
+// points the dispatcher calls: launch_igemm_f32, launch_win_f32, launch_head_f32.
 //
 // conv_igemm_f32_kernel: implicit-GEMM convolution on the gfx950 matrix cores, exact fp32 numerics.
 // Replaces the torch.nn.Conv2d (+bias, +LeakyReLU/ReLU/ELU/sigmoid, +residual, +BatchNorm(eval),
@@ -30,22 +22,13 @@
 // and B (16 k x couts) tiles are staged global -> registers -> LDS with the next step's loads in
 // flight under the current step's MFMAs.  The LDS A image is XOR-swizzled on the k-group so the four
 // 16-lane service groups of ds_read_b128 each hit 16 distinct 16-byte slots.
-#include "dfvo_common.h"
+#include "conv.h"
 
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <mutex>
-#include <tuple>
-#include <type_traits>
-#include <utility>
-#include <vector>
-
-namespace dfvo {
 
 #include "conv_epi.h"
+
+namespace dfvo {
 
 // Split-K finish inside the contracting kernel.  After a workgroup has written its partial tile to the workspace it draws
 // a ticket for that tile; whoever draws the last one (all z-slices are then written) reduces the partials and runs the
@@ -546,78 +529,6 @@ __global__ void conv_splitk_epilogue(const ConvParams p, int splits) {
     p.dst[(size_t)m * p.dst_cs + p.dst_co + col] = v;
 }
 
-int conv_pick_bn(int cout, long long M) {
-    (void)M;
-    if (cout <= 16) return 16;
-    if (cout <= 32) return 32;
-    if (cout % 128 == 0) return 128;
-    if (cout % 64 == 0) return 64;
-    if (cout % 32 == 0) return 32;  // 96 -> 3 x 32
-    return 64;                      // 49 -> 64
-}
-
-void conv_pack_weights(const float* w, const float* bias, int cout, int c0, int c1, int kh, int kw, int cout_pad,
-                       const float* fold_scale, const float* fold_shift, float* out_w, float* out_b) {
-    const int G0 = cdiv(c0, 4), G1 = cdiv(c1, 4), G = G0 + G1;
-    const int taps = kh * kw;
-    const int ksteps = cdiv(taps * G, 4);
-    const int cin = c0 + c1;
-    std::fill(out_w, out_w + (size_t)ksteps * 4 * cout_pad * 4, 0.f);
-    for (int tap = 0; tap < taps; ++tap) {
-        const int ky = tap / kw, kx = tap % kw;
-        for (int cg = 0; cg < G; ++cg) {
-            const int g = tap * G + cg;
-            for (int q = 0; q < 4; ++q) {
-                int ci;
-                if (cg < G0) {
-                    ci = cg * 4 + q;
-                    if (ci >= c0) continue;
-                } else {
-                    ci = (cg - G0) * 4 + q;
-                    if (ci >= c1) continue;
-                    ci += c0;
-                }
-                for (int o = 0; o < cout; ++o) {
-                    float v = w[(((size_t)o * cin + ci) * kh + ky) * kw + kx];
-                    if (fold_scale) v *= fold_scale[o];
-                    out_w[((size_t)g * cout_pad + o) * 4 + q] = v;
-                }
-            }
-        }
-    }
-    for (int o = 0; o < cout_pad; ++o) {
-        float b = 0.f;
-        if (o < cout) {
-            b = bias ? bias[o] : 0.f;
-            if (fold_scale) b *= fold_scale[o];
-            if (fold_shift) b += fold_shift[o];
-        }
-        out_b[o] = b;
-    }
-}
-
-
-size_t conv_head_weight_floats(int cout, int c0, int c1, int k) {
-    return (size_t)(cdiv(c0, 8) + cdiv(c1, 8)) * k * 2 * k * cout * 4;
-}
-void conv_pack_head_weights(const float* w, int cout, int c0, int c1, int k, const float* fold_scale, float* out) {
-    const int nchunk0 = cdiv(c0, 8), nchunks = nchunk0 + cdiv(c1, 8), cin = c0 + c1;
-    std::fill(out, out + conv_head_weight_floats(cout, c0, c1, k), 0.f);
-    for (int c = 0; c < nchunks; ++c)
-        for (int kx = 0; kx < k; ++kx)
-            for (int cg = 0; cg < 2; ++cg)
-                for (int ky = 0; ky < k; ++ky)
-                    for (int o = 0; o < cout; ++o)
-                        for (int q = 0; q < 4; ++q) {
-                            const int cl = (c < nchunk0 ? c : c - nchunk0) * 8 + cg * 4 + q;  // channel inside its source
-                            if (cl >= (c < nchunk0 ? c0 : c1)) continue;
-                            const int ci = c < nchunk0 ? cl : c0 + cl;
-                            float v = w[(((size_t)o * cin + ci) * k + ky) * k + kx];
-                            if (fold_scale) v *= fold_scale[o];
-                            out[(((((size_t)c * k + kx) * 2 + cg) * k + ky) * cout + o) * 4 + q] = v;
-                        }
-}
-
 // ------------------------------------------------------------------------------------------------
 // Direct (VALU) convolution for the 1- and 2-channel heads: LiteFlowNet's flow outputs (7x7 / 5x5 / 3x3, 32 -> 2) and
 // monodepth2's disparity outputs (3x3, C -> 1).  On the MFMA kernels these layers pad cout to a 16-wide tile and
@@ -782,107 +693,6 @@ __global__ __launch_bounds__(256) void conv_head_f32_kernel(const ConvParams p) 
     }
 }
 
-
-// ---- optional per-launch timing with HIP events on the launch stream (bench.py roofline leg)
-struct ConvProfEntry {
-    hipEvent_t e0, e1;
-    int cfg;
-    double flops;
-    // N H W Ho Wo cin cout k stride gx gy gz.  gx gy gz are what the launcher passes to ConvProfScope::done(), three conventions:
-    //   fp32 kernels (cfg 0-18): the grid -- gz = split-K slices, heads gy = gz = 1
-    //   window f16 kernels (cfg 19): gx gy = the grid, gz = the skeleton (1 conv_win_f16s.h, 2 conv_win_f16s2.h, mixed heights too)
-    //   generic kernels (cfg 20-23): gx = the grid, gy = cout blocks per wave TC, gz = 100 KSP + 1 (K slices per workgroup);
-    //     the tap-window kernel: gy = 0, gz = 7; the fp32 twin conv_gemm_f32g: gy = 0
-    int shape[12];
-    // the instantiation that ran: "igemm<2,2,4,4>", "f16g<4,1,2,rag> np3", "win3<2,2,4,2,3> tickets" (ConvProfScope::done)
-    char variant[48];
-};
-static std::vector<ConvProfEntry>* g_prof = nullptr;
-
-ConvProfScope::ConvProfScope(const ConvParams& p, hipStream_t stream, int cfg_id) : p_(p), stream_(stream), cfg_(cfg_id) {
-    if (!g_prof) return;
-    if ((err_ = hipEventCreate(&e0_)) != hipSuccess) return;
-    if ((err_ = hipEventCreate(&e1_)) == hipSuccess) err_ = hipEventRecord(e0_, stream_);
-}
-ConvProfScope::~ConvProfScope() {
-    if (e0_) (void)hipEventDestroy(e0_);
-    if (e1_) (void)hipEventDestroy(e1_);
-}
-int ConvProfScope::done(int gx, int gy, int gz, const char* variant, int f16_terms, int splitk) {
-    if (err_ != hipSuccess) {  // of the constructor: reported here, where the launcher can return it
-        set_last_error(std::string("conv profile events: ") + hipGetErrorString(err_));
-        return DFVO_ERR_HIP;
-    }
-    if (!e1_ || !g_prof) return DFVO_OK;  // no profile is running
-    DFVO_HIP_CHECK(hipEventRecord(e1_, stream_));
-    g_prof->push_back({e0_, e1_, cfg_, p_.useful_flops,
-                       {p_.N, p_.H, p_.W, p_.Ho, p_.Wo, (p_.G0 + p_.G1) * 4, p_.cout, p_.kh, p_.stride, gx, gy, gz}, {0}});
-    snprintf(g_prof->back().variant, sizeof(g_prof->back().variant), "%s%s%s", variant,
-             f16_terms == 3 ? " np3" : (f16_terms == 1 ? " np1" : ""),
-             splitk == CONV_SPLITK_TICKETS ? " tickets" : (splitk == CONV_SPLITK_EPILOGUE ? " epilogue" : ""));
-    e0_ = e1_ = nullptr;  // conv_profile_end() destroys them
-    return DFVO_OK;
-}
-
-void conv_profile_begin() {
-    if (!g_prof) g_prof = new std::vector<ConvProfEntry>();
-    g_prof->clear();
-}
-// cfg ids (BM x BN): 0 <2,2,4,4> 128x128  1 <1,4,2,2> 32x128  2 <4,1,4,4> 256x64  3 <2,2,2,2> 64x64  4 <4,1,4,2> 256x32
-//   5 <2,2,2,1> 64x32  6 <4,1,4,1> 256x16  7 <4,1,1,1> 64x16  8 <1,4,4,2> 64x128  9 <2,2,4,2> 128x64  10 <4,1,2,2> 128x32
-//   11 <4,1,2,1> 128x16; LDS-window 3x3 kernel: 12 (8x16)x128  13 (8x16)x64  14 (8x16)x32  15 (4x16)x128
-//   16 7x7 heads  17 5x5 heads  18 3x3 heads (direct kernel for cout <= 2; the window kernel (8x16)x16 above that)
-// bytes (optional): ALGORITHMIC HBM bytes of the launches of a configuration -- fp32 input map once + fp32 output map once +
-// fp32 weights once (the figure SURVEY.md section 8d prices the streaming layers with); what the kernels really moved comes
-// from the PMC passes under profiles/
-int conv_profile_end(double* ms, double* flops, int* launches, double* bytes) {
-    for (int i = 0; i < CONV_NUM_CFGS; i++) {
-        ms[i] = 0;
-        flops[i] = 0;
-        launches[i] = 0;
-        if (bytes) bytes[i] = 0;
-    }
-    if (!g_prof) return DFVO_OK;
-    // DFVO_CONV_PROFILE_CSV=<path>: one line per launch (tuning aid; tests/test_conv_variants_gpu.py reads the last column).
-    // variant, the last column, names the instantiation that ran from the launcher's own template arguments and contains
-    // commas itself: igemm<WM,WN,TM,TN>, win3<WM,WN,TM,TN,KS>, head<KS,CO,py1|py2>, f16s<WC,WR,TC,TR>, f16s2<WC,WR,TC,TR>,
-    // f16s2mix<WC,WR,TC,TRA,TRB>, f16g<WP,KSP,TC[,rag]>, taps<TH,TC>, f32g<WP,KSP,TC>, wino<WN>; then " np3" / " np1" for the
-    // kernels that come in f16x3 and f16 form, then " tickets" / " epilogue" for a launch whose K slices over grid.z were
-    // finished inside the kernel / by conv_splitk_epilogue
-    const char* csv_path = getenv("DFVO_CONV_PROFILE_CSV");
-    FILE* csv = csv_path ? fopen(csv_path, "a") : nullptr;
-    if (csv) fprintf(csv, "cfg,N,H,W,Ho,Wo,cin,cout,k,stride,gx,gy,gz,us,tflops,variant\n");
-    for (auto& e : *g_prof) {
-        float t = 0.f;
-        DFVO_HIP_CHECK(hipEventSynchronize(e.e1));
-        DFVO_HIP_CHECK(hipEventElapsedTime(&t, e.e0, e.e1));
-        ms[e.cfg] += t;
-        if (csv)
-            fprintf(csv, "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%.4f,%.4f,%s\n", e.cfg, e.shape[0], e.shape[1], e.shape[2],
-                    e.shape[3], e.shape[4], e.shape[5], e.shape[6], e.shape[7], e.shape[8], e.shape[9], e.shape[10],
-                    e.shape[11], t * 1e3, e.flops / (t * 1e-3) / 1e12, e.variant);
-        flops[e.cfg] += e.flops;
-        launches[e.cfg] += 1;
-        if (bytes) {
-            const double opx = (double)e.shape[0] * e.shape[3] * e.shape[4], ipx = (double)e.shape[0] * e.shape[1] * e.shape[2];
-            const double macs_per_px = opx > 0 ? e.flops / (2.0 * opx) : 0.0;  // cout x cin x kh x kw
-            bytes[e.cfg] += 4.0 * (ipx * e.shape[5] + opx * e.shape[6] + macs_per_px);
-        }
-        (void)hipEventDestroy(e.e0);
-        (void)hipEventDestroy(e.e1);
-    }
-    if (csv) fclose(csv);
-    delete g_prof;
-    g_prof = nullptr;
-    return DFVO_OK;
-}
-
-#include "conv_pack_f16s.h"
-#include "conv_win_f16s.h"
-#include "conv_gemm_f16s.h"
-#include "conv_win_f16s2.h"
-#include "conv_wino_f32.h"
-
 // Split-K when the grid cannot fill the chip (fewer than 600 workgroups): the number of K slices for `units` units of K
 // (K-steps, or channel chunks) with at least `min_per_slice` units each, at most `cap`, partials [slices][M][cout_pad] inside p.ws
 static int conv_splitk_slices(const ConvParams& p, long long blocks, int units, int min_per_slice, int cap) {
@@ -959,120 +769,34 @@ static int launch_head(const ConvParams& p, hipStream_t stream, int cfg_id) {
     return prof.done((int)grid.x, 1, 1, (py1 ? variant1 : variant2).c_str());
 }
 
-// the direct kernel serves the square, stride-1, "same"-padded heads with one or two output channels
-static bool conv_use_head(const ConvParams& p) {
-    if (p.cout > 2 || !p.wh) return false;
-    if (p.kh != p.kw || p.stride != 1 || p.pad_h != p.kh / 2 || p.pad_w != p.kw / 2) return false;
-    if (p.kh != 3 && p.kh != 5 && p.kh != 7) return false;
-    return (long long)p.N * p.Ho * p.Wo >= 1024;
+// ---- what the dispatcher calls (conv_dispatch.hip makes the choices; the template arguments they stand for are here) ----
+int launch_head_f32(const ConvParams& p, hipStream_t stream) {
+    if (p.kh == 7) return p.cout == 2 ? launch_head<7, 2>(p, stream, 16) : launch_head<7, 1>(p, stream, 16);
+    if (p.kh == 5) return p.cout == 2 ? launch_head<5, 2>(p, stream, 17) : launch_head<5, 1>(p, stream, 17);
+    return p.cout == 2 ? launch_head<3, 2>(p, stream, 18) : launch_head<3, 1>(p, stream, 18);
 }
 
-// the LDS-window kernel serves 3x3 / stride-1 layers on maps large enough to fill the chip with TH x 16 tiles
-static bool conv_use_window(const ConvParams& p, int bn) {
-    if (p.kh != p.kw || p.stride != 1 || p.pad_h != p.kh / 2 || p.pad_w != p.kw / 2) return false;
-    const long long M = (long long)p.N * p.Ho * p.Wo;
-    if (p.kh == 3) return bn >= 32 && M >= 30000;
-    // 5x5 / 7x7 flow heads (32 -> 2 channels): the whole tap loop runs out of one window
-    return (p.kh == 5 || p.kh == 7) && bn == 16 && (p.G0 + p.G1) >= 4 && M >= 8000;
-}
-
-// the profile row (12-15) of the window kernel's tile class for a 3x3 layer: launch_conv's window branch and the Winograd
-// launcher (which files its launches under the row of the class they replace) both go by it.  Under
-// dfvo_set_fp32_winograd(2), the unit-test mode, layers that never were window layers (bn 16, small maps) land on a row too.
-static int conv_window_cfg(const ConvParams& p, int bn) {
-    const long long tiles8 = (long long)p.N * ((p.Ho + 7) / 8) * ((p.Wo + 15) / 16) * (p.cout_pad / bn);
-    // 128-wide layers on the largest maps run as two 64-wide column blocks: 2x the workgroups at 4 (instead of 3) per CU
-    // shortens the under-filled last round of the grid (+5 % measured at 2 x 192 x 624)
-    if (bn == 128) return tiles8 >= 1200 ? 13 : (tiles8 >= 400 ? 12 : 15);
-    return bn == 64 ? 13 : 14;
-}
-// fp32 Winograd under dfvo_set_fp32_winograd(1), EXPERIMENTAL: the window kernel's own size rule without the 32-wide class,
-// whose Winograd workgroup is two waves (half of a CU's SIMDs).  A class stays here only where tools/wino_bench.py shows
-// Winograd at <= 0.90 x the direct kernel's time (DESIGN.md section 5d holds the table this rule goes by)
-constexpr long long WINO_MIN_PIXELS = 30000;  // conv_use_window's
-bool conv_wino_rule_may_accept(int cout, long long max_pixels) {
-    return conv_pick_bn(cout, max_pixels) >= 64 && (max_pixels <= 0 || max_pixels >= WINO_MIN_PIXELS);
-}
-static bool conv_wino_size_rule(const ConvParams& p, int bn) {
-    return conv_use_window(p, bn) && conv_wino_rule_may_accept(p.cout, (long long)p.N * p.Ho * p.Wo);
-}
-
-// Tile choice: the widest N tile the layer's cout allows (conv_pick_bn); the M tile from a sweep on MI355X
-// (tools/sweep_conv.sh): 64-row tiles win or tie on every layer with BN <= 64 and on BN = 128 below ~1200
-// workgroups (more resident workgroups hide the global -> LDS staging latency; the per-tap gather is served by
-// L2 either way); 128 x 128 keeps the largest maps.  Small grids additionally split K (conv_splitk_slices).
-static int conv_pick_bm(const ConvParams& p, int bn) {
-    const long long M = (long long)p.N * p.Ho * p.Wo;
-    const long long ntiles_n = p.cout_pad / bn;
-    auto blocks = [&](int bm) { return ((M + bm - 1) / bm) * ntiles_n; };
-    if (bn == 128) {
-        int bm = blocks(128) >= 1200 ? 128 : 64;
-        if (M <= 4096) bm = 32;
-        return bm;
+int launch_win_f32(const ConvParams& p, hipStream_t stream, int cfg_id) {
+    switch (cfg_id) {
+        case 16: return launch_win3<4, 1, 2, 1, 7>(p, stream, 16);
+        case 17: return launch_win3<4, 1, 2, 1, 5>(p, stream, 17);
+        case 12: return launch_win3<2, 2, 4, 4>(p, stream, 12);
+        case 13: return launch_win3<2, 2, 4, 2>(p, stream, 13);
+        case 15: return launch_win3<1, 4, 4, 2>(p, stream, 15);
+        default: return launch_win3<4, 1, 2, 2>(p, stream, 14);
     }
-    return M >= 400000 ? 128 : 64;
 }
 
-// exact-fp32 mode: which layers leave conv_igemm_f32_kernel for the register-ring kernel (conv_gemm_f32g.hip).  Not the
-// 3x3 / stride-1 layers the LDS-window kernel takes, not the one- / two-channel heads.
-// Measured (profiles/r4e_fp32_f32g_ab.txt): the small maps only 156.5 -> 160 pairs/s; every non-window layer 158 (the
-// streaming layers are no faster than on conv_igemm_f32_kernel).
-static bool conv_f32g_takes(const ConvParams& p, int bn) {
-    if (conv_use_head(p)) return false;
-    if (conv_use_window(p, bn)) return false;
-    const long long M = (long long)p.N * p.Ho * p.Wo;
-    return M <= 8192;  // pyramid levels 5 / 6 (2 x 11 x 38 .. 2 x 44 x 152) and the depth net's 6 x 20 .. 48 x 160 maps
-}
-
-int launch_conv(const ConvParams& p, hipStream_t stream, bool wino_all) {
-    const long long M = (long long)p.N * p.Ho * p.Wo;
-    const int bn = conv_pick_bn(p.cout, M);
-    DFVO_ARG_CHECK(p.cout_pad % bn == 0, "launch_conv: cout_pad not a multiple of the N tile");
-    DFVO_ARG_CHECK((p.cs0 % 4) == 0 && (p.co0 % 4) == 0, "launch_conv: src0 stride/offset must be multiples of 4");
-    DFVO_ARG_CHECK(p.G1 == 0 || ((p.cs1 % 4) == 0 && (p.co1 % 4) == 0), "launch_conv: src1 stride/offset");
-    if (conv_use_head(p)) {
-        if (p.kh == 7) return p.cout == 2 ? launch_head<7, 2>(p, stream, 16) : launch_head<7, 1>(p, stream, 16);
-        if (p.kh == 5) return p.cout == 2 ? launch_head<5, 2>(p, stream, 17) : launch_head<5, 1>(p, stream, 17);
-        return p.cout == 2 ? launch_head<3, 2>(p, stream, 18) : launch_head<3, 1>(p, stream, 18);
-    }
-    if (p.wf16 && conv_f16s_ok(p)) {  // f16x3: the 3x3 / stride-1 layers whose map fills the chip
-        const int rc2 = launch_f16s2(p, stream, 19);  // one-wave-per-SIMD skeleton where the grid is large enough
-        return rc2 != F16S2_NOT_APPLICABLE ? rc2 : launch_f16s(p, stream, 19);  // errors (negative) propagate
-    }
-    if (conv_f16g_ok(p)) return launch_f16g(p, stream);  // f16x3: everything else (small maps, 1x1, k x 1, stride 2, 7x7)
-    // fp32 Winograd (opt-in, decided when the layer was packed): ahead of every direct fp32 kernel.  Its launches are filed
-    // under the window row of the tile class they replace, with the direct convolution's FLOP count
-    if (conv_wino_applicable(p) && (wino_all || conv_wino_size_rule(p, bn))) return launch_wino(p, stream, conv_window_cfg(p, bn));
-    if (conv_f32g_ok(p) && conv_f32g_takes(p, bn)) return launch_f32g(p, stream);  // exact fp32: the same skeleton on fp32 MFMAs
-    if (conv_use_window(p, bn) && p.kh == 7) return launch_win3<4, 1, 2, 1, 7>(p, stream, 16);
-    if (conv_use_window(p, bn) && p.kh == 5) return launch_win3<4, 1, 2, 1, 5>(p, stream, 17);
-    if (conv_use_window(p, bn)) {
-        switch (conv_window_cfg(p, bn)) {
-            case 12: return launch_win3<2, 2, 4, 4>(p, stream, 12);
-            case 13: return launch_win3<2, 2, 4, 2>(p, stream, 13);
-            case 15: return launch_win3<1, 4, 4, 2>(p, stream, 15);
-            default: return launch_win3<4, 1, 2, 2>(p, stream, 14);
-        }
-    }
-    const int bm = conv_pick_bm(p, bn);  // (never 256 today: those tiles stay instantiated and selectable by the rule)
+// bm of conv_pick_bm: 128, 64, or 32 (128-wide tiles only).  No rule picks 256 rows, and no such tile is built.
+int launch_igemm_f32(const ConvParams& p, hipStream_t stream, int bm, int bn) {
     if (bn == 128) {
         if (bm == 128) return launch_cfg<2, 2, 4, 4>(p, stream, 0);
         if (bm == 64) return launch_cfg<1, 4, 4, 2>(p, stream, 8);
         return launch_cfg<1, 4, 2, 2>(p, stream, 1);
     }
-    if (bn == 64) {
-        if (bm == 256) return launch_cfg<4, 1, 4, 4>(p, stream, 2);
-        if (bm == 128) return launch_cfg<2, 2, 4, 2>(p, stream, 9);
-        return launch_cfg<2, 2, 2, 2>(p, stream, 3);
-    }
-    if (bn == 32) {
-        if (bm == 256) return launch_cfg<4, 1, 4, 2>(p, stream, 4);
-        if (bm == 128) return launch_cfg<4, 1, 2, 2>(p, stream, 10);
-        return launch_cfg<2, 2, 2, 1>(p, stream, 5);
-    }
-    if (bm == 256) return launch_cfg<4, 1, 4, 1>(p, stream, 6);
-    if (bm == 128) return launch_cfg<4, 1, 2, 1>(p, stream, 11);
-    return launch_cfg<4, 1, 1, 1>(p, stream, 7);
+    if (bn == 64) return bm == 128 ? launch_cfg<2, 2, 4, 2>(p, stream, 9) : launch_cfg<2, 2, 2, 2>(p, stream, 3);
+    if (bn == 32) return bm == 128 ? launch_cfg<4, 1, 2, 2>(p, stream, 10) : launch_cfg<2, 2, 2, 1>(p, stream, 5);
+    return bm == 128 ? launch_cfg<4, 1, 2, 1>(p, stream, 11) : launch_cfg<4, 1, 1, 1>(p, stream, 7);
 }
 
 }  // namespace dfvo

@@ -1,7 +1,9 @@
-// Winograd F(2x2,3x3) weights for conv_wino_f32_kernel (conv_wino_f32.h), packed on the host.  Host-only and free of HIP:
+// Winograd F(2x2,3x3) weights for conv_wino_f32_kernel (conv_wino_f32.hip), packed on the host.  Host-only and free of HIP:
 // a plain C++ compiler builds it (tests/test_wino_cpu.py does, under the address and undefined-behaviour sanitizers).
-// The including file provides <cstddef> and <cstring>; conv_igemm_f32.hip includes it inside namespace dfvo.
+// conv_pack.hip wraps the packer for the library; conv_wino_f32.hip takes the layout's sizes from here.
 #pragma once
+#include <cstddef>
+#include <cstring>
 
 // U = G g G^T of one 3x3 filter, G = [[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], in float64
 static inline void wino_f32_filter_transform(const double g[9], double U[16]) {

@@ -13,13 +13,11 @@
 // Arithmetic: the generic kernel's, unchanged -- same packed weights and k-group table (g = tap G + channel group, four
 // k-groups per MFMA step), same operand positions in every MFMA, same products (hi x lo, lo x hi -> cross sums, hi x hi ->
 // main sums), same step order: outputs are bit-identical to conv_gemm_f16s_kernel<4, 1, TC>.
-#include "dfvo_common.h"
-
-
-namespace dfvo {
-
+#include "conv.h"
 #include "conv_epi.h"
 #include "conv_f16_split.h"
+
+namespace dfvo {
 
 typedef unsigned int u32x4t __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2t __attribute__((ext_vector_type(2)));

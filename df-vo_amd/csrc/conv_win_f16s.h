@@ -1,5 +1,5 @@
 // 3x3 / stride-1 convolution with fp32-class accuracy on the f16 matrix cores (opt-in: DFVO_CONV_PRECISION=f16x3).
-// Included by conv_igemm_f32.hip (same translation unit: shares the epilogue and the saturation counter of conv_f16_clamp.h).
+// A unit of conv_f16.hip (the f16 families share the saturation counter of conv_f16_clamp.h).
 //
 // Every fp32 operand x is split into two f16 planes  x = hi + 2^-11 lo,  hi = f16(x),  lo = f16((x - hi) * 2^11):
 // 22 mantissa bits, the scaled low plane never leaves f16's normal range (an unscaled residue would be subnormal for
@@ -20,9 +20,10 @@
 // The accumulator layout (col = lane & 31 = pixel, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) = cout) gives a lane
 // four consecutive couts of one pixel per register quad: the fp32 kernels' 16-byte vector epilogue is reused as is.
 #pragma once
-// (included inside namespace dfvo)
-
+#include "conv_epi.h"
 #include "conv_f16_clamp.h"
+
+namespace dfvo {
 
 template <int WC, int WR, int TC, int TR, int NP = 3>  // NP: products per term (3 = f16x3, 1 = "f16" mode: hi planes only)
 __global__ __launch_bounds__(64 * WC * WR, 2) void conv_win_f16s_kernel(const ConvParams p) {
@@ -217,18 +218,6 @@ __global__ __launch_bounds__(64 * WC * WR, 2) void conv_win_f16s_kernel(const Co
     }
 }
 
-static bool conv_f16s_ok(const ConvParams& p) {
-    if (p.kh != 3 || p.kw != 3 || p.stride != 1 || p.pad_h != 1 || p.pad_w != 1) return false;
-    if (p.wf16_cout_pad % 32 != 0 || p.Wo < 24 || p.Ho < 4) return false;
-    // small maps stay on the fp32 split-K kernels: with fewer than ~200 of the smallest (32 couts x 4 x 32 px) tiles the
-    // grid cannot fill the chip and the un-split K loop makes the launch longer than the fp32 one (measured: pyramid
-    // levels 5 / 6 and the depth net's inner layers 2-4x slower, level 4 1.5-2x faster)
-    const long long e = (long long)p.N * ((p.Ho + 3) / 4) * ((p.Wo + 31) / 32) * (p.wf16_cout_pad / 32);
-    // (round 4: raising the bound to 450 / 900 tiles sends pyramid level 4 / 3 to the generic kernel instead -- the window
-    // family's average TFLOP/s rises, 0.265 -> 0.30 / 0.31 of its roofline, and the pair rate FALLS, 287 -> 280 / 272: kept at 200)
-    return e >= 200;
-}
-
 // workgroups of a launch with this tile shape, either window skeleton (0: the shape does not divide the layer's couts)
 template <int WC, int WR, int TC, int TR>
 static long long f16s_blocks(const ConvParams& p) {
@@ -258,3 +247,5 @@ static int launch_f16s_cfg(const ConvParams& p, hipStream_t stream, int cfg_id) 
 static int launch_f16s(const ConvParams& p, hipStream_t stream, int cfg_id) {
     return launch_f16s_cfg<1, 4, 1, 1>(p, stream, cfg_id);
 }
+
+}  // namespace dfvo

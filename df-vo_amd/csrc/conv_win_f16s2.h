@@ -13,7 +13,15 @@
 // (once per 9 taps = 216 MFMAs).  One 4-wave workgroup per CU (512 registers per lane: __launch_bounds__(256, 1)).
 // Same arithmetic, window layout, weight packing and epilogue as conv_win_f16s_kernel.
 #pragma once
-// (included inside namespace dfvo, after conv_win_f16s.h)
+#include <algorithm>
+#include <map>
+#include <mutex>
+#include <tuple>
+#include <utility>
+
+#include "conv_win_f16s.h"  // f16s_blocks, and what it includes
+
+namespace dfvo {
 
 template <class F, int... T>
 __device__ __forceinline__ void f16s2_static_for_impl(F&& f, std::integer_sequence<int, T...>) {
@@ -443,3 +451,5 @@ static int launch_f16s2(const ConvParams& p, hipStream_t stream, int cfg_id) {
     if (cost(b3, 12) <= cost(b2, 8)) return launch_f16s2_cfg<1, 4, 1, 3>(p, stream, cfg_id);
     return launch_f16s2_cfg<1, 4, 1, 2>(p, stream, cfg_id);
 }
+
+}  // namespace dfvo

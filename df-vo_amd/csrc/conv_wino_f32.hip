@@ -1,5 +1,5 @@
 // Winograd F(2x2,3x3) on the fp32 MFMA: the opt-in path of the 3x3 / stride-1 / zero-pad layers packed in "fp32"
-// (dfvo_set_fp32_winograd; included by conv_igemm_f32.hip inside namespace dfvo).  All-fp32 arithmetic, 16 instead of 36
+// (dfvo_set_fp32_winograd): the kernel, its switch, launch counter and launcher.  All-fp32 arithmetic, 16 instead of 36
 // multiplications per 2x2 output tile, not bit-identical to the direct kernels.
 //
 // One launch per layer; neither the transformed input V nor the product M leaves the chip.  A workgroup of WN * 2 waves owns
@@ -20,9 +20,15 @@
 // spilled to VGPR lanes (the window masks and offsets), outside the MFMA sequence.
 // The grid is exactly N * tiles_y * tiles_x workgroups in x (the XCD-aware remap of blockIdx.x is a permutation of that
 // range only) and round_up(cout, 32) / BN in y; the launcher below is the only caller.
-#pragma once
+#include "conv.h"
 
+#include <cstdlib>
+#include <mutex>
+
+#include "conv_epi.h"
 #include "conv_pack_wino_f32.h"
+
+namespace dfvo {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -254,13 +260,9 @@ int conv_fp32_winograd_launches(unsigned long long* n, int reset) {
     if (reset) g_wino_launches = 0;
     return DFVO_OK;
 }
-size_t conv_wino_f32_weight_floats(int cout, int c0, int c1) { return conv_wino_f32_floats(cout, c0, c1); }
-void conv_pack_weights_wino_f32(const float* w_oihw, int cout, int c0, int c1, const float* fold_scale, float* out) {
-    conv_pack_wino_f32(w_oihw, cout, c0, c1, fold_scale, out);
-}
 
 // what the kernel computes: 3x3, stride 1, zero padding of 1, no upsampled source, not the one- / two-channel heads
-static bool conv_wino_applicable(const ConvParams& p) {
+bool conv_wino_applicable(const ConvParams& p) {
     return p.wu32 && p.kh == 3 && p.kw == 3 && p.stride == 1 && p.pad_h == 1 && p.pad_w == 1 && p.pad_mode == PAD_ZERO &&
            p.up0 == 0 && p.cout > 2;
 }
@@ -282,6 +284,8 @@ static int launch_wino_cfg(const ConvParams& p, hipStream_t stream, int cfg_id) 
     return prof.done((int)grid.x, (int)grid.y, 1, variant.c_str());
 }
 // cfg_id: the window row of the class the launch replaces (12-15), with the direct convolution's FLOP count
-static int launch_wino(const ConvParams& p, hipStream_t stream, int cfg_id) {
+int launch_wino(const ConvParams& p, hipStream_t stream, int cfg_id) {
     return wino_f32_cout_pad(p.cout) % 64 == 0 ? launch_wino_cfg<2>(p, stream, cfg_id) : launch_wino_cfg<1>(p, stream, cfg_id);
 }
+
+}  // namespace dfvo

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "conv.h"
 #include "dev_mem.h"
 
 #define DFVO_TRY(expr)                   \

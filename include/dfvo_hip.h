@@ -101,7 +101,7 @@ int dfvo_set_sklearn_compat(const char* version);
  * *h_count = events since the last reset (0 = the f16x3 result is the 22-bit split of the true operands everywhere).
  * reset != 0 clears the counter. */
 int dfvo_f16s_overflow_count(unsigned long long* h_count, int reset);
-/* Opt-in Winograd F(2x2,3x3) for the layers packed in "fp32" (df-vo_amd/csrc/conv_wino_f32.h): all-fp32 arithmetic, 16
+/* Opt-in Winograd F(2x2,3x3) for the layers packed in "fp32" (df-vo_amd/csrc/conv_wino_f32.hip): all-fp32 arithmetic, 16
  * instead of 36 multiplications per 2x2 output tile, NOT bit-identical to the direct fp32 kernels (its error bound is the
  * fp32 row's constant on the magnitudes of the transformed products: tests/wino_bounds.py).
  * 0 off (default); 1 on (experimental): 3x3 / stride-1 / zero-pad-1 layers with cout > 2 that the size rule accepts run as

@@ -3,7 +3,7 @@
 touches the GPU.
 
 A variant is named by the tag the per-launch profile records (the `variant` column of DFVO_CONV_PROFILE_CSV, see
-conv_profile_end in df-vo_amd/csrc/conv_igemm_f32.hip): the launcher's family and its template arguments,
+conv_profile_end in df-vo_amd/csrc/conv_profile.hip): the launcher's family and its template arguments,
     igemm<WM,WN,TM,TN>   win3<WM,WN,TM,TN,KS>   head<KS,CO,py1|py2>   f16s<WC,WR,TC,TR>   f16s2<WC,WR,TC,TR>
     f16s2mix<WC,WR,TC,TRA,TRB>   f16g<WP,KSP,TC[,rag]>   taps<TH,TC>   f32g<WP,KSP,TC>   wino<WN>
 followed in the profile by " np3" / " np1" (the f16 families, by packing) and " tickets" / " epilogue" (a launch whose K
@@ -13,8 +13,8 @@ VARIANTS      tag -> the packings (dfvo_set_conv_precision) in which dfvo_conv2d
               The head kernels are exact fp32 in every packing.  conv_igemm_f32_kernel is listed under fp32 alone: in the f16
               packings only a kernel wider than 31 taps falls through to it.  wino<WN> needs dfvo_set_fp32_winograd (a call,
               not an environment switch): its two cases turn mode 2 on around the launch.
-UNREACHABLE   what no case can run, each with its reason: the three 256-row tiles of profile rows 2 / 4 / 6, and the forms that
-              only a switch read once per process selects.
+UNREACHABLE   what no case can run, each with its reason: the forms that only a switch read once per process selects.  (The
+              three 256-row tiles of profile rows 2 / 4 / 6, which no tile rule chose, are no longer built.)
               The " epilogue" finish of a split-K launch is one of the latter (DFVO_SPLITK_FUSED=0): split-K needs fewer than
               600 tiles and the tickets cover 4096, so the in-kernel finish always applies; a child process of
               tests/test_nets_gpu.py compares the two finishes bit for bit.
@@ -51,9 +51,6 @@ for _t in ("1", "2"):
     VARIANTS["wino<%s>" % _t] = _FP32
 
 UNREACHABLE = {
-    "igemm<4,1,4,4>": "profile row 2 (256 x 64): conv_pick_bm never returns 256",
-    "igemm<4,1,4,2>": "profile row 4 (256 x 32): conv_pick_bm never returns 256",
-    "igemm<4,1,4,1>": "profile row 6 (256 x 16): conv_pick_bm never returns 256",
     # forms of reachable instantiations that only a test hook, read once per process, selects
     "DFVO_TAPS=0": "f16g<4,1,TC> on the tap-window kernel's layers: the child process of tests/test_nets_gpu.py compares the two",
     "DFVO_WIN_MIX=0": "single-height f16s2 launches where the mixed rule fires: child processes of "

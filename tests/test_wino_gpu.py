@@ -1,4 +1,4 @@
-"""GPU: the opt-in fp32 Winograd F(2x2,3x3) path (dfvo_set_fp32_winograd, df-vo_amd/csrc/conv_wino_f32.h).
+"""GPU: the opt-in fp32 Winograd F(2x2,3x3) path (dfvo_set_fp32_winograd, df-vo_amd/csrc/conv_wino_f32.hip).
   1. operator parity through dfvo_conv2d with mode 2 against the float64 convolution within tests/wino_bounds.py's bound,
      one launch of the Winograd kernel per call;
   2. layers the kernel does not compute return the bit-identical array of mode 0 and launch nothing;

@@ -1,5 +1,5 @@
 """Winograd F(2x2,3x3) in fp32 on the CPU, and its per-output error bound against float64 -- shared by tests/test_wino_cpu.py
-and tests/test_wino_gpu.py (the device kernel: df-vo_amd/csrc/conv_wino_f32.h).
+and tests/test_wino_gpu.py (the device kernel: df-vo_amd/csrc/conv_wino_f32.hip).
 
 The bound is the Winograd analogue of layer_bounds.conv_bound's fp32 row, the same constant on the magnitudes of the products
 the algorithm really forms:

@@ -1,5 +1,7 @@
 """condensed view of a kernel's main loop in the gfx950 ISA (no GPU needed):
-    python tools/isa_loop.py df-vo_amd/csrc/conv_igemm_f32.hip '<mangled-name prefix>'
+    python tools/isa_loop.py df-vo_amd/csrc/conv_f16.hip '<mangled-name prefix>'
+(the unit that instantiates the kernel: conv_igemm_f32.hip the fp32 kernels, conv_f16.hip the f16 families of the conv_*_f16s*.h
+headers, conv_wino_f32.hip, conv_gemm_f32g.hip, conv_taps_f16s.hip)
 prints the instruction stream between the loop header that contains the MFMAs and its back edge, run-length encoded, with the
 operands of waits / memory instructions kept."""
 import re

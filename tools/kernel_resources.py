@@ -1,5 +1,6 @@
 """register / LDS / scratch usage of the kernels of one .hip file (hipcc -Rpass-analysis=kernel-resource-usage, no GPU
-needed): python tools/kernel_resources.py df-vo_amd/csrc/conv_igemm_f32.hip [name filter]"""
+needed): python tools/kernel_resources.py df-vo_amd/csrc/conv_f16.hip [name filter]
+(a unit that instantiates kernels: the f16 conv families are instantiated by conv_f16.hip, not by their headers)"""
 import re
 import subprocess
 import sys
