@@ -285,24 +285,32 @@ def test_splitk_in_kernel_finish_under_pipeline_load(gpu, tmp_path):
 
 
 def test_flownet_graph_replay_is_identical(gpu):
+    """graph replay equals the eager pass bit for bit, on ANOTHER pair in every pass (the net's output buffers still hold the
+    pass before, so a replay that does nothing or reads a stale frame differs) and into host arrays that hold NaN before the
+    call; the first pair again at the end.  tests/test_graph_replay_gpu.py has the caller's buffers, the depth net, the
+    pipeline and the session."""
     lib = gpu.lib()
     h, w = 128, 224
     sd = O.liteflownet_state_dict(4869)
-    ref_img, cur_img = image_pair(h, w, seed=7)
-    outs = []
+    pairs = [image_pair(h, w, seed=s) for s in (7, 8, 9, 7)]
+    outs = {}
     for graph in (0, 1):
         net, _, _ = make_flownet(gpu, h, w, sd, graph=graph)
-        for _ in range(3):  # eager+capture, replay, replay
-            fwd = np.zeros((2, h, w), np.float32)
-            bwd = np.zeros((2, h, w), np.float32)
-            diff = np.zeros((h, w), np.float32)
+        outs[graph] = []
+        for ref_img, cur_img in pairs:  # graphs on: eager + capture, then replays
+            fwd = np.full((2, h, w), np.nan, np.float32)
+            bwd = np.full((2, h, w), np.nan, np.float32)
+            diff = np.full((h, w), np.nan, np.float32)
             gpu.check(lib.dfvo_flownet_forward_host(net, gpu.as_ptr(ref_img), gpu.as_ptr(cur_img), gpu.as_ptr(fwd),
                                                     gpu.as_ptr(bwd), gpu.as_ptr(diff)))
-            outs.append((fwd, bwd, diff))
+            outs[graph].append((fwd, bwd, diff))
         lib.dfvo_flownet_destroy(net)
-    for o in outs[1:]:
-        for a, b in zip(outs[0], o):
-            assert np.array_equal(a, b)
+    for k, (eager, replay) in enumerate(zip(outs[0], outs[1])):
+        for a, b in zip(eager, replay):
+            assert np.isfinite(a).all() and np.array_equal(a, b), "pass %d" % k
+    for a, b in zip(outs[0][0], outs[0][3]):
+        assert np.array_equal(a, b)
+    assert not any(np.array_equal(outs[0][k][0], outs[0][k + 1][0]) for k in range(3))
 
 
 @pytest.mark.parametrize("h,w", [(64, 96), (192, 640)])
