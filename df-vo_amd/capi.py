@@ -215,7 +215,18 @@ SIGNATURES = {
     "dfvo_depthnet_forward_image_host": (_i, [_vp, _vp, _i, _i, _vp]),
     "dfvo_depthnet_last_flops": (_d, [_vp]),
     "dfvo_depthnet_sync": (_i, [_vp]),
+    "dfvo_posenet_create": (_i, [_i, _i, _f, _vp, C.POINTER(_vp)]),
+    "dfvo_posenet_destroy": (None, [_vp]),
+    "dfvo_posenet_set_param": (_i, [_vp, C.c_char_p, _vp, _i, _ip]),
+    "dfvo_posenet_finalize": (_i, [_vp]),
+    "dfvo_posenet_set_graph": (_i, [_vp, _i]),
+    "dfvo_posenet_forward": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "dfvo_posenet_forward_images_host": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "dfvo_posenet_last_flops": (_d, [_vp]),
+    "dfvo_posenet_sync": (_i, [_vp]),
     "dfvo_depth_postprocess": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
+    "dfvo_depth_consistency": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dfvo_depth_consistency_host": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "dfvo_read_depth_u16": (_i, [_vp, _i, _i, _d, _i, _i, _i, _i, _i, _i, _d, _d, _vp, _vp, _vp]),
     "dfvo_tracker_create": (_i, [_vp, C.POINTER(_vp)]),
     "dfvo_tracker_destroy": (None, [_vp]),
@@ -228,6 +239,7 @@ SIGNATURES = {
     "dfvo_tracker_get_rng_state": (_i, [_vp, _vp]),
     "dfvo_kp_local_bestn": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _ip, _ip]),
     "dfvo_kp_local_bestn_ex": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _ip, _ip]),
+    "dfvo_kp_local_bestn_depth": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _ip, _ip]),
     "dfvo_kp_sampled": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "dfvo_kp_bestn": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "dfvo_kp_rigid_flow": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.POINTER(RigidKpCfg), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

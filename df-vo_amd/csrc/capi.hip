@@ -483,12 +483,92 @@ int dfvo_depthnet_sync(dfvo_depthnet* n) {
     DFVO_HIP_CHECK(hipStreamSynchronize(n->net.stream));
     return DFVO_OK;
 }
+// ------------------------------------------------------------------------------------------------
+int dfvo_posenet_create(int feed_h, int feed_w, float baseline_mult, void* stream, dfvo_posenet** out) {
+    DFVO_ARG_CHECK(out, "dfvo_posenet_create: null out");
+    dfvo_posenet* n = new dfvo_posenet();
+    n->net.baseline_mult = baseline_mult;
+    int rc = n->net.init(feed_h, feed_w, (hipStream_t)stream);
+    if (rc != DFVO_OK) {
+        delete n;
+        return rc;
+    }
+    *out = n;
+    return DFVO_OK;
+}
+void dfvo_posenet_destroy(dfvo_posenet* n) {
+    delete n;
+}
+int dfvo_posenet_set_param(dfvo_posenet* n, const char* name, const float* h, int ndim, const int* shape) {
+    DFVO_ARG_CHECK(n, "null net");
+    DFVO_ARG_CHECK(!n->net.finalized, "set_param after finalize");
+    return store_param(&n->net.params, name, h, ndim, shape);
+}
+int dfvo_posenet_finalize(dfvo_posenet* n) {
+    DFVO_ARG_CHECK(n, "null net");
+    return n->net.finalize();
+}
+int dfvo_posenet_set_graph(dfvo_posenet* n, int enable) {
+    DFVO_ARG_CHECK(n, "null net");
+    n->net.use_graph = enable != 0;
+    return DFVO_OK;
+}
+int dfvo_posenet_forward(dfvo_posenet* n, const uint8_t* d_img0, const uint8_t* d_img1, float* d_pose16, float* d_params6) {
+    DFVO_ARG_CHECK(n && d_img0 && d_img1 && d_pose16, "dfvo_posenet_forward: null argument");
+    return n->net.forward(d_img0, d_img1, d_pose16, d_params6);
+}
+int dfvo_posenet_forward_images_host(dfvo_posenet* n, const uint8_t* h_img0, const uint8_t* h_img1, int img_h, int img_w,
+                                     float* h_pose16) {
+    DFVO_ARG_CHECK(n && h_img0 && h_img1 && h_pose16 && img_h > 0 && img_w > 0, "dfvo_posenet_forward_images_host: bad argument");
+    PoseNet& p = n->net;
+    DFVO_ARG_CHECK(p.finalized, "forward before finalize");
+    if (n->resize.H != img_h || n->resize.W != img_w || n->resize.oh != p.H || n->resize.ow != p.W)
+        API_TRY(n->resize.init(img_h, img_w, p.H, p.W));
+    const size_t bytes = (size_t)img_h * img_w * 3, pitch = (bytes + 15) / 16 * 16;
+    API_TRY(n->img_full.grow(2 * pitch));
+    uint8_t* feed0 = (uint8_t*)p.u8_in.p;
+    uint8_t* feed1 = (uint8_t*)(p.u8_in.p + p.u8_frame_floats());
+    DFVO_HIP_CHECK(hipMemcpyAsync(n->img_full.p, h_img0, bytes, hipMemcpyHostToDevice, p.stream));
+    DFVO_HIP_CHECK(hipMemcpyAsync(n->img_full.p + pitch, h_img1, bytes, hipMemcpyHostToDevice, p.stream));
+    API_TRY(n->resize.enqueue(n->img_full.p, feed0, p.stream));
+    API_TRY(n->resize.enqueue(n->img_full.p + pitch, feed1, p.stream));
+    API_TRY(p.forward(feed0, feed1, p.out.p, p.out.p + 16));
+    DFVO_HIP_CHECK(hipMemcpyAsync(h_pose16, p.out.p, 16 * sizeof(float), hipMemcpyDeviceToHost, p.stream));
+    DFVO_HIP_CHECK(hipStreamSynchronize(p.stream));
+    return DFVO_OK;
+}
+double dfvo_posenet_last_flops(const dfvo_posenet* n) { return n ? n->net.flops_last : 0.0; }
+int dfvo_posenet_sync(dfvo_posenet* n) {
+    DFVO_ARG_CHECK(n, "null net");
+    DFVO_HIP_CHECK(hipStreamSynchronize(n->net.stream));
+    return DFVO_OK;
+}
 int dfvo_depth_postprocess(const float* d_depth, int h, int w, int H, int W, int y0, int y1, int x0, int x1,
                            float min_depth, float max_depth, float* d_raw, double* d_proc, void* stream) {
     DFVO_ARG_CHECK(d_depth && d_raw && d_proc, "dfvo_depth_postprocess: null argument");
     DFVO_ARG_CHECK(h >= 1 && w >= 1 && H >= 1 && W >= 1, "dfvo_depth_postprocess: empty map");
     return launch_depth_post(d_depth, h, w, H, W, y0, y1, x0, x1, min_depth, max_depth, d_raw, d_proc,
                              (hipStream_t)stream);
+}
+int dfvo_depth_consistency(const float* d_cur_depth, const float* d_ref_depth, int H, int W, const float* h_K, const float* h_Kinv,
+                           const float* h_T, float* d_out, void* stream) {
+    return launch_depth_consistency(d_cur_depth, d_ref_depth, H, W, h_K, h_Kinv, h_T, d_out, (hipStream_t)stream);
+}
+int dfvo_depth_consistency_host(const float* h_cur_depth, const float* h_ref_depth, int H, int W, const float* h_K, const float* h_Kinv,
+                                const float* h_T, float* h_out) {
+    DFVO_ARG_CHECK(h_cur_depth && h_ref_depth && h_out && H >= 2 && W >= 2, "dfvo_depth_consistency_host: bad argument");
+    const size_t px = (size_t)H * W;
+    DevArr<float> buf;  // current | reference | result, each on a 16-byte boundary
+    const size_t pitch = (px + 3) / 4 * 4;
+    API_TRY(buf.alloc(3 * pitch));
+    DFVO_HIP_CHECK(hipMemcpyAsync(buf.p, h_cur_depth, px * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    DFVO_HIP_CHECK(hipMemcpyAsync(buf.p + pitch, h_ref_depth, px * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    int rc = launch_depth_consistency(buf.p, buf.p + pitch, H, W, h_K, h_Kinv, h_T, buf.p + 2 * pitch, nullptr);
+    if (rc == DFVO_OK && hipMemcpyAsync(h_out, buf.p + 2 * pitch, px * sizeof(float), hipMemcpyDeviceToHost, nullptr) != hipSuccess) {
+        set_last_error("dfvo_depth_consistency_host: copying the result failed");
+        rc = DFVO_ERR_HIP;
+    }
+    return finish(rc, nullptr);  // the buffer dies behind the wait
 }
 int dfvo_read_depth_u16(const uint16_t* d_src_u16, int src_h, int src_w, double scale, int H, int W, int y0, int y1, int x0, int x1,
                         double min_depth, double max_depth, float* d_raw_f32, double* d_proc_f64, void* stream) {

@@ -248,9 +248,10 @@ int dfvo_kp_local_bestn(dfvo_tracker* t, const float* h_flow, const float* h_dif
                                   n_out, good_kp_found);
 }
 
-int dfvo_kp_local_bestn_ex(dfvo_tracker* t, const float* h_flow, const float* h_diff, int H, int W, int num_row,
-                           int num_col, int num_bestN, float thre, int score_method, double* h_kp1, double* h_kp2,
-                           int* n_out, int* good_kp_found) {
+// local_bestN over host arrays; h_depth_diff (null: no depth mask) is kp_selection.depth_consistency's map
+static int local_bestn_host(dfvo_tracker* t, const float* h_flow, const float* h_diff, const float* h_depth_diff, int H, int W,
+                            int num_row, int num_col, int num_bestN, float thre, float depth_thre, int score_method, double* h_kp1,
+                            double* h_kp2, int* n_out, int* good_kp_found) {
     DFVO_ARG_CHECK(t && h_flow && h_diff && h_kp1 && h_kp2 && n_out && good_kp_found && H > 0 && W > 0,
                    "dfvo_kp_local_bestn: bad argument");
     DFVO_ARG_CHECK(score_method == DFVO_KP_SCORE_FLOW || score_method == DFVO_KP_SCORE_FLOW_RATIO,
@@ -259,7 +260,12 @@ int dfvo_kp_local_bestn_ex(dfvo_tracker* t, const float* h_flow, const float* h_
     if (int rc_f = stage_flow(t, px)) return rc_f;
     DFVO_HIP_CHECK(hipMemcpyAsync(t->d_flow, h_flow, sizeof(float) * 2 * px, hipMemcpyHostToDevice, t->stream));
     DFVO_HIP_CHECK(hipMemcpyAsync(t->d_diff, h_diff, sizeof(float) * px, hipMemcpyHostToDevice, t->stream));
-    int rc = enqueue_local_bestn(t->tb, t->d_flow, t->d_diff, H, W, num_row, num_col, num_bestN, thre, t->stream, score_method);
+    if (h_depth_diff) {
+        if (int rc_d = t->d_depth_diff.grow(px)) return rc_d;
+        DFVO_HIP_CHECK(hipMemcpyAsync(t->d_depth_diff, h_depth_diff, sizeof(float) * px, hipMemcpyHostToDevice, t->stream));
+    }
+    int rc = enqueue_local_bestn(t->tb, t->d_flow, t->d_diff, H, W, num_row, num_col, num_bestN, thre, t->stream, score_method,
+                                 h_depth_diff ? t->d_depth_diff.p : nullptr, depth_thre);
     if (rc != DFVO_OK) return rc;
     int info[3];
     DFVO_HIP_CHECK(hipMemcpyAsync(info, t->tb.kp_info, sizeof(info), hipMemcpyDeviceToHost, t->stream));
@@ -271,6 +277,21 @@ int dfvo_kp_local_bestn_ex(dfvo_tracker* t, const float* h_flow, const float* h_
         DFVO_HIP_CHECK(hipMemcpy(h_kp2, t->tb.kp_cur, sizeof(double) * 2 * info[0], hipMemcpyDeviceToHost));
     }
     return DFVO_OK;
+}
+
+int dfvo_kp_local_bestn_ex(dfvo_tracker* t, const float* h_flow, const float* h_diff, int H, int W, int num_row,
+                           int num_col, int num_bestN, float thre, int score_method, double* h_kp1, double* h_kp2,
+                           int* n_out, int* good_kp_found) {
+    return local_bestn_host(t, h_flow, h_diff, nullptr, H, W, num_row, num_col, num_bestN, thre, 0.f, score_method, h_kp1, h_kp2,
+                            n_out, good_kp_found);
+}
+
+int dfvo_kp_local_bestn_depth(dfvo_tracker* t, const float* h_flow, const float* h_diff, const float* h_depth_diff, int H, int W,
+                              int num_row, int num_col, int num_bestN, float thre, float depth_thre, int score_method,
+                              double* h_kp1, double* h_kp2, int* n_out, int* good_kp_found) {
+    DFVO_ARG_CHECK(h_depth_diff, "dfvo_kp_local_bestn_depth: null depth_diff");
+    return local_bestn_host(t, h_flow, h_diff, h_depth_diff, H, W, num_row, num_col, num_bestN, thre, depth_thre, score_method,
+                            h_kp1, h_kp2, n_out, good_kp_found);
 }
 
 int dfvo_kp_bestn(dfvo_tracker* t, const float* h_flow, const float* h_diff, int H, int W, int num_bestN, double* h_kp1,

@@ -15,6 +15,11 @@ struct dfvo_depthnet {
     dfvo::LanczosResizer resize;  // dfvo_depthnet_forward_image_host / the session: tables for the last image size seen
     dfvo::DevArr<uint8_t> img_full;  // the full-size frame of dfvo_depthnet_forward_image_host, grown on demand
 };
+struct dfvo_posenet {
+    dfvo::PoseNet net;
+    dfvo::LanczosResizer resize;     // dfvo_posenet_forward_images_host: tables for the last image size seen
+    dfvo::DevArr<uint8_t> img_full;  // its two full-size frames, grown on demand
+};
 struct dfvo_tracker {
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -24,6 +29,7 @@ struct dfvo_tracker {
     dfvo::RansacWorkspace& ws = tb.ws_e;
     // staging of the host-array entry points, grown on demand (capi_tracker.hip: stage_flow, stage_depth)
     dfvo::DevArr<float> d_flow, d_diff;  // [2][px], [px]
+    dfvo::DevArr<float> d_depth_diff;    // [px], dfvo_kp_local_bestn_depth
     dfvo::DevArr<double> d_depth;
     dfvo::DevArr<double> d_small;        // 64 doubles
     dfvo::DevArr<double> d_x1, d_x2, d_X4;

@@ -133,6 +133,20 @@ struct FlowNet {
     ~FlowNet() { destroy(); }
 };
 
+// monodepth2's ResNet-18 encoder (resnet_encoder.py:87-98) over `in_ch` input channels: 3 for the depth net, 6 for the pose net
+// (ResnetEncoder(18, False, 2): two frames concatenated).  Both nets build and enqueue it through these two functions.
+struct ResNetEncoder {
+    ConvLayer conv1;
+    struct Block {
+        ConvLayer c1, c2, ds;
+        bool has_ds = false;
+    } blocks[8];
+    // x0: the normalised NHWC input (channels padded to a multiple of 4) the owner fills in front of enqueue()
+    DevArr<float> x0, pool, feat[5], blk_t, blk_ds, blk_o[2];
+    int build(const ParamStore& params, int H, int W, int in_ch);  // layers + activations; may be called again after a failure
+    int enqueue(int H, int W, hipStream_t s, double* fl, const DevArr<float>* splitk) const;  // x0 -> feat[0..4]
+};
+
 struct DepthNet {
     int H = 0, W = 0;  // feed size
     hipStream_t stream = nullptr;
@@ -141,13 +155,9 @@ struct DepthNet {
     bool finalized = false;
     float min_depth = 0.1f, max_depth = 100.f, baseline_mult = 5.4f;
 
-    ConvLayer conv1;
-    struct Block {
-        ConvLayer c1, c2, ds;
-        bool has_ds = false;
-    } blocks[8];
+    ResNetEncoder enc;
     ConvLayer up[5][2], dispconv;
-    DevArr<float> x0, pool, feat[5], blk_t, blk_ds, blk_o[2], du[5], dx[5], disp, depth;
+    DevArr<float> du[5], dx[5], disp, depth;
     DevArr<float> u8_in;
     DevArr<float> splitk;
     unsigned long long out_epoch = 0;  // forward() calls so far (see FlowNet::out_epoch)
@@ -165,6 +175,40 @@ struct DepthNet {
     int enqueue(const uint8_t* d_img, float* d_depth);
     void destroy();  // the graph and the owned stream; idempotent
     ~DepthNet() { destroy(); }
+};
+
+// monodepth2's two-frame pose net (pose/monodepth2/monodepth2.py:86-99): the encoder over six channels, PoseDecoder's four
+// convolutions (pose_decoder.py:26-54) and the head (mean, x 0.01, transformation_from_parameters(invert=True), translation x
+// baseline_mult).  One chain on one stream, captured like DepthNet's.
+struct PoseNet {
+    int H = 0, W = 0;  // feed size
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    ParamStore params;
+    bool finalized = false;
+    float baseline_mult = 5.4f;
+
+    ResNetEncoder enc;
+    ConvLayer dec[4];               // net.0 .. net.3
+    DevArr<float> d0, d1, d2, d3;   // their outputs ([H/32, W/32] maps of 256, 256, 256 and 12 channels)
+    DevArr<float> out;              // 16 floats of the 4x4, 6 raw parameters (the host entry point's device side)
+    DevArr<float> u8_in;            // two feed-size uint8 frames, each on a 16-byte boundary
+    DevArr<float> splitk;
+    double flops_last = 0.0;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t graph_exec = nullptr;
+    const uint8_t *graph_in0 = nullptr, *graph_in1 = nullptr;
+    float *graph_pose = nullptr, *graph_params = nullptr;
+    bool use_graph = true;
+    bool tuned_once = false;
+
+    size_t u8_frame_floats() const { return (((size_t)H * W * 3 + 15) / 16) * 4; }
+    int init(int feedH, int feedW, hipStream_t s);
+    int finalize();
+    int forward(const uint8_t* d_img0, const uint8_t* d_img1, float* d_pose16, float* d_params6);  // d_params6 may be null
+    int enqueue(const uint8_t* d_img0, const uint8_t* d_img1, float* d_pose16, float* d_params6);
+    void destroy();  // the graph and the owned stream; idempotent
+    ~PoseNet() { destroy(); }
 };
 
 }  // namespace dfvo

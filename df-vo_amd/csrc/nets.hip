@@ -676,15 +676,15 @@ static int bn_fold(const ParamStore& ps, const std::string& bn, int c, std::vect
     return DFVO_OK;
 }
 
+static const int kEncCh[5] = {64, 64, 128, 256, 512};
+
 // (may be called again after a failed attempt, as FlowNet::finalize)
-int DepthNet::finalize() {
-    if (finalized) return DFVO_OK;
+int ResNetEncoder::build(const ParamStore& params, int H, int W, int in_ch) {
     std::vector<float> sc, sh;
     const int N = 1;
-    const int ch[5] = {64, 64, 128, 256, 512};
-    // encoder
+    const int* ch = kEncCh;
     DFVO_TRY(bn_fold(params, "encoder.bn1", 64, &sc, &sh));
-    DFVO_TRY(make_conv(params, "encoder.conv1.weight", "", 3, 0, (long long)(H / 2) * (W / 2), sc.data(), sh.data(),
+    DFVO_TRY(make_conv(params, "encoder.conv1.weight", "", in_ch, 0, (long long)(H / 2) * (W / 2), sc.data(), sh.data(),
                        &conv1));
     conv1.stride = 2;
     conv1.pad_h = conv1.pad_w = 3;
@@ -722,6 +722,24 @@ int DepthNet::finalize() {
             }
         }
     }
+    DFVO_TRY(x0.alloc_zeroed((size_t)N * H * W * round_up(in_ch, 4)));
+    DFVO_TRY(feat[0].alloc_zeroed((size_t)N * (H / 2) * (W / 2) * 64));
+    DFVO_TRY(pool.alloc_zeroed((size_t)N * (H / 4) * (W / 4) * 64));
+    for (int i = 1; i < 5; ++i) DFVO_TRY(feat[i].alloc_zeroed((size_t)N * (H >> (i + 1)) * (W >> (i + 1)) * ch[i]));
+    const size_t big = (size_t)N * (H / 4) * (W / 4) * 64;  // every block tensor is <= this many floats
+    DFVO_TRY(blk_t.alloc_zeroed(big));
+    DFVO_TRY(blk_ds.alloc_zeroed(big));
+    DFVO_TRY(blk_o[0].alloc_zeroed(big));
+    DFVO_TRY(blk_o[1].alloc_zeroed(big));
+    return DFVO_OK;
+}
+
+// (may be called again after a failed attempt, as FlowNet::finalize)
+int DepthNet::finalize() {
+    if (finalized) return DFVO_OK;
+    const int N = 1;
+    const int* ch = kEncCh;
+    DFVO_TRY(enc.build(params, H, W, 3));
     // decoder (depth_decoder.py:29-47): ModuleList order (4,0),(4,1),(3,0),...,(0,1), dispconv 0..3
     const int dec[5] = {16, 32, 64, 128, 256};
     for (int i = 4; i >= 0; --i) {
@@ -748,15 +766,6 @@ int DepthNet::finalize() {
     dispconv.pad_mode = PAD_REFLECT;
     dispconv.act = ACT_SIGMOID;
     // buffers
-    DFVO_TRY(x0.alloc_zeroed((size_t)N * H * W * 4));
-    DFVO_TRY(feat[0].alloc_zeroed((size_t)N * (H / 2) * (W / 2) * 64));
-    DFVO_TRY(pool.alloc_zeroed((size_t)N * (H / 4) * (W / 4) * 64));
-    for (int i = 1; i < 5; ++i) DFVO_TRY(feat[i].alloc_zeroed((size_t)N * (H >> (i + 1)) * (W >> (i + 1)) * ch[i]));
-    const size_t big = (size_t)N * (H / 4) * (W / 4) * 64;  // every block tensor is <= this many floats
-    DFVO_TRY(blk_t.alloc_zeroed(big));
-    DFVO_TRY(blk_ds.alloc_zeroed(big));
-    DFVO_TRY(blk_o[0].alloc_zeroed(big));
-    DFVO_TRY(blk_o[1].alloc_zeroed(big));
     for (int i = 4; i >= 0; --i) {
         DFVO_TRY(du[i].alloc_zeroed((size_t)N * (H >> (i + 1)) * (W >> (i + 1)) * dec[i]));
         DFVO_TRY(dx[i].alloc_zeroed((size_t)N * (H >> i) * (W >> i) * dec[i]));
@@ -769,15 +778,14 @@ int DepthNet::finalize() {
     return DFVO_OK;
 }
 
-int DepthNet::enqueue(const uint8_t* d_img, float* d_depth) {
+int ResNetEncoder::enqueue(int H, int W, hipStream_t s, double* flops, const DevArr<float>* splitk_ws) const {
     const int N = 1;
-    hipStream_t s = stream;
-    double fl = 0.0;
     const View none{nullptr, 0, 0};
-    const int ch[5] = {64, 64, 128, 256, 512};
-    const int dec[5] = {16, 32, 64, 128, 256};
-    DFVO_TRY(launch_img_u8_to_depth_input(d_img, H, W, x0.p, s));
-    DFVO_TRY(run_conv(conv1, N, H, W, View{x0.p, 4, 0}, 0, none, nullptr, 0, 0, feat[0].p, 64, 0, 0, s, &fl, &splitk));
+    const int* ch = kEncCh;
+    const DevArr<float>& splitk = *splitk_ws;
+    double& fl = *flops;
+    DFVO_TRY(run_conv(conv1, N, H, W, View{x0.p, round_up(conv1.c0, 4), 0}, 0, none, nullptr, 0, 0, feat[0].p, 64, 0, 0, s, &fl,
+                      &splitk));
     DFVO_TRY(launch_maxpool3x3s2(feat[0].p, N, H / 2, W / 2, 64, pool.p, s));
     const float* x = pool.p;
     int hh = H / 4, ww = W / 4, c = 64;
@@ -802,6 +810,19 @@ int DepthNet::enqueue(const uint8_t* d_img, float* d_depth) {
             c = cout;
         }
     }
+    return DFVO_OK;
+}
+
+int DepthNet::enqueue(const uint8_t* d_img, float* d_depth) {
+    const int N = 1;
+    hipStream_t s = stream;
+    double fl = 0.0;
+    const View none{nullptr, 0, 0};
+    const int* ch = kEncCh;
+    const int dec[5] = {16, 32, 64, 128, 256};
+    const DevArr<float>* feat = enc.feat;
+    DFVO_TRY(launch_img_u8_to_depth_input(d_img, H, W, enc.x0.p, s));
+    DFVO_TRY(enc.enqueue(H, W, s, &fl, &splitk));
     // decoder
     const float* cur = feat[4].p;
     int cc = 512;
@@ -860,6 +881,99 @@ int DepthNet::forward(const uint8_t* d_img, float* d_depth) {
 }
 
 void DepthNet::destroy() {
+    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
+    if (graph) (void)hipGraphDestroy(graph);
+    graph_exec = nullptr;
+    graph = nullptr;
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+    stream = nullptr;
+}
+
+// ================================================================================================
+// monodepth2 pose net
+// ================================================================================================
+int PoseNet::init(int feedH, int feedW, hipStream_t s) {
+    H = feedH;
+    W = feedW;
+    DFVO_ARG_CHECK(H >= 32 && W >= 32 && H % 32 == 0 && W % 32 == 0, "PoseNet: feed size must be a multiple of 32");
+    if (s) {
+        stream = s;
+    } else {
+        DFVO_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        own_stream = true;
+    }
+    return DFVO_OK;
+}
+
+// (may be called again after a failed attempt, as FlowNet::finalize)
+int PoseNet::finalize() {
+    if (finalized) return DFVO_OK;
+    DFVO_TRY(enc.build(params, H, W, 6));
+    const long long M = (long long)(H / 32) * (W / 32);
+    // pose_decoder.py:26-29: squeeze 1x1, two 3x3 (zero padding), 1x1 to 6 values per predicted frame
+    const int cin[4] = {512, 256, 256, 256}, pad[4] = {0, 1, 1, 0};
+    for (int i = 0; i < 4; ++i) {
+        const std::string base = "net." + std::to_string(i);
+        DFVO_TRY(make_conv(params, base + ".weight", base + ".bias", cin[i], 0, M, nullptr, nullptr, &dec[i]));
+        DFVO_ARG_CHECK(dec[i].kh == 2 * pad[i] + 1 && dec[i].cout == (i == 3 ? 12 : 256), "PoseNet: unexpected decoder layer shape");
+        dec[i].stride = 1;
+        dec[i].pad_h = dec[i].pad_w = pad[i];
+        dec[i].act = i == 3 ? ACT_NONE : ACT_RELU;
+    }
+    DFVO_TRY(d0.alloc_zeroed((size_t)M * 256));
+    DFVO_TRY(d1.alloc_zeroed((size_t)M * 256));
+    DFVO_TRY(d2.alloc_zeroed((size_t)M * 256));
+    DFVO_TRY(d3.alloc_zeroed((size_t)M * 12));
+    DFVO_TRY(out.alloc_zeroed(24));
+    DFVO_TRY(splitk.alloc_zeroed((size_t)12 << 20));
+    DFVO_TRY(u8_in.alloc_zeroed(2 * u8_frame_floats()));
+    finalized = true;
+    return DFVO_OK;
+}
+
+int PoseNet::enqueue(const uint8_t* d_img0, const uint8_t* d_img1, float* d_pose16, float* d_params6) {
+    const int N = 1, h = H / 32, w = W / 32;
+    hipStream_t s = stream;
+    double fl = 0.0;
+    const View none{nullptr, 0, 0};
+    DFVO_TRY(launch_img2_u8_to_pose_input(d_img0, d_img1, H, W, enc.x0.p, s));
+    DFVO_TRY(enc.enqueue(H, W, s, &fl, &splitk));
+    DFVO_TRY(run_conv(dec[0], N, h, w, View{enc.feat[4].p, 512, 0}, 0, none, nullptr, 0, 0, d0.p, 256, 0, 0, s, &fl, &splitk));
+    DFVO_TRY(run_conv(dec[1], N, h, w, View{d0.p, 256, 0}, 0, none, nullptr, 0, 0, d1.p, 256, 0, 0, s, &fl, &splitk));
+    DFVO_TRY(run_conv(dec[2], N, h, w, View{d1.p, 256, 0}, 0, none, nullptr, 0, 0, d2.p, 256, 0, 0, s, &fl, &splitk));
+    DFVO_TRY(run_conv(dec[3], N, h, w, View{d2.p, 256, 0}, 0, none, nullptr, 0, 0, d3.p, 12, 0, 0, s, &fl, &splitk));
+    DFVO_TRY(launch_pose_head(d3.p, h, w, 12, baseline_mult, d_pose16, d_params6, s));
+    flops_last = fl;
+    return DFVO_OK;
+}
+
+int PoseNet::forward(const uint8_t* d_img0, const uint8_t* d_img1, float* d_pose16, float* d_params6) {
+    if (!finalized) {
+        set_last_error("PoseNet::forward before finalize");
+        return DFVO_ERR_STATE;
+    }
+    if (!tuned_once) {  // one eager run before any graph capture
+        DFVO_TRY(enqueue(d_img0, d_img1, d_pose16, d_params6));
+        DFVO_HIP_CHECK(hipStreamSynchronize(stream));
+        tuned_once = true;
+    }
+    if (!use_graph) return enqueue(d_img0, d_img1, d_pose16, d_params6);
+    // (the pointers are baked into the graph: recaptured when one changes)
+    if (graph_exec && graph_in0 == d_img0 && graph_in1 == d_img1 && graph_pose == d_pose16 && graph_params == d_params6) {
+        DFVO_HIP_CHECK(hipGraphLaunch(graph_exec, stream));
+        return DFVO_OK;
+    }
+    DFVO_TRY(enqueue(d_img0, d_img1, d_pose16, d_params6));
+    DFVO_HIP_CHECK(hipStreamSynchronize(stream));
+    DFVO_TRY(capture_graph(stream, &graph, &graph_exec, [&]() { return enqueue(d_img0, d_img1, d_pose16, d_params6); }));
+    graph_in0 = d_img0;
+    graph_in1 = d_img1;
+    graph_pose = d_pose16;
+    graph_params = d_params6;
+    return DFVO_OK;
+}
+
+void PoseNet::destroy() {
     if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
     if (graph) (void)hipGraphDestroy(graph);
     graph_exec = nullptr;

@@ -11,6 +11,13 @@ int launch_img_u8_to_flow_input(const uint8_t* img, int H, int W, float* dst, in
 // uint8 HWC RGB (already at feed size) -> float NHWC4, value = (float(u8)/255 - 0.45)/0.225
 // (ToTensor deep_models.py:199 + resnet_encoder.py:89).
 int launch_img_u8_to_depth_input(const uint8_t* img, int H, int W, float* dst, hipStream_t s);
+// two uint8 HWC RGB frames (at feed size) -> float NHWC8: image 0's RGB, image 1's RGB, two zero channels; values as above
+// (forward_pose, deep_models.py:217-225).  pose_ops.hip
+int launch_img2_u8_to_pose_input(const uint8_t* img0, const uint8_t* img1, int H, int W, float* dst, hipStream_t s);
+// PoseDecoder's tail + transformation_from_parameters(invert=True) + the baseline multiplier on the translation
+// (pose_decoder.py:47-52, monodepth2.py:97,118): map [h, w, cs] (12 channels used) -> pose16 (row-major 4x4) and, unless
+// null, params6 (frame 0's axis-angle and translation).  One workgroup.  pose_ops.hip
+int launch_pose_head(const float* map, int h, int w, int cs, float mult, float* pose16, float* params6, hipStream_t s);
 // generic NHWC bilinear resize (C multiple of 4, dense), torch F.interpolate semantics.
 int launch_resize_bilinear(const float* src, int N, int H, int W, int C, float* dst, int Ho, int Wo,
                            int align_corners, hipStream_t s);
@@ -61,6 +68,11 @@ int launch_disp_to_depth(const float* disp, int dcs, int dco, int n, float min_d
 // dfvo.py:314-319: nearest resize (cv2.INTER_NEAREST) to (H,W) -> raw f32 and preprocessed f64 map.
 int launch_depth_post(const float* depth, int h, int w, int H, int W, int y0, int y1, int x0, int x1,
                       float min_depth, float max_depth, float* raw, double* proc, hipStream_t s);
+// DepthConsistency.compute (depth_consistency.py:69-151, method depth_ratio): the current and the reference raw depth [H, W],
+// K / K^-1 (host, row-major 3x3) and the pose T (host, row-major 4x4, current -> reference) -> out [H, W] =
+// clamp(|warp - reproj| / reproj, 0, 1), NaN passed through.  cur and out 16-byte aligned.  depth_consistency.hip
+int launch_depth_consistency(const float* cur, const float* ref, int H, int W, const float* K9, const float* Kinv9, const float* T16,
+                             float* out, hipStream_t s);
 // read_depth (utils.py:55-73: uint16 / scale_factor, cv2.INTER_NEAREST to (H,W)) + preprocess_depth of an external 16-bit depth
 // image: raw = (float)(u16 / scale), proc = the float64 quotient inside the crop and strictly inside (min_depth, max_depth).
 int launch_read_depth_u16(const uint16_t* src, int h, int w, double scale, int H, int W, int y0, int y1, int x0, int x1,

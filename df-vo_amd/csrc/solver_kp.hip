@@ -259,7 +259,8 @@ __global__ __launch_bounds__(256) void k_kp_cell(const float* __restrict__ diff,
                                                   float thre, int n_best, int cap, int* __restrict__ cell_count,
                                                   int* __restrict__ cell_sel /*[cells][n_best] (y<<16|x)*/,
                                                   unsigned short* __restrict__ lidx_all /*[cells][cap]*/, int par,
-                                                  const float* __restrict__ mask_map, int* __restrict__ count_partial) {
+                                                  const float* __restrict__ mask_map, int* __restrict__ count_partial,
+                                                  const float* __restrict__ depth_diff /*nullable*/, float depth_thre) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     if ((int)blockIdx.x >= num_row * num_col) {
         __shared__ int s_cnt[4];
@@ -292,10 +293,14 @@ __global__ __launch_bounds__(256) void k_kp_cell(const float* __restrict__ diff,
     // round trips to memory in front of the selection of a KITTI-sized cell)
     constexpr int KB = 8;
     float vb[KB];
+    // depth_diff (kp_selection.depth_consistency, kp_selection.py:145-148): a candidate must also lie under depth_thre in
+    // that map -- bit u of dmask: element u of the batch does; the ranking key stays the score alone
+    unsigned dmask = ~0u;
     for (int c0 = 0; c0 < total; c0 += 256) {
         const int e = c0 + t;
         const int slot = (c0 / 256) % KB;
         if (slot == 0) {
+            if (depth_diff) dmask = 0u;
 #pragma unroll
             for (int u = 0; u < KB; ++u) {
                 const int eu = c0 + u * 256 + t;
@@ -303,6 +308,7 @@ __global__ __launch_bounds__(256) void k_kp_cell(const float* __restrict__ diff,
                 if (eu < total) {
                     const int ly = eu / tw, lx = eu - ly * tw;
                     vb[u] = diff[(size_t)(y0 + ly) * W + x0 + lx];
+                    if (depth_diff) dmask |= (depth_diff[(size_t)(y0 + ly) * W + x0 + lx] < depth_thre ? 1u : 0u) << u;
                 }
             }
         }
@@ -312,7 +318,7 @@ __global__ __launch_bounds__(256) void k_kp_cell(const float* __restrict__ diff,
             v = vb[0];
 #pragma unroll
             for (int u = 1; u < KB; ++u) v = slot == u ? vb[u] : v;
-            f = v < thre;
+            f = v < thre && ((dmask >> slot) & 1u);
         }
         const unsigned long long b = __ballot(f);
         const int before = __popcll(b & ((1ull << lane) - 1ull));
@@ -632,7 +638,8 @@ __global__ void k_flow_ratio(const float* __restrict__ flow, const float* __rest
 }
 
 int enqueue_local_bestn(TrackerBuffers& tb, const float* d_flow, const float* d_diff, int H, int W, int num_row,
-                        int num_col, int num_bestN, float thre, hipStream_t s, int score_method) {
+                        int num_col, int num_bestN, float thre, hipStream_t s, int score_method, const float* d_depth_diff,
+                        float depth_thre) {
     const int cells = num_row * num_col;
     DFVO_ARG_CHECK(cells > 0 && cells <= 1024 && H < 65536 && W < 65536, "local_bestN: grid too large");
     const int n_best = num_bestN / cells;  // math.floor(N / (rows*cols))
@@ -656,7 +663,7 @@ int enqueue_local_bestn(TrackerBuffers& tb, const float* d_flow, const float* d_
     }
     // (the counting blocks read the consistency map itself, whatever the cells rank: kp_selection.py:158)
     hipLaunchKernelGGL(k_kp_cell, dim3(cells + KP_CNT_BLOCKS), dim3(256), lds, s, d_key, H, W, num_row, num_col, thre, n_best, cap,
-                       tb.cell_count, tb.cell_sel, tb.lidx, par, d_diff, tb.kp_total + KPT_CELL_PARTIAL);
+                       tb.cell_count, tb.cell_sel, tb.lidx, par, d_diff, tb.kp_total + KPT_CELL_PARTIAL, d_depth_diff, depth_thre);
     // thresholds exactly as the python float comparisons: count < N*0.1 ; regions < rows*cols*0.1
     const int min_total = (int)ceil((double)num_bestN * 0.1);
     const int min_regions = (int)ceil((double)cells * 0.1);

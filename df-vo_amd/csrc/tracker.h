@@ -186,8 +186,10 @@ private:
 };
 
 // score_method: 0 'flow' (the consistency map itself), 1 'flow_ratio' (map / |flow|), kp_selection.py:137-141,151-156
+// d_depth_diff (kp_selection.depth_consistency, :145-148; null: off): a cell's candidates must also lie under depth_thre in it
 int enqueue_local_bestn(TrackerBuffers& tb, const float* d_flow, const float* d_diff, int H, int W, int num_row,
-                        int num_col, int num_bestN, float thre, hipStream_t s, int score_method = 0);
+                        int num_col, int num_bestN, float thre, hipStream_t s, int score_method = 0,
+                        const float* d_depth_diff = nullptr, float depth_thre = 0.f);
 // bestN_flow_kp (kp_selection.py:33-71): whole-image argpartition
 struct BestNBuffers {
     DevArr<float> key_base;      // keys carried along with the index array, with slack on either side

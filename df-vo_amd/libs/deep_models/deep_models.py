@@ -10,6 +10,7 @@ from ... import capi
 from ..tracker import _ctx
 from .depth.monodepth2.monodepth2 import Monodepth2DepthNet
 from .flow.lite_flow_net.lite_flow import LiteFlow
+from .pose.monodepth2.monodepth2 import Monodepth2PoseNet
 from .session import FrameSession
 
 
@@ -64,14 +65,17 @@ class DeepModel:
                     self.depth = self.initialize_deep_depth_model()
                 else:
                     assert False, "No precomputed depths nor pretrained depth model"
+            if self.cfg.deep_pose.enable:
+                if self.cfg.deep_pose.pretrained_model is not None:
+                    self.pose = self.initialize_deep_pose_model()
+                else:
+                    assert False, "No pretrained pose model"
         finally:
             capi.check(lib.dfvo_set_conv_precision(before))
             capi.check(lib.dfvo_set_fp32_winograd(wino_before))
         if self.conv_precision != "fp32":
             # weights beyond f16's range are clamped (and counted) by the packer: refuse them here, loudly
             capi.check_f16_range(seen, "the packed weights")
-        if self.cfg.deep_pose.enable:
-            raise NotImplementedError("deep_pose is 'Experiment Ver. only' in the reference; out of scope")
         if opts["session"] and getattr(self, "depth", None) is not None and isinstance(self.flow, LiteFlow):
             self.session = FrameSession(self.flow.model, self.depth.model, _ctx.tracker(), self.cfg.image.height,
                                         self.cfg.image.width, self.depth.feed_height, self.depth.feed_width)
@@ -141,10 +145,22 @@ class DeepModel:
         return out
 
     def initialize_deep_pose_model(self):
-        raise NotImplementedError("deep_pose is 'Experiment Ver. only' in the reference; out of scope")
+        """deep_models.py:104-117.  Packed in the conv precision in force (initialize_models sets it); the device net is built
+        for the size forward_pose feeds, which is the DEPTH net's feed size (deep_models.py:221)."""
+        net = Monodepth2PoseNet()
+        net.initialize_network_model(weight_path=self.cfg.deep_pose.pretrained_model,
+                                     dataset=self.cfg.dataset,
+                                     finetune=self.finetune_cfg.enable and self.finetune_cfg.pose.enable)
+        if getattr(self, "depth", None) is not None:
+            net._net(self.depth.feed_height, self.depth.feed_width)  # (nothing to do at the usual 192 x 640)
+        return net
 
     def forward_pose(self, imgs):
-        raise NotImplementedError("deep_pose is 'Experiment Ver. only' in the reference; out of scope")
+        """deep_models.py:208-230: two uint8 [H, W, 3] frames -> float32 [4, 4], the relative pose from imgs[1] to imgs[0].
+        Both frames are uploaded, resized (LANCZOS, Pillow's 8-bit arithmetic) to the depth net's feed size and run through
+        the pose net in one blocking call; the frame session is not involved."""
+        return self._in_range("the pose net", self.pose.inference_pose_images_u8, np.ascontiguousarray(imgs[0]),
+                              np.ascontiguousarray(imgs[1]), self.depth.feed_height, self.depth.feed_width)
 
     def finetune(self, img1, img2, pose, K, inv_K):
         raise NotImplementedError("online finetuning is training; out of scope of the inference hot path")

@@ -18,13 +18,18 @@ class KeypointSampler:
             self.kps['uniform'] = self.generate_kp_samples(img_h=self.cfg.image.height, img_w=self.cfg.image.width,
                                                            crop=self.cfg.crop.flow_crop, N=ks.sampled_kp.num_kp)
         if ks.local_bestN.enable and ks.local_bestN.score_method not in ("flow", "flow_ratio"):
-            raise NotImplementedError("local_bestN.score_method '%s' (flow_depth needs depth_consistency: Experiment Ver. only)"
-                                      % ks.local_bestN.score_method)
-        if ks.depth_consistency.enable:
-            raise NotImplementedError("depth_consistency is experiment-only in the reference (out of scope)")
-        # the frame session runs local_bestN behind the flow net with this configuration (libs/deep_models/session.py)
+            raise NotImplementedError(
+                "local_bestN.score_method '%s': 'flow_depth' does not run in the reference either -- kp_selection.py:135-143 defines "
+                "flow_mask for 'flow' and 'flow_ratio' only (an unbound name for any other method) and :193-199 leaves no fb_flow_mask"
+                % ks.local_bestN.score_method)
+        # kp_selection.depth_consistency (kp_selection.py:118-119,145-148): local_bestN masks its candidates with
+        # ref_data['depth_diff'] as well (libs/matching/depth_consistency.py writes it from the CNN depths and the CNN pose)
+        self._depth_mask = bool(ks.depth_consistency.enable) and bool(ks.local_bestN.enable)
+        # the frame session runs local_bestN behind the flow net with this configuration (libs/deep_models/session.py); with
+        # the depth mask there is none: the map needs the pose net's output, every call takes the plain entry point and the
+        # session speculates neither keypoints nor the pose half behind them
         self._session_kp_cfg = None
-        if ks.local_bestN.enable:
+        if ks.local_bestN.enable and not self._depth_mask:
             c = ks.local_bestN
             self._session_kp_cfg = capi.SessionKpCfg(num_row=int(c.num_row), num_col=int(c.num_col), num_bestN=int(c.num_bestN),
                                                      thre=float(c.thre), score_method={"flow": 0, "flow_ratio": 1}[c.score_method])
@@ -112,9 +117,18 @@ class KeypointSampler:
         kp2 = np.zeros((nmax, 2))
         n, good = C.c_int(), C.c_int()
         score = {"flow": 0, "flow_ratio": 1}[c.score_method]
-        capi.check(capi.lib().dfvo_kp_local_bestn_ex(_ctx.tracker_exclusive(), capi.as_ptr(flow), capi.as_ptr(diff.reshape(h, w)), h,
-                                                     w, int(c.num_row), int(c.num_col), nmax, float(c.thre), score,
-                                                     capi.as_ptr(kp1), capi.as_ptr(kp2), C.byref(n), C.byref(good)))
+        if self._depth_mask:
+            if s is not None:
+                s.stats["kp_plain"] += 1
+            ddiff = np.ascontiguousarray(ref_data['depth_diff'], dtype=np.float32).reshape(h, w)
+            capi.check(capi.lib().dfvo_kp_local_bestn_depth(
+                _ctx.tracker_exclusive(), capi.as_ptr(flow), capi.as_ptr(diff.reshape(h, w)), capi.as_ptr(ddiff), h, w, int(c.num_row),
+                int(c.num_col), nmax, float(c.thre), float(self.cfg.kp_selection.depth_consistency.thre), score, capi.as_ptr(kp1),
+                capi.as_ptr(kp2), C.byref(n), C.byref(good)))
+        else:
+            capi.check(capi.lib().dfvo_kp_local_bestn_ex(_ctx.tracker_exclusive(), capi.as_ptr(flow), capi.as_ptr(diff.reshape(h, w)),
+                                                         h, w, int(c.num_row), int(c.num_col), nmax, float(c.thre), score,
+                                                         capi.as_ptr(kp1), capi.as_ptr(kp2), C.byref(n), C.byref(good)))
         if not good.value:
             print("Cannot find enough good keypoints!")
             outputs['good_kp_found'] = False

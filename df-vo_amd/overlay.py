@@ -30,6 +30,7 @@ PKG = __name__.rsplit(".", 1)[0]
 _MAP = {
     "libs.deep_models.deep_models": ".libs.deep_models.deep_models",
     "libs.matching.keypoint_sampler": ".libs.matching.keypoint_sampler",
+    "libs.matching.depth_consistency": ".libs.matching.depth_consistency",
     "libs.tracker": ".libs.tracker",
     "libs.tracker.E_tracker": ".libs.tracker.E_tracker",
     "libs.tracker.pnp_tracker": ".libs.tracker.pnp_tracker",

@@ -119,6 +119,18 @@ def monodepth2_state_dict(seed=4869):
     return sd
 
 
+def posenet_state_dict(seed=4869):
+    """monodepth2's pose net: the ResNet18 encoder over two concatenated frames ('encoder.*' as in pose_encoder.pth,
+    conv1 [64, 6, 7, 7]) + PoseDecoder ('net.0' .. 'net.3' as in pose.pth), seeded like monodepth2_state_dict."""
+    sd = {k: v for k, v in monodepth2_state_dict(seed + 17).items() if k.startswith('encoder.')}
+    g = torch.Generator().manual_seed(seed + 2)
+    sd['encoder.conv1.weight'] = torch.randn(64, 6, 7, 7, generator=g) * math.sqrt(2.0 / (6 * 49))
+    for i, (cout, cin, k) in enumerate([(256, 512, 1), (256, 256, 3), (256, 256, 3), (12, 256, 1)]):
+        sd['net.%d.weight' % i] = torch.randn(cout, cin, k, k, generator=g) * math.sqrt(2.0 / (cin * k * k))
+        sd['net.%d.bias' % i] = torch.randn(cout, generator=g) * 0.01
+    return sd
+
+
 def smooth_noise(rng, h, w, sigmas=(2, 4, 8, 16)):
     from scipy.ndimage import gaussian_filter
     acc = np.zeros((h, w, 3))

@@ -240,6 +240,32 @@ int dfvo_depthnet_forward_host(dfvo_depthnet* net, const uint8_t* h_img, float* 
 int dfvo_depthnet_forward_image_host(dfvo_depthnet* net, const uint8_t* h_img, int img_h, int img_w, float* h_depth);
 double dfvo_depthnet_last_flops(const dfvo_depthnet* net);
 int dfvo_depthnet_sync(dfvo_depthnet* net);
+
+/* =====================================================================================
+ * monodepth2 two-frame pose net  (replaces Monodepth2PoseNet.inference / inference_pose,
+ * pose/monodepth2/monodepth2.py:86-119, behind DeepModel.forward_pose, deep_models.py:208-230)
+ * ResnetEncoder(18, False, 2) + PoseDecoder(num_ch_enc, 1, 2) + transformation_from_parameters(invert=True);
+ * packed in the conv precision in force at dfvo_posenet_finalize, like the other nets.
+ * ===================================================================================== */
+typedef struct dfvo_posenet dfvo_posenet;
+/* feed size: multiples of 32; baseline_mult multiplies the translation column (stereo_baseline_multiplier) */
+int dfvo_posenet_create(int feed_h, int feed_w, float baseline_mult, void* stream, dfvo_posenet** out);
+void dfvo_posenet_destroy(dfvo_posenet* net);
+/* keys of pose_encoder.pth ("encoder.conv1.weight" [64,6,7,7], ...) and pose.pth ("net.0.weight", ... "net.3.bias") */
+int dfvo_posenet_set_param(dfvo_posenet* net, const char* name, const float* h_data, int ndim, const int* shape);
+int dfvo_posenet_finalize(dfvo_posenet* net);
+int dfvo_posenet_set_graph(dfvo_posenet* net, int enable);
+/* two device images uint8 [feed_h, feed_w, 3] (channel order of the net input: image 0's RGB, then image 1's) ->
+ * d_pose16: row-major float 4x4, the relative pose from image 1 to image 0, translation x baseline_mult;
+ * d_params6 (may be NULL): frame 0's raw axis-angle (3) and translation (3), before the multiplier.
+ * Asynchronous on the net's stream (dfvo_posenet_sync). */
+int dfvo_posenet_forward(dfvo_posenet* net, const uint8_t* d_img0, const uint8_t* d_img1, float* d_pose16, float* d_params6);
+/* DeepModel.forward_pose in one blocking call: two host uint8 images [img_h,img_w,3] -> Pillow-exact LANCZOS resize of
+ * each to the feed size on the device -> net -> host float[16] */
+int dfvo_posenet_forward_images_host(dfvo_posenet* net, const uint8_t* h_img0, const uint8_t* h_img1, int img_h, int img_w,
+                                     float* h_pose16);
+double dfvo_posenet_last_flops(const dfvo_posenet* net);
+int dfvo_posenet_sync(dfvo_posenet* net);
 /* dfvo.py:314-319 + utils.py:89-114: nearest resize to (H,W), crop rows/cols, range mask.
  * d_depth float [h,w] -> d_raw float [H,W], d_proc double [H,W].  The resize is cv2.resize's INTER_NEAREST: source column
  * min(floor(x * (1.0 / ((double)W / w))), w - 1), rows alike.  d_raw holds the resized map bit for bit; d_proc is
@@ -260,6 +286,18 @@ int dfvo_depth_postprocess(const float* d_depth, int h, int w, int H, int W, int
  * Asynchronous on `stream`. */
 int dfvo_read_depth_u16(const uint16_t* d_src_u16, int src_h, int src_w, double scale, int H, int W, int y0, int y1, int x0,
                         int x1, double min_depth, double max_depth, float* d_raw_f32, double* d_proc_f64, void* stream);
+/* kp_selection.depth_consistency (DepthConsistency.warp_and_reproj_depth + compute_depth_diff, method depth_ratio,
+ * libs/matching/depth_consistency.py:69-151) in one launch, float32 per pixel:
+ *   P = K^-1 (x, y, 1) d_cur;  P' = T[:3, :] (P, 1);  reproj = P'_z;  pixel = (K P')_xy / ((K P')_z + 1e-7), normalised
+ *   /(W - 1), /(H - 1), (. - 0.5) * 2;  warp = bilinear sample of d_ref at it, border padding, corners aligned (torch 1.1's
+ *   grid_sample);  out = clamp(|warp - reproj| / reproj, 0, 1) -- a NaN stays a NaN, as torch.clamp leaves it.
+ * d_cur_depth / d_ref_depth: the raw depths of the current and the reference frame, float [H,W]; h_K, h_Kinv: host float[9],
+ * row-major; h_T: host float[16], row-major, the pose from the current to the reference frame (DeepModel.forward_pose).
+ * d_cur_depth and d_out 16-byte aligned, H, W >= 2.  Asynchronous on `stream`; _host is the blocking host-array form. */
+int dfvo_depth_consistency(const float* d_cur_depth, const float* d_ref_depth, int H, int W, const float* h_K, const float* h_Kinv,
+                           const float* h_T, float* d_out, void* stream);
+int dfvo_depth_consistency_host(const float* h_cur_depth, const float* h_ref_depth, int H, int W, const float* h_K,
+                                const float* h_Kinv, const float* h_T, float* h_out);
 
 /* =====================================================================================
  * Pose solvers (wavefront-parallel RANSAC, f64).  Host arrays in / out, synchronous: these are the
@@ -317,6 +355,13 @@ int dfvo_kp_local_bestn(dfvo_tracker* trk, const float* h_flow, const float* h_d
 int dfvo_kp_local_bestn_ex(dfvo_tracker* trk, const float* h_flow, const float* h_diff, int H, int W, int num_row,
                            int num_col, int num_bestN, float thre, int score_method, double* h_kp1, double* h_kp2,
                            int* n_out, int* good_kp_found);
+/* same with kp_selection.depth_consistency.enable (kp_selection.py:118-119,145-148): h_depth_diff float [H,W] is
+ * ref_data['depth_diff'] (dfvo_depth_consistency); a cell's candidates are the pixels with score < thre AND depth_diff <
+ * depth_thre (a NaN in either map fails its comparison).  The ranking key is the score alone, the "enough good pixels" rule
+ * stays on h_diff alone, the order is numpy's over the masked candidates. */
+int dfvo_kp_local_bestn_depth(dfvo_tracker* trk, const float* h_flow, const float* h_diff, const float* h_depth_diff, int H,
+                              int W, int num_row, int num_col, int num_bestN, float thre, float depth_thre, int score_method,
+                              double* h_kp1, double* h_kp2, int* n_out, int* good_kp_found);
 /* bestN_flow_kp (kp_selection.py:33-71, ablation_correspondences_best_n.yml): the num_bestN pixels of the whole image
  * with the least forward-backward inconsistency, in np.argpartition(flow_diff[flow_diff >= 0], num_bestN)[:num_bestN]
  * order (numpy's scalar introselect).  *n_out = num_bestN, or 0 when the image has no more than num_bestN candidates
