@@ -98,6 +98,10 @@ class PipelineDepthSrc(C.Structure):
     _fields_ = [("source", C.c_int), ("scale", C.c_double), ("src_h", C.c_int), ("src_w", C.c_int)]
 
 
+class PipelinePoseOpts(C.Structure):
+    _fields_ = [("enable", C.c_int), ("depth_consistency", C.c_int), ("depth_thre", C.c_float)]
+
+
 class TrackOut(C.Structure):
     _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("scale", C.c_double), ("status", C.c_int),
                 ("n_kp", C.c_int), ("good_kp_found", C.c_int), ("best_inlier_cnt", C.c_int), ("num_valid", C.c_int),
@@ -226,6 +230,7 @@ SIGNATURES = {
     "dfvo_posenet_sync": (_i, [_vp]),
     "dfvo_depth_postprocess": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
     "dfvo_depth_consistency": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dfvo_depth_consistency_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dfvo_depth_consistency_host": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "dfvo_read_depth_u16": (_i, [_vp, _i, _i, _d, _i, _i, _i, _i, _i, _i, _d, _d, _vp, _vp, _vp]),
     "dfvo_tracker_create": (_i, [_vp, C.POINTER(_vp)]),
@@ -252,6 +257,10 @@ SIGNATURES = {
     "dfvo_pipeline_seed": (_i, [_vp, C.c_uint32]),
     "dfvo_pipeline_set_options": (_i, [_vp, C.POINTER(PipelineOpts)]),
     "dfvo_pipeline_set_graph": (_i, [_vp, _i]),
+    "dfvo_pipeline_set_pose_param": (_i, [_vp, C.c_char_p, _vp, _i, _ip]),
+    "dfvo_pipeline_set_pose_net": (_i, [_vp, C.POINTER(PipelinePoseOpts)]),
+    "dfvo_pipeline_set_pose_override": (_i, [_vp, _i, _vp]),
+    "dfvo_pipeline_get_pose_net": (_i, [_vp, _i, _vp, _vp]),
     "dfvo_pipeline_set_iterative": (_i, [_vp, C.POINTER(PipelineIterOpts)]),
     "dfvo_pipeline_get_prev_scale": (_i, [_vp, C.POINTER(_d)]),
     "dfvo_pipeline_set_prev_scale": (_i, [_vp, _d]),

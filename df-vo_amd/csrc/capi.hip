@@ -554,6 +554,10 @@ int dfvo_depth_consistency(const float* d_cur_depth, const float* d_ref_depth, i
                            const float* h_T, float* d_out, void* stream) {
     return launch_depth_consistency(d_cur_depth, d_ref_depth, H, W, h_K, h_Kinv, h_T, d_out, (hipStream_t)stream);
 }
+int dfvo_depth_consistency_dev(const float* d_cur_depth, const float* d_ref_depth, int H, int W, const float* h_K, const float* h_Kinv,
+                               const float* d_T16, float* d_out, void* stream) {
+    return launch_depth_consistency_dev(d_cur_depth, d_ref_depth, H, W, h_K, h_Kinv, d_T16, d_out, (hipStream_t)stream);
+}
 int dfvo_depth_consistency_host(const float* h_cur_depth, const float* h_ref_depth, int H, int W, const float* h_K, const float* h_Kinv,
                                 const float* h_T, float* h_out) {
     DFVO_ARG_CHECK(h_cur_depth && h_ref_depth && h_out && H >= 2 && W >= 2, "dfvo_depth_consistency_host: bad argument");

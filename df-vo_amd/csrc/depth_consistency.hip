@@ -83,6 +83,62 @@ __global__ void __launch_bounds__(256) k_depth_consistency(const float* __restri
     }
 }
 
+// The same lanes and stores with the pose in device memory (PoseNet's 4x4, written by k_pose_head earlier on the stream).  Every
+// workgroup assembles the camera in LDS -- K and K^-1 from the kernel argument, whose T comes in unset, and the twelve pose values
+// from T16 -- and every lane copies that struct whole before it does anything else.  The pose is another kernel's output and no
+// launch constant: twelve lanes read it with relaxed atomic loads, which the compiler lowers to per-lane vector loads of global
+// memory and never to the scalar-cache loads it selects for a uniform address behind a plain or `const __restrict__` pointer.
+// The whole-struct copy is what keeps the arithmetic that of k_depth_consistency: under -ffp-contract=fast the compiler decides
+// which product of a sum goes into an fma from how it packs the operands, and it packs a camera it copied as one aggregate as it
+// packs the kernel argument, but not one whose T was assigned element by element (measured: identical on every pixel against
+// one pixel in five off by an ulp or two; tests/test_pipeline_posenet_gpu.py holds it bit for bit).
+__global__ void __launch_bounds__(256) k_depth_consistency_dev(const float* __restrict__ cur, const float* __restrict__ ref, int H, int W,
+                                                               int G, DcCam cam, const float* T16, float* __restrict__ out) {
+    __shared__ DcCam sc;
+    if (threadIdx.x < 12)
+        sc.T[threadIdx.x] = __hip_atomic_load(T16 + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else if (threadIdx.x < 21)
+        sc.K[threadIdx.x - 12] = cam.K[threadIdx.x - 12];
+    else if (threadIdx.x < 30)
+        sc.Kinv[threadIdx.x - 21] = cam.Kinv[threadIdx.x - 21];
+    __syncthreads();  // (ahead of every return: all 256 lanes of the workgroup reach it)
+    const DcCam c = sc;
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long long)H * G) return;
+    const int y = (int)(t / G), g = (int)(t - (long long)y * G);
+    const long long r0 = (long long)y * W;
+    const long long q0 = ((r0 >> 2) + g) << 2;
+    const long long lo = q0 > r0 ? q0 : r0, hi = q0 + 4 < r0 + W ? q0 + 4 : r0 + W;
+    if (lo >= hi) return;
+    const int n = (int)(hi - lo), xa = (int)(lo - r0);
+    if (n == 4) {
+        const DcF4 d = *reinterpret_cast<const DcF4*>(cur + lo);
+        DcF4 o;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o.v[i] = dc_pixel(c, ref, H, W, xa + i, y, d.v[i]);
+        *reinterpret_cast<DcF4*>(out + lo) = o;
+    } else {
+        for (int i = 0; i < n; ++i) out[lo + i] = dc_pixel(c, ref, H, W, xa + i, y, cur[lo + i]);
+    }
+}
+
+int launch_depth_consistency_dev(const float* cur, const float* ref, int H, int W, const float* K9, const float* Kinv9,
+                                 const float* d_T16, float* out, hipStream_t s) {
+    DFVO_ARG_CHECK(cur && ref && out && K9 && Kinv9 && d_T16, "depth_consistency_dev: null argument");
+    DFVO_ARG_CHECK(H >= 2 && W >= 2 && (long long)H * W < (1ll << 31), "depth_consistency_dev: the map must be at least 2 x 2");
+    DFVO_ARG_CHECK(((uintptr_t)cur & 15) == 0 && ((uintptr_t)out & 15) == 0, "depth_consistency_dev: maps must be 16-byte aligned");
+    DFVO_ARG_CHECK(((uintptr_t)d_T16 & 3) == 0, "depth_consistency_dev: the pose must be 4-byte aligned");
+    DcCam cam;
+    for (int i = 0; i < 9; ++i) cam.K[i] = K9[i], cam.Kinv[i] = Kinv9[i];
+    for (int i = 0; i < 12; ++i) cam.T[i] = 0.f;
+    const int G = (W + 3) / 4 + 1;
+    const long long lanes = (long long)H * G;
+    hipLaunchKernelGGL(k_depth_consistency_dev, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, cur, ref, H, W, G, cam, d_T16,
+                       out);
+    DFVO_HIP_CHECK(hipGetLastError());
+    return DFVO_OK;
+}
+
 int launch_depth_consistency(const float* cur, const float* ref, int H, int W, const float* K9, const float* Kinv9, const float* T16,
                              float* out, hipStream_t s) {
     DFVO_ARG_CHECK(cur && ref && out && K9 && Kinv9 && T16, "depth_consistency: null argument");

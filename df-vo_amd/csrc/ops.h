@@ -73,6 +73,10 @@ int launch_depth_post(const float* depth, int h, int w, int H, int W, int y0, in
 // clamp(|warp - reproj| / reproj, 0, 1), NaN passed through.  cur and out 16-byte aligned.  depth_consistency.hip
 int launch_depth_consistency(const float* cur, const float* ref, int H, int W, const float* K9, const float* Kinv9, const float* T16,
                              float* out, hipStream_t s);
+// the same map with the pose in device memory (d_T16: row-major 4x4 float, 4-byte aligned, as PoseNet / k_pose_head leave it --
+// read by the kernel in stream order, never by the host): bit-identical to launch_depth_consistency for the same 16 floats
+int launch_depth_consistency_dev(const float* cur, const float* ref, int H, int W, const float* K9, const float* Kinv9,
+                                 const float* d_T16, float* out, hipStream_t s);
 // read_depth (utils.py:55-73: uint16 / scale_factor, cv2.INTER_NEAREST to (H,W)) + preprocess_depth of an external 16-bit depth
 // image: raw = (float)(u16 / scale), proc = the float64 quotient inside the crop and strictly inside (min_depth, max_depth).
 int launch_read_depth_u16(const uint16_t* src, int h, int w, double scale, int H, int W, int y0, int y1, int x0, int x1,

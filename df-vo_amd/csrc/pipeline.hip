@@ -6,7 +6,8 @@
 // dfvo_pipeline_set_options selects the keypoint source (local_bestN | bestN | sampled), the validity and scale-RANSAC methods
 // and hybrid | PnP-only tracking; dfvo_pipeline_set_iterative puts scale_recovery.method "iterative" (the one-call device loop
 // of solver_scale.hip) in the place of find_scale_from_depth; dfvo_pipeline_set_depth_source puts a 16-bit depth image per
-// frame (depth.depth_src gt, dfvo.py:296-319) in the place of the depth net; without them the pipeline runs
+// frame (depth.depth_src gt, dfvo.py:296-319) in the place of the depth net; dfvo_pipeline_set_pose_net adds the pose lane
+// (monodepth2's pose net, the depth-consistency keypoint mask, tracking_method deep_pose); without them the pipeline runs
 // default_configuration.yml.
 #include "../../include/dfvo_hip.h"
 #include <algorithm>
@@ -15,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "nets.h"
@@ -70,6 +72,11 @@ struct Slot {
     // outputs of the nets
     DevArr<float> fwd, bwd, diff, raw_depth;
     DevArr<double> proc_depth;
+    // dfvo_pipeline_set_pose_net: the 4x4 the slot's pair uses (the net's, or the override's copy), the depth-difference map of
+    // the mask, the caller's pose for the next pair enqueued here (until track_end), deep_pose tracking's pinned result
+    DevArr<float> pose16, depth_diff;
+    const float* pose_override = nullptr;
+    PinnedArr<float> h_pose;
 };
 
 struct dfvo_pipeline {
@@ -107,6 +114,17 @@ struct dfvo_pipeline {
     dfvo_pipeline_opts opts = {};
     // dfvo_pipeline_set_depth_source: all zero = the depth net; EXTERNAL = 16-bit depth images (depth.depth_src gt), no depth net
     dfvo_pipeline_depth_src dsrc = {};
+    // dfvo_pipeline_set_pose_net: all zero = no pose lane.  The net replays a captured graph, so its addresses are fixed: two
+    // staging frames (pose_feed: reference | current, the current copied to the reference's behind the net) and one output
+    // (pose_out, copied into the slot).  pose_ref_raw: the reference frame's raw depth as the NEXT pair's mask reads it -- the
+    // raw depth of the slot the last enqueue_nets* call filled, or ref_raw after a set_ref_* call (null: neither came yet)
+    dfvo_pipeline_pose_opts pose = {};
+    PoseNet pose_net;
+    DevArr<uint8_t> pose_feed;
+    size_t pose_feed_pitch = 0;
+    DevArr<float> pose_out;
+    bool pose_ref_feed = false;  // pose_feed's reference half holds the previous call's current feed
+    const float* pose_ref_raw = nullptr;
     bool started = false;                   // a pair or a reference depth was enqueued: the options are final
     DevArr<int> d_samples;                  // kp_source sampled: generate_kp_samples' index list, uploaded once
     int sample_crop[4] = {0, 0, 0, 0};      // y0 y1 x0 x1 [px] of cfg.crop.flow_crop
@@ -330,11 +348,22 @@ int dfvo_pipeline_set_depth_param(dfvo_pipeline* p, const char* name, const floa
     DFVO_ARG_CHECK(p && !p->nets_ready, "dfvo_pipeline_set_depth_param: bad state");
     return pipe_store(&p->depth.params, name, h, ndim, shape);
 }
+int dfvo_pipeline_set_pose_param(dfvo_pipeline* p, const char* name, const float* h, int ndim, const int* shape) {
+    DFVO_ARG_CHECK(p && !p->pose_net.finalized, "dfvo_pipeline_set_pose_param: bad state");
+    return pipe_store(&p->pose_net.params, name, h, ndim, shape);
+}
+// the pose net on the depth stream (stream order is the whole synchronisation of the pose lane), built once
+static int finalize_pose_net(dfvo_pipeline* p) {
+    if (!p->pose_net.stream) P_TRY(p->pose_net.init(p->feedH, p->feedW, p->s_depth));
+    p->pose_net.baseline_mult = p->cfg.baseline_mult;
+    return p->pose_net.finalize();
+}
 int dfvo_pipeline_finalize(dfvo_pipeline* p) {
     DFVO_ARG_CHECK(p, "null pipeline");
     P_TRY(p->flow.finalize());
     for (int i = 0; i + 1 < p->flow_instances; ++i) P_TRY(p->flow_x[i].finalize());
     if (p->dsrc.source != DFVO_DEPTH_EXTERNAL) P_TRY(p->depth.finalize());  // (external depth: no parameters, no graph)
+    if (p->pose.enable) P_TRY(finalize_pose_net(p));
     p->nets_ready = true;
     return DFVO_OK;
 }
@@ -343,6 +372,57 @@ int dfvo_pipeline_set_graph(dfvo_pipeline* p, int enable) {
     p->flow.use_graph = enable != 0;
     for (int i = 0; i + 1 < p->flow_instances; ++i) p->flow_x[i].use_graph = enable != 0;
     p->depth.use_graph = enable != 0;
+    p->pose_net.use_graph = enable != 0;
+    return DFVO_OK;
+}
+
+int dfvo_pipeline_set_pose_net(dfvo_pipeline* p, const dfvo_pipeline_pose_opts* o) {
+    DFVO_ARG_CHECK(p && o, "dfvo_pipeline_set_pose_net: null argument");
+    DFVO_ARG_CHECK(!p->started, "dfvo_pipeline_set_pose_net: comes before the first dfvo_pipeline_enqueue_nets / _set_ref_*");
+    const bool deep = p->opts.tracking_method == DFVO_TRACKING_DEEP_POSE;
+    if (!o->enable) {
+        DFVO_ARG_CHECK(!o->depth_consistency, "dfvo_pipeline_set_pose_net: depth_consistency needs enable (the mask reads the net's pose)");
+        DFVO_ARG_CHECK(!deep, "dfvo_pipeline_set_pose_net: tracking_method DFVO_TRACKING_DEEP_POSE needs the pose net");
+        p->pose = {};
+        return DFVO_OK;
+    }
+    if (o->depth_consistency) {
+        DFVO_ARG_CHECK(p->opts.kp_source == DFVO_KP_SOURCE_LOCAL_BESTN,
+                       "dfvo_pipeline_set_pose_net: depth_consistency masks kp_source DFVO_KP_SOURCE_LOCAL_BESTN only (kp_selection.py:118-148)");
+        DFVO_ARG_CHECK(!deep, "dfvo_pipeline_set_pose_net: depth_consistency under tracking_method DFVO_TRACKING_DEEP_POSE: nothing "
+                              "selects keypoints");
+        DFVO_ARG_CHECK(o->depth_thre == o->depth_thre, "dfvo_pipeline_set_pose_net: depth_thre is NaN");
+    }
+    // every buffer of the lane at its final size, here: nothing on the per-pair path allocates
+    const size_t px = (size_t)p->H * p->W;
+    p->pose_feed_pitch = ((size_t)p->feedH * p->feedW * 3 + 15) / 16 * 16;
+    if (!p->pose_feed && p->pose_feed.alloc_zeroed(2 * p->pose_feed_pitch)) return DFVO_ERR_HIP;
+    if (!p->pose_out && p->pose_out.alloc_zeroed(16)) return DFVO_ERR_HIP;
+    for (Slot& sl : p->slots) {
+        if (!sl.pose16 && sl.pose16.alloc_zeroed(16)) return DFVO_ERR_HIP;
+        if (!sl.h_pose && sl.h_pose.alloc(16)) return DFVO_ERR_HIP;
+        if (o->depth_consistency && !sl.depth_diff && sl.depth_diff.alloc_zeroed(px)) return DFVO_ERR_HIP;
+    }
+    if (p->nets_ready) P_TRY(finalize_pose_net(p));
+    p->pose = *o;
+    return DFVO_OK;
+}
+
+int dfvo_pipeline_set_pose_override(dfvo_pipeline* p, int slot, const float* d_pose16) {
+    DFVO_ARG_CHECK(p && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS), "dfvo_pipeline_set_pose_override: bad argument");
+    DFVO_ARG_CHECK(p->pose.enable, "dfvo_pipeline_set_pose_override: the pose net is not on (dfvo_pipeline_set_pose_net)");
+    p->slots[slot].pose_override = d_pose16;
+    return DFVO_OK;
+}
+
+int dfvo_pipeline_get_pose_net(dfvo_pipeline* p, int slot, float* h_pose16, float* h_depth_diff) {
+    DFVO_ARG_CHECK(p && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS), "dfvo_pipeline_get_pose_net: bad argument");
+    DFVO_ARG_CHECK(p->pose.enable, "dfvo_pipeline_get_pose_net: the pose net is not on (dfvo_pipeline_set_pose_net)");
+    DFVO_ARG_CHECK(!h_depth_diff || p->pose.depth_consistency, "dfvo_pipeline_get_pose_net: no depth-difference map without depth_consistency");
+    const Slot& sl = p->slots[slot];
+    DFVO_HIP_CHECK(hipDeviceSynchronize());
+    if (h_pose16) DFVO_HIP_CHECK(hipMemcpy(h_pose16, sl.pose16, 16 * sizeof(float), hipMemcpyDeviceToHost));
+    if (h_depth_diff) DFVO_HIP_CHECK(hipMemcpy(h_depth_diff, sl.depth_diff, (size_t)p->H * p->W * sizeof(float), hipMemcpyDeviceToHost));
     return DFVO_OK;
 }
 int dfvo_pipeline_seed(dfvo_pipeline* p, uint32_t seed) {
@@ -367,8 +447,13 @@ int dfvo_pipeline_set_options(dfvo_pipeline* p, const dfvo_pipeline_opts* o) {
                    "dfvo_pipeline_set_options: validity_thre is NaN");
     DFVO_ARG_CHECK(o->scale_method == DFVO_SCALE_DEPTH_RATIO || o->scale_method == DFVO_SCALE_ABS_DIFF,
                    "dfvo_pipeline_set_options: scale_method is DFVO_SCALE_DEPTH_RATIO or DFVO_SCALE_ABS_DIFF");
-    DFVO_ARG_CHECK(o->tracking_method == DFVO_TRACKING_HYBRID || o->tracking_method == DFVO_TRACKING_PNP,
-                   "dfvo_pipeline_set_options: tracking_method is DFVO_TRACKING_HYBRID or DFVO_TRACKING_PNP");
+    DFVO_ARG_CHECK(o->tracking_method == DFVO_TRACKING_HYBRID || o->tracking_method == DFVO_TRACKING_PNP ||
+                       (o->tracking_method == DFVO_TRACKING_DEEP_POSE && p->pose.enable && !p->pose.depth_consistency),
+                   "dfvo_pipeline_set_options: tracking_method is DFVO_TRACKING_HYBRID, DFVO_TRACKING_PNP or, behind "
+                   "dfvo_pipeline_set_pose_net with enable and without depth_consistency, DFVO_TRACKING_DEEP_POSE");
+    DFVO_ARG_CHECK(!p->pose.depth_consistency || o->kp_source == DFVO_KP_SOURCE_LOCAL_BESTN,
+                   "dfvo_pipeline_set_options: kp_source with dfvo_pipeline_set_pose_net's depth_consistency is DFVO_KP_SOURCE_LOCAL_BESTN, "
+                   "the only source the reference masks");
     const dfvo_pipeline_cfg& c = p->cfg;
     // every buffer the chosen source needs at its final size, here: nothing on the per-pair path allocates (hipFree waits
     // for the whole device).  kp_count stays 0 for local_bestN, whose launcher sizes its own buffers as before
@@ -507,16 +592,85 @@ static int enqueue_read_depth(dfvo_pipeline* p, const uint16_t* d_u16, float* ra
 
 static int enqueue_flow_half(dfvo_pipeline* p, int slot, const uint8_t* d_ref, const uint8_t* d_cur);
 
+static bool deep_pose_tracking(const dfvo_pipeline* p) { return p->opts.tracking_method == DFVO_TRACKING_DEEP_POSE; }
+
+// what a pair's pose lane needs from earlier calls, checked before anything of the pair is enqueued
+static int check_pose_lane(const dfvo_pipeline* p, const uint8_t* d_ref, const char* who) {
+    if (!d_ref && !p->pose_ref_feed) {
+        dfvo::set_last_error(std::string(who) + ": d_ref == NULL (reference frame = the previous call's current frame) needs a previous call");
+        return DFVO_ERR_ARG;
+    }
+    if (p->pose.depth_consistency && !p->pose_ref_raw) {
+        dfvo::set_last_error(std::string(who) + ": the depth-consistency mask needs the reference frame's raw depth: "
+                             "dfvo_pipeline_set_ref_image / _set_ref_depth (d_feed) / _set_ref_depth_u16 / _set_ref_raw_depth first");
+        return DFVO_ERR_ARG;
+    }
+    return DFVO_OK;
+}
+
+// A pair enqueued into the slot the previous pair used: the slot's raw depth is the mask's reference depth and is about to be
+// overwritten with the current frame's, so it moves to ref_raw first (on the depth stream, behind a pending roll-over, which is
+// ref_raw's other writer)
+static int keep_ref_raw(dfvo_pipeline* p, Slot& sl) {
+    if (!p->pose.depth_consistency || p->pose_ref_raw != sl.raw_depth.p) return DFVO_OK;
+    if (p->roll_pending) DFVO_HIP_CHECK(hipStreamWaitEvent(p->s_depth, p->e_roll, 0));
+    DFVO_HIP_CHECK(hipMemcpyAsync(p->ref_raw, sl.raw_depth, (size_t)p->H * p->W * sizeof(float), hipMemcpyDeviceToDevice, p->s_depth));
+    p->pose_ref_raw = p->ref_raw.p;
+    return DFVO_OK;
+}
+
+// The pose lane of a pair, on the depth stream behind the slot's raw depth (deep_models.py:217-230, depth_consistency.py:69-151):
+// both feed images into the net's fixed staging frames, the net, its 4x4 (or the caller's) into the slot, the current feed kept as
+// the next pair's reference feed, and with the mask on the depth-difference map from the pose where it lies, in device memory.
+// d_cur_feed: the current frame at feed size (the caller's or the depth net's), or null to resize d_cur here.
+// Stream order is all the synchronisation there is: the previous slot's raw depth was written on this stream, and is overwritten
+// on it three pairs later.  ref_raw's other writer is the iterative loop's roll-over on s_trk, under the e_roll rule.
+static int enqueue_pose_lane(dfvo_pipeline* p, int slot, const uint8_t* d_ref, const uint8_t* d_cur, const uint8_t* d_cur_feed) {
+    Slot& sl = p->slots[slot];
+    hipStream_t s = p->s_depth;
+    const size_t feed_bytes = (size_t)p->feedH * p->feedW * 3;
+    uint8_t* feed_ref = p->pose_feed.p;
+    uint8_t* feed_cur = p->pose_feed.p + p->pose_feed_pitch;
+    if (d_cur_feed)
+        DFVO_HIP_CHECK(hipMemcpyAsync(feed_cur, d_cur_feed, feed_bytes, hipMemcpyDeviceToDevice, s));
+    else
+        P_TRY(p->feed_resize.enqueue(d_cur, feed_cur, s));
+    if (d_ref) P_TRY(p->feed_resize.enqueue(d_ref, feed_ref, s));
+    P_TRY(p->pose_net.forward(feed_ref, feed_cur, p->pose_out, nullptr));
+    const float* pose = sl.pose_override ? sl.pose_override : p->pose_out.p;
+    DFVO_HIP_CHECK(hipMemcpyAsync(sl.pose16, pose, 16 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    DFVO_HIP_CHECK(hipMemcpyAsync(feed_ref, feed_cur, feed_bytes, hipMemcpyDeviceToDevice, s));
+    p->pose_ref_feed = true;
+    if (p->pose.depth_consistency) {
+        const dfvo_pipeline_cfg& c = p->cfg;
+        const float K[9] = {(float)c.fx, 0.f, (float)c.cx, 0.f, (float)c.fy, (float)c.cy, 0.f, 0.f, 1.f};
+        float Kinv[9];
+        for (int i = 0; i < 9; ++i) Kinv[i] = (float)c.Kinv[i];
+        if (p->pose_ref_raw == p->ref_raw.p && p->roll_pending) DFVO_HIP_CHECK(hipStreamWaitEvent(s, p->e_roll, 0));
+        P_TRY(launch_depth_consistency_dev(sl.raw_depth, p->pose_ref_raw, p->H, p->W, K, Kinv, sl.pose16, sl.depth_diff, s));
+        p->pose_ref_raw = sl.raw_depth.p;
+    }
+    return DFVO_OK;
+}
+
 int dfvo_pipeline_enqueue_nets(dfvo_pipeline* p, int slot, const uint8_t* d_ref, const uint8_t* d_cur,
                                const uint8_t* d_cur_feed) {
     DFVO_ARG_CHECK(p && p->nets_ready && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS) && d_cur,
                    "dfvo_pipeline_enqueue_nets: bad argument");
     DFVO_ARG_CHECK(p->dsrc.source == DFVO_DEPTH_NET, "dfvo_pipeline_enqueue_nets: the depth source is DFVO_DEPTH_EXTERNAL (no depth net): "
                                                      "dfvo_pipeline_enqueue_nets_depth takes the pair's depth image");
+    if (p->pose.enable) P_TRY(check_pose_lane(p, d_ref, "dfvo_pipeline_enqueue_nets"));
+    if (deep_pose_tracking(p)) {  // dfvo.py:302: neither the depth net nor the flow net
+        p->started = true;
+        P_TRY(enqueue_pose_lane(p, slot, d_ref, d_cur, d_cur_feed));
+        DFVO_HIP_CHECK(hipEventRecord(p->slots[slot].e_depth, p->s_depth));
+        return DFVO_OK;
+    }
     DFVO_ARG_CHECK(d_ref || p->last_flow, "dfvo_pipeline_enqueue_nets: d_ref == NULL (reference frame = the previous call's "
                                           "current frame) needs a previous call");
     p->started = true;
     Slot& sl = p->slots[slot];
+    P_TRY(keep_ref_raw(p, sl));
     // depth of the current frame (dfvo.py:305-319); without a caller-resized frame the LANCZOS resize of
     // deep_models.py:195-199 runs here, ahead of the net on its stream
     if (!d_cur_feed) {
@@ -525,6 +679,7 @@ int dfvo_pipeline_enqueue_nets(dfvo_pipeline* p, int slot, const uint8_t* d_ref,
     }
     P_TRY(p->depth.forward(d_cur_feed, p->depth_small));
     P_TRY(enqueue_depth_post(p, sl.raw_depth, sl.proc_depth));
+    if (p->pose.enable) P_TRY(enqueue_pose_lane(p, slot, d_ref, d_cur, d_cur_feed));
     DFVO_HIP_CHECK(hipEventRecord(sl.e_depth, p->s_depth));
     return enqueue_flow_half(p, slot, d_ref, d_cur);
 }
@@ -534,12 +689,21 @@ int dfvo_pipeline_enqueue_nets_depth(dfvo_pipeline* p, int slot, const uint8_t* 
                    "dfvo_pipeline_enqueue_nets_depth: bad argument");
     DFVO_ARG_CHECK(p->dsrc.source == DFVO_DEPTH_EXTERNAL, "dfvo_pipeline_enqueue_nets_depth: the depth source is DFVO_DEPTH_NET "
                                                           "(dfvo_pipeline_set_depth_source): dfvo_pipeline_enqueue_nets runs the depth net");
+    if (p->pose.enable) P_TRY(check_pose_lane(p, d_ref, "dfvo_pipeline_enqueue_nets_depth"));
+    if (deep_pose_tracking(p)) {  // (the depth image has no reader)
+        p->started = true;
+        P_TRY(enqueue_pose_lane(p, slot, d_ref, d_cur, nullptr));
+        DFVO_HIP_CHECK(hipEventRecord(p->slots[slot].e_depth, p->s_depth));
+        return DFVO_OK;
+    }
     DFVO_ARG_CHECK(d_ref || p->last_flow, "dfvo_pipeline_enqueue_nets_depth: d_ref == NULL (reference frame = the previous call's "
                                           "current frame) needs a previous call");
     p->started = true;
     Slot& sl = p->slots[slot];
+    P_TRY(keep_ref_raw(p, sl));
     // depth of the current frame: the sensor's image where dfvo.py:305-319 runs the depth net
     P_TRY(enqueue_read_depth(p, d_depth_u16, sl.raw_depth, sl.proc_depth));
+    if (p->pose.enable) P_TRY(enqueue_pose_lane(p, slot, d_ref, d_cur, nullptr));  // (the LANCZOS feed for the pose net alone)
     DFVO_HIP_CHECK(hipEventRecord(sl.e_depth, p->s_depth));
     return enqueue_flow_half(p, slot, d_ref, d_cur);
 }
@@ -585,6 +749,7 @@ int dfvo_pipeline_set_ref_depth(dfvo_pipeline* p, const uint8_t* d_feed, const d
         // is ordered behind it on the device, the depth stream runs its later passes in order anyway
         DFVO_HIP_CHECK(hipEventRecord(p->e_ref, p->s_depth));
         DFVO_HIP_CHECK(hipStreamWaitEvent(p->s_trk, p->e_ref, 0));
+        p->pose_ref_raw = p->ref_raw.p;  // (written on the depth stream: the mask's read is in stream order)
     }
     p->has_ref_depth = true;
     return DFVO_OK;
@@ -607,6 +772,7 @@ int dfvo_pipeline_set_ref_depth_u16(dfvo_pipeline* p, const uint16_t* d_depth_u1
     // (ordered as the depth net's reference depth is: the solver stream behind it on the device, no host wait)
     DFVO_HIP_CHECK(hipEventRecord(p->e_ref, p->s_depth));
     DFVO_HIP_CHECK(hipStreamWaitEvent(p->s_trk, p->e_ref, 0));
+    p->pose_ref_raw = p->ref_raw.p;
     p->has_ref_depth = true;
     return DFVO_OK;
 }
@@ -616,6 +782,7 @@ int dfvo_pipeline_set_ref_raw_depth(dfvo_pipeline* p, const float* d_raw) {
     p->started = true;
     DFVO_HIP_CHECK(hipMemcpyAsync(p->ref_raw, d_raw, (size_t)p->H * p->W * sizeof(float), hipMemcpyDeviceToDevice, p->s_trk));
     DFVO_HIP_CHECK(hipStreamSynchronize(p->s_trk));
+    p->pose_ref_raw = p->ref_raw.p;  // (complete: the host waited)
     return DFVO_OK;
 }
 
@@ -716,8 +883,11 @@ static int enqueue_pre_part(dfvo_pipeline* p, int slot, const float* d_flow_over
         P_TRY(enqueue_kp_sampled(flow, p->H, p->W, p->sample_crop[0], p->sample_crop[1], p->sample_crop[2], p->sample_crop[3],
                                  p->d_samples, o.kp_sampled_num, tb.kp_ref, tb.kp_cur, sp, tb.kp_info));
     } else {
+        // the depth mask (kp_selection.py:118-119,145-148): the slot's map, written by the pose lane ahead of e_depth
+        const bool mask = p->pose.depth_consistency != 0;
+        if (mask) DFVO_HIP_CHECK(hipStreamWaitEvent(sp, sl.e_depth, 0));
         P_TRY(enqueue_local_bestn(tb, flow, diff, p->H, p->W, c.kp_num_row, c.kp_num_col, c.kp_num_bestN, (float)c.kp_thre, sp,
-                                  o.kp_score_method));
+                                  o.kp_score_method, mask ? sl.depth_diff.p : nullptr, mask ? p->pose.depth_thre : 0.f));
     }
     DFVO_HIP_CHECK(hipMemcpyAsync(sl.h_info, tb.kp_info, 3 * sizeof(int), hipMemcpyDeviceToHost, sp));
     DFVO_HIP_CHECK(hipEventRecord(sl.e_pre, sp));  // the host only needs the keypoint count; tb.ev_h orders the rest
@@ -735,6 +905,7 @@ static int enqueue_pre_part(dfvo_pipeline* p, int slot, const float* d_flow_over
 
 int dfvo_pipeline_prefetch_track(dfvo_pipeline* p, int slot, const float* d_flow_override, const float* d_diff_override) {
     DFVO_ARG_CHECK(p && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS), "dfvo_pipeline_prefetch_track: bad argument");
+    if (deep_pose_tracking(p)) return DFVO_OK;  // no keypoint stage: nothing to run ahead
     DFVO_ARG_CHECK(!p->slots[slot].prefetched, "dfvo_pipeline_prefetch_track: slot already prefetched and not yet tracked");
     P_TRY(enqueue_pre_part(p, slot, d_flow_override, d_diff_override, p->s_pre[slot & 1]));
     p->slots[slot].prefetched = true;
@@ -757,6 +928,18 @@ int dfvo_pipeline_track_begin(dfvo_pipeline* p, int slot, const float* d_flow_ov
     static const bool trace = getenv("DFVO_TRACK_TRACE") != nullptr;
     if (trace && !tb.ev_t[0])
         for (int i = 0; i < 4; i++) DFVO_HIP_CHECK(hipEventCreate(&tb.ev_t[i]));
+    if (deep_pose_tracking(p)) {
+        // dfvo.py:252-255: the pair's motion is the pose net's matrix.  No keypoints, no RandomState draw; the 16 floats go to
+        // pinned memory behind the pose lane
+        DFVO_HIP_CHECK(hipStreamWaitEvent(s, sl.e_depth, 0));
+        DFVO_HIP_CHECK(hipMemcpyAsync(sl.h_pose.p, sl.pose16, 16 * sizeof(float), hipMemcpyDeviceToHost, s));
+        DFVO_HIP_CHECK(hipEventRecord(sl.e_res, s));
+        sl.depth_override = nullptr;
+        sl.n = 0;
+        sl.begun = CHAIN_ENQUEUED;
+        p->pending_slot = slot;
+        return DFVO_OK;
+    }
     const bool pnp_only = p->opts.tracking_method == DFVO_TRACKING_PNP;
     const bool iterative = p->iter.enable && !pnp_only;
     // side stream: the scale stage's fills leave the dependent chain (the iterative loop clears the map itself, every round)
@@ -838,8 +1021,20 @@ int dfvo_pipeline_track_end(dfvo_pipeline* p, int slot, dfvo_track_out* out) {
     const double* d_depth_override = sl.depth_override;
     sl.begun = IDLE;
     p->pending_slot = -1;
+    sl.pose_override = nullptr;  // (held for the pair that ends here)
     memset(out, 0, sizeof(*out));
     for (int i = 0; i < 3; i++) out->R[i * 4] = 1.0;
+    if (deep_pose_tracking(p)) {
+        DFVO_HIP_CHECK(hipEventSynchronize(sl.e_res));
+        const float* T = sl.h_pose.p;  // row-major 4x4; float32 -> double is exact
+        for (int r = 0; r < 3; r++) {
+            for (int q = 0; q < 3; q++) out->R[r * 3 + q] = (double)T[r * 4 + q];
+            out->t[r] = (double)T[r * 4 + 3];
+        }
+        out->scale = 1.0;
+        out->status = DFVO_TRACK_DEEP_POSE;
+        return DFVO_OK;  // (no depth to roll over: none was computed)
+    }
     const int* info = sl.h_info;
     out->n_kp = info[0];
     out->good_kp_found = info[1];
@@ -949,6 +1144,8 @@ int dfvo_pipeline_track(dfvo_pipeline* p, int slot, const float* d_flow_override
 int dfvo_pipeline_get_flow(dfvo_pipeline* p, int slot, float* h_fwd, float* h_bwd, float* h_diff, float* h_raw_depth,
                            double* h_depth) {
     DFVO_ARG_CHECK(p && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS), "dfvo_pipeline_get_flow: bad argument");
+    DFVO_ARG_CHECK(!deep_pose_tracking(p), "dfvo_pipeline_get_flow: tracking_method DFVO_TRACKING_DEEP_POSE runs neither the flow net "
+                                           "nor the depth net: there are no outputs");
     const size_t px = (size_t)p->H * p->W;
     const Slot& sl = p->slots[slot];
     DFVO_HIP_CHECK(hipDeviceSynchronize());
@@ -973,6 +1170,7 @@ int dfvo_pipeline_get_keypoints(dfvo_pipeline* p, int slot, int cap, double* h_k
                                 uint8_t* h_inliers, int* n_out) {
     DFVO_ARG_CHECK(p && n_out && (slot >= 0 && slot < DFVO_PIPELINE_SLOTS) && cap >= 0,
                    "dfvo_pipeline_get_keypoints: bad argument");
+    DFVO_ARG_CHECK(!deep_pose_tracking(p), "dfvo_pipeline_get_keypoints: tracking_method DFVO_TRACKING_DEEP_POSE selects no keypoints");
     TrackerBuffers& tb = p->slots[slot].tb;
     DFVO_HIP_CHECK(hipDeviceSynchronize());
     int info[3] = {0, 0, 0};
@@ -1064,7 +1262,9 @@ int dfvo_pipeline_stream_layout(dfvo_pipeline* p, char* buf, int n) {
 
 double dfvo_pipeline_net_flops(const dfvo_pipeline* p) {
     if (!p) return 0.0;
-    return p->dsrc.source == DFVO_DEPTH_EXTERNAL ? p->flow.flops_last : p->flow.flops_last + p->depth.flops_last;
+    const double pose = p->pose.enable ? p->pose_net.flops_last : 0.0;
+    if (p->opts.tracking_method == DFVO_TRACKING_DEEP_POSE) return pose;
+    return pose + (p->dsrc.source == DFVO_DEPTH_EXTERNAL ? p->flow.flops_last : p->flow.flops_last + p->depth.flops_last);
 }
 
 }  // extern "C"

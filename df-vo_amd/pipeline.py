@@ -2,8 +2,9 @@
 double-buffered net/solver software pipeline, and pose accumulation as in
 the reference's libs/dfvo.py:109-119 (update_global_pose) and :121-262 (tracking: the hybrid path of
 default_configuration.yml, and through the option keys below the keypoint sources, validity / scale methods, the
-PnP-only tracking and the iterative scale recovery of the shipped ablation files, and depth.depth_src gt: 16-bit depth images in
-the place of the depth net; options_from_cfg maps the reference's configuration object to them)."""
+PnP-only tracking and the iterative scale recovery of the shipped ablation files, depth.depth_src gt: 16-bit depth images in
+the place of the depth net, and the pose net with its two consumers, the kp_selection.depth_consistency mask and tracking_method
+deep_pose; options_from_cfg maps the reference's configuration object to them)."""
 import ctypes as C
 
 import numpy as np
@@ -17,7 +18,7 @@ DEFAULTS = dict(  # options/examples/default_configuration.yml
     e_reproj_thre=0.2, e_repeat=5, e_max_iters=1000, scale_min_samples=3, scale_max_trials=100,
     scale_stop_prob=0.99, scale_thre=0.1, seed=4869, pnp_repeat=5, pnp_iters=100, pnp_reproj_thre=1.0)
 
-STATUS = {0: "E", 1: "constant_motion", 2: "needs_pnp", 3: "PnP"}
+STATUS = {0: "E", 1: "constant_motion", 2: "needs_pnp", 3: "PnP", 4: "DeepPose"}
 
 # dfvo_pipeline_set_options: the tracking configurations beyond default_configuration.yml.  Every key defaults to that
 # configuration; the values are the reference's own spellings (options/examples/ablation_*.yml)
@@ -27,7 +28,7 @@ _KP_SOURCE = {"local_bestN": 0, "bestN": 1, "sampled": 2}
 _KP_SCORE = {"flow": 0, "flow_ratio": 1}
 _VALIDITY = {"GRIC": 0, "flow": 1, "homo_ratio": 2}
 _SCALE_METHOD = {"depth_ratio": 0, "abs_diff": 1}
-_TRACKING = {"hybrid": 0, "PnP": 1}
+_TRACKING = {"hybrid": 0, "PnP": 1, "deep_pose": 2}
 
 # dfvo_pipeline_set_iterative: scale_recovery.method and the kp_selection.rigid_flow_kp block (ablation_scale_iterative.yml).
 # Kept apart from OPTION_DEFAULTS, whose keys are the fields of capi.PipelineOpts
@@ -43,6 +44,11 @@ ITER_STATUS = {0: "finished", 1: "empty_selection", 2: "no_consensus", 3: "not_r
 # other two
 DEPTH_DEFAULTS = dict(depth_source="net", depth_scale=None, depth_size=None)
 _DEPTH_SOURCE = {"net": capi.DEPTH_NET, "external": capi.DEPTH_EXTERNAL}
+
+
+# dfvo_pipeline_set_pose_net: deep_pose.enable (monodepth2's two-frame pose net on the depth stream) and what reads its pose --
+# kp_selection.depth_consistency (enable, thre) here, tracking_method "deep_pose" among the option keys.  A fourth table
+POSE_DEFAULTS = dict(pose_net=False, depth_consistency=False, depth_consistency_thre=0.05)
 
 
 def _choice(o, key, table):
@@ -122,6 +128,21 @@ def check_depth_options(o, img_h=None, img_w=None):
     return f
 
 
+def check_pose_options(o, kp_source="local_bestN"):
+    """the pose-lane keys of `o` (POSE_DEFAULTS filled in) as the fields of capi.PipelinePoseOpts; ValueError on a bad value"""
+    for key in ("pose_net", "depth_consistency"):
+        if not isinstance(o[key], (bool, np.bool_)):
+            raise ValueError("%s = %r: True or False" % (key, o[key]))
+    v = o["depth_consistency_thre"]
+    if v is None or isinstance(v, (bool, str)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(float(v)):
+        raise ValueError("depth_consistency_thre = %r: a finite threshold" % (v,))
+    if o["depth_consistency"] and not o["pose_net"]:
+        raise ValueError("depth_consistency = True without pose_net: the mask is computed from the pose net's pose")
+    if o["depth_consistency"] and kp_source != "local_bestN":
+        raise ValueError("depth_consistency = True with kp_source = %r: the reference masks local_bestN only" % (kp_source,))
+    return dict(enable=int(o["pose_net"]), depth_consistency=int(o["depth_consistency"]), depth_thre=float(v))
+
+
 def options_from_cfg(cfg):
     """The reference's configuration object (default_cfg.Cfg / EasyDict of options/examples/*.yml) as the override dict of
     TrackingPipeline -- only the keys that differ from DEFAULTS / OPTION_DEFAULTS, so default_configuration.yml maps to {}.
@@ -139,10 +160,21 @@ def options_from_cfg(cfg):
         raise NotImplementedError("scale_recovery.method: %s: not run by the fused pipeline" % method)
     iterative = method == "iterative"
     for path in ("e_tracker.iterative_kp.enable", "scale_recovery.iterative_kp.enable", "pnp_tracker.iterative_kp.enable",
-                 "kp_selection.rigid_flow_kp.enable", "kp_selection.depth_consistency.enable", "deep_pose.enable",
-                 "online_finetune.enable"):
+                 "kp_selection.rigid_flow_kp.enable", "online_finetune.enable"):
         if get(path, False) and not (iterative and path == "kp_selection.rigid_flow_kp.enable"):
             raise NotImplementedError("%s: not run by the fused pipeline" % path)
+    # the pose net runs for a consumer: tracking_method deep_pose (dfvo.py:252-255) or the depth mask of hybrid / PnP tracking
+    tracking = get("tracking_method", "hybrid")
+    deep, mask = bool(get("deep_pose.enable", False)), bool(get("kp_selection.depth_consistency.enable", False))
+    if mask and not deep:  # (DepthConsistency.compute dies on the missing ref_data['deep_pose'])
+        raise NotImplementedError("kp_selection.depth_consistency.enable: without deep_pose.enable the mask has no pose to warp with")
+    if tracking == "deep_pose" and not deep:
+        raise NotImplementedError("tracking_method: deep_pose without deep_pose.enable: there is no pose net to track with")
+    if tracking == "deep_pose":
+        mask = False  # (dfvo.py:139-143: the map is computed in the hybrid / PnP branch only)
+    if deep and not mask and tracking != "deep_pose":
+        raise NotImplementedError("deep_pose.enable: nothing reads the pose (tracking_method is not deep_pose, "
+                                  "kp_selection.depth_consistency is off): the fused pipeline does not run the net")
     if iterative and not get("kp_selection.rigid_flow_kp.enable", False):
         # (kp_selection_good_depth returns nothing then, and the loop dies on its missing key: E_tracker.py:541,671)
         raise NotImplementedError("kp_selection.rigid_flow_kp.enable: False under scale_recovery.method: iterative: the loop "
@@ -161,6 +193,9 @@ def options_from_cfg(cfg):
         raise NotImplementedError("kp_src: %s disagree; the fused pipeline tracks one keypoint set" % ", ".join(
             "%s.kp_src = %s" % kv for kv in sorted(srcs.items())))
     src = srcs["e_tracker"]
+    if tracking == "deep_pose":
+        # nothing selects keypoints: the source keys are not read
+        return {"tracking_method": "deep_pose", "pose_net": True}
     if src == "kp_best":  # keypoint_sampler.py:108-129: local_bestN, else bestN
         if get("kp_selection.local_bestN.enable", False):
             source = "local_bestN"
@@ -172,7 +207,10 @@ def options_from_cfg(cfg):
         if not get("kp_selection.sampled_kp.enable", False):
             raise NotImplementedError("kp_src: kp_list, but kp_selection.sampled_kp is not enabled")
         source = "sampled"
-    full = dict(kp_source=source, tracking_method=get("tracking_method", "hybrid"),
+    if mask and source != "local_bestN":
+        raise NotImplementedError("kp_selection.depth_consistency.enable: with keypoint source %s: the reference masks "
+                                  "kp_selection.local_bestN only" % source)
+    full = dict(kp_source=source, tracking_method=tracking,
                 validity=get("e_tracker.validity.method", "GRIC"),
                 scale_method=get("scale_recovery.ransac.method", "depth_ratio"),
                 seed=get("seed", 4869), min_depth=get("depth.min_depth", 0.0), max_depth=get("depth.max_depth", 50.0),
@@ -209,10 +247,13 @@ def options_from_cfg(cfg):
     elif depth_src is not None:
         raise NotImplementedError("depth.depth_src: %s: not run by the fused pipeline (None: the depth net, gt: 16-bit depth images)"
                                   % (depth_src,))
+    if mask:
+        full.update(pose_net=True, depth_consistency=True, depth_consistency_thre=get("kp_selection.depth_consistency.thre", 0.05))
     base = dict(DEFAULTS)
     base.update(OPTION_DEFAULTS)
     base.update(ITER_DEFAULTS)
     base.update(DEPTH_DEFAULTS)
+    base.update(POSE_DEFAULTS)
     out = {k: v for k, v in full.items() if base.get(k) != v}
     check = dict(OPTION_DEFAULTS)
     check.update({k: v for k, v in out.items() if k in OPTION_DEFAULTS})
@@ -220,21 +261,34 @@ def options_from_cfg(cfg):
     check = dict(ITER_DEFAULTS)
     check.update({k: v for k, v in out.items() if k in ITER_DEFAULTS})
     check_iter_options(check)
+    check = dict(POSE_DEFAULTS)
+    check.update({k: v for k, v in out.items() if k in POSE_DEFAULTS})
+    check_pose_options(check, source)
     return out
 
 
 class TrackingPipeline:
-    def __init__(self, img_h, img_w, feed_h, feed_w, K, flow_sd, depth_sd, **overrides):
+    def __init__(self, img_h, img_w, feed_h, feed_w, K, flow_sd, depth_sd, pose_sd=None, **overrides):
         o = dict(DEFAULTS)
         o.update(OPTION_DEFAULTS)
         io = dict(ITER_DEFAULTS)
         io.update({k: overrides.pop(k) for k in list(overrides) if k in ITER_DEFAULTS})
         do = dict(DEPTH_DEFAULTS)
         do.update({k: overrides.pop(k) for k in list(overrides) if k in DEPTH_DEFAULTS})
+        po = dict(POSE_DEFAULTS)
+        po.update({k: overrides.pop(k) for k in list(overrides) if k in POSE_DEFAULTS})
         o.update(overrides)
         fields = check_options(o)  # (before anything touches the device: a bad value is a ValueError)
         iter_fields = check_iter_options(io)
         depth_fields = check_depth_options(do, img_h, img_w)
+        pose_fields = check_pose_options(po, o["kp_source"])
+        self.deep_pose = o["tracking_method"] == "deep_pose"
+        if self.deep_pose and not po["pose_net"]:
+            raise ValueError("tracking_method = 'deep_pose' without pose_net = True: there is no pose net to track with")
+        if self.deep_pose and po["depth_consistency"]:
+            raise ValueError("depth_consistency = True under tracking_method 'deep_pose': nothing selects keypoints")
+        if po["pose_net"] and pose_sd is None:
+            raise ValueError("pose_sd = None: pose_net = True runs the pose net and needs its weights")
         self.external_depth = do["depth_source"] == "external"
         if depth_sd is None and not self.external_depth:
             raise ValueError("depth_sd = None: depth_source 'net' runs the depth net and needs its weights (depth_source "
@@ -244,6 +298,7 @@ class TrackingPipeline:
         self.opts = o
         self.iter_opts = io
         self.depth_opts = do
+        self.pose_opts = po
         self.depth_size = (depth_fields["src_h"], depth_fields["src_w"])
         self.iterative = io["scale_recovery"] == "iterative"
         self.H, self.W, self.feed_h, self.feed_w = img_h, img_w, feed_h, feed_w
@@ -275,13 +330,19 @@ class TrackingPipeline:
             except capi.DfvoError:
                 self.close()
                 raise
+        if po["pose_net"]:  # (ahead of set_options, which takes tracking_method deep_pose only behind it)
+            try:
+                capi.check(self.lib.dfvo_pipeline_set_pose_net(h, C.byref(capi.PipelinePoseOpts(**pose_fields))))
+            except capi.DfvoError:
+                self.close()
+                raise
         if any(o[k] != v for k, v in OPTION_DEFAULTS.items()):
             crop = fields.pop("flow_crop")
-            po = capi.PipelineOpts(**fields)
+            popts = capi.PipelineOpts(**fields)
             for i, v in enumerate(crop):
-                po.flow_crop[i] = v
+                popts.flow_crop[i] = v
             try:
-                capi.check(self.lib.dfvo_pipeline_set_options(h, C.byref(po)))
+                capi.check(self.lib.dfvo_pipeline_set_options(h, C.byref(popts)))
             except capi.DfvoError:
                 self.close()
                 raise
@@ -304,14 +365,18 @@ class TrackingPipeline:
             dparams = {k: v.detach().cpu().float().numpy() for k, v in depth_sd.items()
                        if hasattr(v, "detach") and v.dim() > 0 and "num_batches_tracked" not in k}
             capi.set_params(self.lib.dfvo_pipeline_set_depth_param, h, dparams)
+        if po["pose_net"]:
+            pparams = {k: v.detach().cpu().float().numpy() for k, v in pose_sd.items()
+                       if hasattr(v, "detach") and v.dim() > 0 and "num_batches_tracked" not in k and not k.startswith("encoder.fc")}
+            capi.set_params(self.lib.dfvo_pipeline_set_pose_param, h, pparams)
         capi.check(self.lib.dfvo_pipeline_finalize(h))
 
     @classmethod
-    def from_cfg(cls, cfg, K, flow_sd, depth_sd, feed_h, feed_w, **overrides):
+    def from_cfg(cls, cfg, K, flow_sd, depth_sd, feed_h, feed_w, pose_sd=None, **overrides):
         """a pipeline for the reference's configuration object `cfg` (image size from cfg.image); `overrides` win"""
         o = options_from_cfg(cfg)  # (depth.depth_src gt: depth_scale, the loader's scale factor, comes with `overrides`)
         o.update(overrides)
-        return cls(int(cfg["image"]["height"]), int(cfg["image"]["width"]), feed_h, feed_w, K, flow_sd, depth_sd, **o)
+        return cls(int(cfg["image"]["height"]), int(cfg["image"]["width"]), feed_h, feed_w, K, flow_sd, depth_sd, pose_sd=pose_sd, **o)
 
     @staticmethod
     def _net_size(h, w):
@@ -397,6 +462,19 @@ class TrackingPipeline:
         """the raw float32 depth [H,W] of `slot`'s current frame for the roll-over, until the slot's track_end (None withdraws)"""
         capi.check(self.lib.dfvo_pipeline_set_raw_depth_override(
             self.h, slot, C.c_void_p(raw_depth.data_ptr()) if raw_depth is not None else None))
+
+    def set_pose_override(self, slot, pose16):
+        """a device float32 4x4 (contiguous) that the pair enqueued into `slot` next uses in the place of the pose net's; set
+        before the slot's enqueue_nets, unchanged until its track_end, which withdraws it (as None does)"""
+        capi.check(self.lib.dfvo_pipeline_set_pose_override(
+            self.h, slot, C.c_void_p(pose16.data_ptr()) if pose16 is not None else None))
+
+    def get_pose_net(self, slot):
+        """(pose [4,4] f32, depth_diff [H,W] f32 or None without the mask): what the slot's last pair used"""
+        pose = np.full((4, 4), np.nan, np.float32)  # (NaN: what the library does not write shows)
+        m = np.full((self.H, self.W), np.nan, np.float32) if self.pose_opts["depth_consistency"] else None
+        capi.check(self.lib.dfvo_pipeline_get_pose_net(self.h, slot, capi.as_ptr(pose), capi.as_ptr(m)))
+        return pose, m
 
     def get_prev_scale(self):
         """EssTracker.prev_scale as the pipeline carries it on the device (iterative scale recovery)"""
@@ -502,6 +580,10 @@ class TrackingPipeline:
         if out.status == 2:
             raise capi.DfvoError("PnP fallback required but no reference depth is known: call set_ref_depth() "
                                  "for the first frame")
+        if out.status == 4:  # dfvo.py:252-255: SE3(ref_data['deep_pose'])
+            T[:3, :3] = np.array(out.R[:]).reshape(3, 3)
+            T[:3, 3] = np.array(out.t[:])
+            return T, "DeepPose"
         if out.status == 3:  # pnp_tracker.py:112-118: SE3 from (R, t) of solvePnP, then pose = inv_pose
             T[:3, :3] = np.array(out.R[:]).reshape(3, 3)
             T[:3, 3] = np.array(out.t[:])

@@ -7,7 +7,9 @@ is recomputed by the rank that owns the chunk -- no activation exchange between 
 ahead of the solver stage; nothing but the relative poses leaves the device.  The driver reads nothing but the status word
 and the pose of a pair, so it runs a pipeline of any tracking configuration (pipeline.TrackingPipeline's kp_source / validity /
 scale_method / tracking_method / scale_recovery keys, TrackingPipeline.from_cfg): with tracking_method "PnP" every row has
-status 3; with scale_recovery "iterative" a chunk starts from prev_scale 0 and runs on one rank only.
+status 3; with scale_recovery "iterative" a chunk starts from prev_scale 0 and runs on one rank only; with tracking_method
+"deep_pose" every row has status 4, no depth is computed (the halo's neither) and no RandomState is read, so chunks join exactly
+under either RandomState mode; the depth mask (pose_net + depth_consistency) changes nothing here.
 
 RandomState modes (SURVEY hard part 2):
   "sequential"  one stream seeded once (np.random.seed(cfg.seed), run.py:81-84) and carried from pair to pair -- the
@@ -38,7 +40,9 @@ def track_chunk(pipe, frames, lo, hi, seed=4869, rng_mode="sequential", ahead=3,
     if n <= 0:
         return rel, status
     ahead = max(1, min(ahead, SLOTS - 1))
-    if depths is None:
+    if getattr(pipe, "deep_pose", False):
+        pass  # tracking_method deep_pose: no depth anywhere, the halo's included
+    elif depths is None:
         pipe.set_ref_image(frames[lo])  # halo: depth of the chunk's first reference frame
     else:
         pipe.set_ref_depth_image(depths[lo])
@@ -87,9 +91,9 @@ def run_sequence(pipe, frames, n_frames, world=1, rank=0, dist=None, seed=4869, 
     depths: the frames' 16-bit depth images for a pipeline of depth_source "external" (track_chunk); every rank reads its own
     chunk's, the halo's included.
     Returns (global poses [n_frames,4,4] camera-to-world, gathered [n_frames-1,17])."""
-    if rng_mode is None:
-        rng_mode = "sequential" if world == 1 else "per_pair"
-    if world > 1 and rng_mode == "sequential":
+    if rng_mode is None:  # (tracking_method deep_pose draws nothing: either mode gives the single-rank result)
+        rng_mode = "sequential" if world == 1 or getattr(pipe, "deep_pose", False) else "per_pair"
+    if world > 1 and rng_mode == "sequential" and not getattr(pipe, "deep_pose", False):
         raise ValueError("the sequential numpy RandomState cannot be reproduced frame-parallel; use rng_mode='per_pair'")
     _refuse_iterative_multi_rank(pipe, world)
     bounds = [dmod.chunk_bounds(n_frames - 1, world, r) for r in range(world)]
@@ -118,8 +122,8 @@ def run_sequences(pipe, seqs, world=1, rank=0, dist=None, comm=None, seed=4869, 
     Returns {name: {"poses": [n,4,4], "gathered": [n-1,17], "metrics": dict or None}} in the order of `seqs`."""
     from . import evaluation as ev
     if rng_mode is None:
-        rng_mode = "sequential" if world == 1 else "per_pair"
-    if world > 1 and rng_mode == "sequential":
+        rng_mode = "sequential" if world == 1 or getattr(pipe, "deep_pose", False) else "per_pair"
+    if world > 1 and rng_mode == "sequential" and not getattr(pipe, "deep_pose", False):
         raise ValueError("the sequential numpy RandomState cannot be reproduced frame-parallel; use rng_mode='per_pair'")
     _refuse_iterative_multi_rank(pipe, world)
     n_pairs = [max(0, int(q[2]) - 1) for q in seqs]

@@ -298,6 +298,12 @@ int dfvo_depth_consistency(const float* d_cur_depth, const float* d_ref_depth, i
                            const float* h_T, float* d_out, void* stream);
 int dfvo_depth_consistency_host(const float* h_cur_depth, const float* h_ref_depth, int H, int W, const float* h_K,
                                 const float* h_Kinv, const float* h_T, float* h_out);
+/* dfvo_depth_consistency with the pose in device memory: d_T16 is a device float[16], row-major (4-byte aligned), as
+ * dfvo_posenet_forward leaves it.  The kernel reads it in stream order -- it may be the output of work enqueued earlier on
+ * `stream` -- and the host never does: no wait, no copy.  For the same 16 floats the map is bit-identical to
+ * dfvo_depth_consistency's.  Asynchronous on `stream`. */
+int dfvo_depth_consistency_dev(const float* d_cur_depth, const float* d_ref_depth, int H, int W, const float* h_K,
+                               const float* h_Kinv, const float* d_T16, float* d_out, void* stream);
 
 /* =====================================================================================
  * Pose solvers (wavefront-parallel RANSAC, f64).  Host arrays in / out, synchronous: these are the
@@ -564,10 +570,12 @@ typedef struct dfvo_pipeline_cfg {
 #define DFVO_TRACK_CONSTANT_MOTION 1   /* not enough keypoints: caller reuses the previous motion (dfvo.py:157-161) */
 #define DFVO_TRACK_NEEDS_PNP 2         /* E rejected or scale == -1 and no reference depth is known yet (first pair) */
 #define DFVO_TRACK_PNP 3               /* E rejected or scale == -1: pose from the PnP fallback (dfvo.py:225-250) */
+#define DFVO_TRACK_DEEP_POSE 4         /* tracking_method deep_pose: the pose net's matrix (dfvo.py:252-255) */
 typedef struct dfvo_track_out {
     double R[9], t[3];        /* DFVO_TRACK_E: E-tracker pose cur -> ref (t has unit norm or is zero);
                                  DFVO_TRACK_PNP: the solvePnP pose (ref points -> cur camera; identity when no repeat
-                                 found a model), which the caller inverts as pnp_tracker.py:118 does */
+                                 found a model), which the caller inverts as pnp_tracker.py:118 does;
+                                 DFVO_TRACK_DEEP_POSE: the pose net's float32 [R|t], cur -> ref, converted exactly; scale 1 */
     double scale;
     int status, n_kp, good_kp_found, best_inlier_cnt, num_valid, cheirality;
     int scale_n_valid, scale_n_trials, scale_n_inliers;
@@ -609,6 +617,7 @@ int dfvo_pipeline_seed(dfvo_pipeline* p, uint32_t seed);
 #define DFVO_SCALE_ABS_DIFF 1
 #define DFVO_TRACKING_HYBRID 0
 #define DFVO_TRACKING_PNP 1
+#define DFVO_TRACKING_DEEP_POSE 2  /* needs dfvo_pipeline_set_pose_net (enable) first */
 typedef struct dfvo_pipeline_opts {
     int kp_source;        /* DFVO_KP_SOURCE_* */
     int kp_score_method;  /* local_bestN only: DFVO_KP_SCORE_FLOW | DFVO_KP_SCORE_FLOW_RATIO */
@@ -617,10 +626,46 @@ typedef struct dfvo_pipeline_opts {
     int validity_method;  /* DFVO_VALIDITY_GRIC | _FLOW | _HOMO_RATIO */
     double validity_thre; /* e_tracker.validity.thre (unused under GRIC) */
     int scale_method;     /* DFVO_SCALE_DEPTH_RATIO | DFVO_SCALE_ABS_DIFF (scale_recovery.ransac.method) */
-    int tracking_method;  /* DFVO_TRACKING_HYBRID | DFVO_TRACKING_PNP */
+    int tracking_method;  /* DFVO_TRACKING_HYBRID | DFVO_TRACKING_PNP | DFVO_TRACKING_DEEP_POSE */
 } dfvo_pipeline_opts;
 int dfvo_pipeline_set_options(dfvo_pipeline* p, const dfvo_pipeline_opts* opts);
 int dfvo_pipeline_set_graph(dfvo_pipeline* p, int enable);   /* hipGraph replay of the nets (default on) */
+/* monodepth2's two-frame pose net in the fused pipeline (deep_pose.enable; DeepModel.forward_pose, deep_models.py:217-230) and
+ * its two consumers: kp_selection.depth_consistency (the depth-difference map masks local_bestN's candidates,
+ * kp_selection.py:118-148) and tracking_method deep_pose (dfvo.py:252-255).  A pipeline on which dfvo_pipeline_set_pose_net is
+ * never called enqueues, allocates and waits for exactly what it did without it.
+ * The pose lane runs on the depth stream inside dfvo_pipeline_enqueue_nets / _enqueue_nets_depth, in stream order: the current
+ * frame's LANCZOS feed image (the depth net's, or made for the pose net alone), the reference frame's (d_ref resized, or with
+ * d_ref == NULL the previous call's current feed), the net, and with depth_consistency the map of dfvo_depth_consistency_dev
+ * over the slot's raw depth, the reference frame's raw depth and the pose, all in device memory.  The reference raw depth is
+ * the raw depth of the slot the previous dfvo_pipeline_enqueue_nets* call filled, or what dfvo_pipeline_set_ref_image /
+ * _set_ref_depth (d_feed) / _set_ref_depth_u16 / _set_ref_raw_depth left if one of them came since; a pair with neither is
+ * refused.  The keypoint stage waits for the lane on the device; the host never waits for the net after the first pair (which
+ * tunes and captures it).  baseline_mult is dfvo_pipeline_cfg's.
+ * dfvo_pipeline_set_pose_param: the keys of dfvo_posenet_set_param; before dfvo_pipeline_finalize (with the net enabled after
+ * dfvo_pipeline_finalize, before that dfvo_pipeline_set_pose_net call).
+ * dfvo_pipeline_set_pose_net: state rule of dfvo_pipeline_set_options, and ahead of it where both are called: DFVO_ERR_ARG once a
+ * pair or a reference depth was enqueued, for depth_consistency without enable, with a keypoint source other than
+ * DFVO_KP_SOURCE_LOCAL_BESTN (the only one the reference masks) or with a NaN threshold.  tracking_method
+ * DFVO_TRACKING_DEEP_POSE needs enable, and excludes depth_consistency (nothing selects keypoints).
+ * Under DFVO_TRACKING_DEEP_POSE neither the depth net nor the flow net runs (dfvo.py:302): dfvo_pipeline_enqueue_nets* enqueue
+ * the pose lane only, dfvo_pipeline_prefetch_track is accepted and does nothing, dfvo_pipeline_track_end reports status
+ * DFVO_TRACK_DEEP_POSE, scale 1, n_kp 0, draws nothing from the RandomState and rolls no depth; dfvo_pipeline_get_flow and
+ * dfvo_pipeline_get_keypoints return DFVO_ERR_ARG.
+ * dfvo_pipeline_set_pose_override: a device float[16] the pair enqueued into `slot` uses in the place of the net's matrix; set
+ * before the slot's dfvo_pipeline_enqueue_nets*, complete then and unchanged until the slot's dfvo_pipeline_track_end, which
+ * withdraws it (as NULL does).
+ * dfvo_pipeline_get_pose_net: what the slot's last pair used -- the 4x4 and (depth_consistency; else h_depth_diff must be NULL)
+ * the float [H,W] depth-difference map.  Waits for the device. */
+typedef struct dfvo_pipeline_pose_opts {
+    int enable;             /* deep_pose.enable */
+    int depth_consistency;  /* kp_selection.depth_consistency.enable */
+    float depth_thre;       /* kp_selection.depth_consistency.thre */
+} dfvo_pipeline_pose_opts;
+int dfvo_pipeline_set_pose_param(dfvo_pipeline* p, const char* name, const float* h_data, int ndim, const int* shape);
+int dfvo_pipeline_set_pose_net(dfvo_pipeline* p, const dfvo_pipeline_pose_opts* opts);
+int dfvo_pipeline_set_pose_override(dfvo_pipeline* p, int slot, const float* d_pose16);
+int dfvo_pipeline_get_pose_net(dfvo_pipeline* p, int slot, float* h_pose16, float* h_depth_diff);
 /* scale_recovery.method "iterative" in the fused pipeline (ablation_scale_iterative.yml, the tracking half of the *_extend.yml
  * files): EssTracker.scale_recovery_iterative (see dfvo_scale_recovery_iterative) takes the place of find_scale_from_depth in
  * the chain dfvo_pipeline_track_begin enqueues.  The loop starts and ends on the device: its first kernel reads the E-tracker's
