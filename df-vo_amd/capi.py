@@ -196,6 +196,14 @@ SIGNATURES = {
     "dfvo_resize_lanczos_u8": (_i, [_vp, _i, _i, _vp, _i, _i, _vp]),
     "dfvo_resize_linear_u8": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp]),
     "dfvo_read_image_tail_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "dfvo_read_image_tail_gray_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "dfvo_frame_ring_create": (_i, [_i, _sz, C.POINTER(_vp)]),
+    "dfvo_frame_ring_destroy": (None, [_vp]),
+    "dfvo_frame_ring_staging": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_sz)]),
+    "dfvo_frame_ring_submit_image": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i]),
+    "dfvo_frame_ring_submit_raw": (_i, [_vp, _i, _sz, _vp]),
+    "dfvo_frame_ring_wait": (_i, [_vp, _i]),
+    "dfvo_frame_ring_pending": (_i, [_vp, _ip]),
     "dfvo_resize_bilinear": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "dfvo_flownet_create": (_i, [_i, _i, _vp, C.POINTER(_vp)]),
     "dfvo_flownet_destroy": (None, [_vp]),

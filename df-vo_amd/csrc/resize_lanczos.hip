@@ -224,4 +224,47 @@ int enqueue_resize_linear_u8(const uint8_t* d_src, int H, int W, int C, uint8_t*
     return DFVO_OK;
 }
 
+// The same resize of a 1-channel frame, written as the three equal channels cv2.imread would have replicated it into: a third
+// of k_resize_linear_u8's source bytes, its arithmetic once per pixel (the three channels of a replicated frame go through the
+// same integers, so the bytes are those of the 3-channel kernel on the replicated frame).  One thread per output pixel, x
+// fastest: a wave reads one or two runs of neighbouring bytes per source row and writes 192 consecutive bytes.
+__global__ __launch_bounds__(256) void k_resize_linear_gray_u8(const uint8_t* __restrict__ src, int H, int W, int pitch,
+                                                                uint8_t* __restrict__ dst, int oh, int ow, double scale_x,
+                                                                double scale_y, int area2) {
+    const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y * blockDim.y + threadIdx.y;
+    if (dx >= ow || dy >= oh) return;
+    uint8_t* o = dst + ((size_t)dy * ow + dx) * 3;
+    uint8_t v;
+    if (area2) {
+        const uint8_t* p = src + (size_t)(2 * dy) * pitch + 2 * dx;
+        v = (uint8_t)((p[0] + p[1] + p[pitch] + p[pitch + 1] + 2) >> 2);
+    } else {
+        int sx, a0, a1, sy, b0, b1;
+        float f;
+        linear_coef_u8(dx, scale_x, &sx, &a0, &a1, &f);
+        if (sx < 0) sx = 0, a0 = 2048, a1 = 0;
+        if (sx >= W - 1) sx = W - 1, a0 = 2048, a1 = 0;
+        linear_coef_u8(dy, scale_y, &sy, &b0, &b1, &f);
+        const int y0 = sy < 0 ? 0 : (sy < H ? sy : H - 1), y1 = sy + 1 < 0 ? 0 : (sy + 1 < H ? sy + 1 : H - 1);
+        const int sx1 = sx + 1 < W ? sx + 1 : sx;
+        const uint8_t *r0 = src + (size_t)y0 * pitch, *r1 = src + (size_t)y1 * pitch;
+        const int h0 = r0[sx] * a0 + r0[sx1] * a1;
+        const int h1 = r1[sx] * a0 + r1[sx1] * a1;
+        v = (uint8_t)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2);
+    }
+    o[0] = v, o[1] = v, o[2] = v;
+}
+
+int enqueue_resize_linear_gray_u8(const uint8_t* d_src, int H, int W, uint8_t* d_dst, int oh, int ow, hipStream_t s, int pitch) {
+    if (pitch <= 0) pitch = W;
+    DFVO_ARG_CHECK(d_src && d_dst && H > 0 && W > 0 && oh > 0 && ow > 0 && pitch >= W, "resize_linear_gray_u8: bad argument");
+    volatile double inv_x = (double)ow / (double)W, inv_y = (double)oh / (double)H;
+    const double scale_x = 1.0 / inv_x, scale_y = 1.0 / inv_y;
+    const int area2 = (std::fabs(scale_x - 2.0) < 2.220446049250313e-16 && std::fabs(scale_y - 2.0) < 2.220446049250313e-16) ? 1 : 0;
+    hipLaunchKernelGGL(k_resize_linear_gray_u8, dim3(cdiv(ow, 64), cdiv(oh, 4)), dim3(64, 4), 0, s, d_src, H, W, pitch, d_dst, oh, ow,
+                       scale_x, scale_y, area2);
+    DFVO_HIP_CHECK(hipGetLastError());
+    return DFVO_OK;
+}
+
 }  // namespace dfvo

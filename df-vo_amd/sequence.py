@@ -32,7 +32,11 @@ def track_chunk(pipe, frames, lo, hi, seed=4869, rng_mode="sequential", ahead=3,
     depths (a pipeline of depth_source "external", depth.depth_src gt): the frames' 16-bit depth images, device uint16 tensors
     indexable like `frames` (depth_to_device); the halo's depth is depths[lo], pair j tracks on depths[j + 1].
     Returns (rel [n,4,4] cur->ref motions, status [n]); status-1 rows (constant motion) hold the identity and are resolved
-    by dist.compose_trajectory once the previous pair's motion is known."""
+    by dist.compose_trajectory once the previous pair's motion is known.
+    `frames` / `depths` may stream from disk (frame_stream.FrameStream): an object with begin(lo, hi), called before the halo is
+    read (frames lo .. hi follow, in non-decreasing order), and release(k), called once the track_end of the last pair that
+    names frame k has returned -- the pipeline's lifetime rule for device frames; frames j .. j + ahead + 1 are live at once, so
+    an object with `slots` needs ahead + 2 of them.  Objects without the two methods (lists of tensors) see no other call."""
     assert rng_mode in ("sequential", "per_pair")
     n = hi - lo
     rel = np.tile(np.eye(4), (n, 1, 1))
@@ -40,6 +44,13 @@ def track_chunk(pipe, frames, lo, hi, seed=4869, rng_mode="sequential", ahead=3,
     if n <= 0:
         return rel, status
     ahead = max(1, min(ahead, SLOTS - 1))
+    streams = [s for s in (frames, depths) if callable(getattr(s, "release", None)) and callable(getattr(s, "begin", None))]
+    for s in streams:
+        if getattr(s, "slots", ahead + 2) < ahead + 2:
+            raise ValueError("a frame stream of %d slots cannot run %d pairs ahead: frames j .. j + %d are live at once, use "
+                             "slots >= %d" % (s.slots, ahead, ahead + 1, ahead + 2))
+    for s in streams:
+        s.begin(lo, hi)
     if getattr(pipe, "deep_pose", False):
         pass  # tracking_method deep_pose: no depth anywhere, the halo's included
     elif depths is None:
@@ -77,6 +88,8 @@ def track_chunk(pipe, frames, lo, hi, seed=4869, rng_mode="sequential", ahead=3,
             prev = rel[j - lo]
         if collect is not None:
             collect(j, out)
+        for s in streams:  # no later pair names frame j; the chunk's last pair was the last to name frame hi
+            s.release(j if j + 1 < hi else hi)
     pipe.sync()
     return rel, status
 

@@ -188,6 +188,35 @@ int dfvo_resize_linear_u8(const uint8_t* d_src, int H, int W, int C, uint8_t* d_
  * [out_h, out_w, 3].  PNG / JPEG entropy decoding stays on the host (bit-serial). */
 int dfvo_read_image_tail_u8(const uint8_t* d_decoded, int img_h, int img_w, int bgr, int y0, int y1, int x0, int x1, uint8_t* d_dst,
                             int out_h, int out_w, void* stream);
+/* The same tail for a 1-channel decoded frame, d_decoded uint8 [img_h, img_w] (KITTI's grey cameras; any file cv2.imread would
+ * replicate into three equal channels): d_dst uint8 [out_h, out_w, 3] holds exactly the bytes dfvo_read_image_tail_u8 writes for
+ * the replicated frame, from a third of the source bytes. */
+int dfvo_read_image_tail_gray_u8(const uint8_t* d_decoded, int img_h, int img_w, int y0, int y1, int x0, int x1, uint8_t* d_dst,
+                                 int out_h, int out_w, void* stream);
+/* Device frame ring: the upload stage of a sequence read from disk.  `slots` pinned staging buffers of capacity_bytes each with
+ * matching device buffers, one non-blocking stream of the ring's own and one event per slot.
+ * Threads: every dfvo_frame_ring_* call comes from ONE thread (the consumer, which also drives the pipeline); decoder threads only
+ * write decoded frames into the staging memory dfvo_frame_ring_staging hands out, and the caller orders those writes before the
+ * slot's submit.
+ * dfvo_frame_ring_submit_image: one asynchronous copy of the staged uint8 [img_h, img_w, channels] frame (channels 3, or 1 for a
+ * grey frame), then dfvo_read_image_tail_u8 / _gray_u8 with these arguments into d_dst uint8 [out_h, out_w, 3], then an event
+ * record; returns without waiting.  dfvo_frame_ring_submit_raw: the copy of `bytes` staged bytes straight into d_dst and the
+ * event, no kernel (the uint16 [src_h, src_w] depth images dfvo_pipeline_enqueue_nets_depth takes).  d_dst is the caller's and
+ * stays allocated until the slot's wait has returned.
+ * dfvo_frame_ring_wait: hipEventSynchronize on the slot's event -- the hand-over point of the pipeline's ordering contract below
+ * (a frame is complete when handed to dfvo_pipeline_enqueue_nets / _set_ref_image); a slot with nothing submitted returns at once.
+ * DFVO_ERR_ARG, with a message and nothing enqueued: a frame larger than the staging capacity, a slot outside the ring, a crop
+ * outside the frame, a submit on a slot whose last submit has not been waited for.
+ * dfvo_frame_ring_pending: the number of such slots.  dfvo_frame_ring_destroy synchronises the ring's stream first. */
+typedef struct dfvo_frame_ring dfvo_frame_ring;
+int dfvo_frame_ring_create(int slots, size_t capacity_bytes, dfvo_frame_ring** out);
+void dfvo_frame_ring_destroy(dfvo_frame_ring* ring);
+int dfvo_frame_ring_staging(dfvo_frame_ring* ring, int slot, void** h_staging, size_t* capacity_bytes);
+int dfvo_frame_ring_submit_image(dfvo_frame_ring* ring, int slot, int img_h, int img_w, int channels, int bgr, int y0, int y1, int x0,
+                                 int x1, uint8_t* d_dst, int out_h, int out_w);
+int dfvo_frame_ring_submit_raw(dfvo_frame_ring* ring, int slot, size_t bytes, void* d_dst);
+int dfvo_frame_ring_wait(dfvo_frame_ring* ring, int slot);
+int dfvo_frame_ring_pending(dfvo_frame_ring* ring, int* n_pending);
 int dfvo_resize_bilinear(const float* d_src, int N, int H, int W, int C, float* d_dst, int Ho, int Wo,
                          int align_corners, void* stream);
 
