@@ -31,7 +31,7 @@ _SCALE_METHOD = {"depth_ratio": 0, "abs_diff": 1}
 _TRACKING = {"hybrid": 0, "PnP": 1, "deep_pose": 2}
 
 # dfvo_pipeline_set_iterative: scale_recovery.method and the kp_selection.rigid_flow_kp block (ablation_scale_iterative.yml).
-# Kept apart from OPTION_DEFAULTS, whose keys are the fields of capi.PipelineOpts
+# One table per option block of the library (_split_options deals an override dict out to them)
 ITER_DEFAULTS = dict(scale_recovery="simple", iter_kp_src="kp_best", rigid_num_bestN=2000, rigid_num_row=10, rigid_num_col=10,
                      rigid_flow_thre=5.0, optical_flow_thre=0.1)
 _SCALE_RECOVERY = {"simple": 0, "iterative": 1}
@@ -40,15 +40,30 @@ ITER_STATUS = {0: "finished", 1: "empty_selection", 2: "no_consensus", 3: "not_r
 
 # dfvo_pipeline_set_depth_source: depth.depth_src.  "external" (depth_src: gt) tracks on a 16-bit depth image per frame in the
 # place of the depth net; depth_scale is the loader's scale_factor of read_depth (500 kitti.py, 5000 tum.py / kinect.py: not in
-# the reference's YAML), depth_size the (height, width) of those images, None = the image size.  A third table, apart from the
-# other two
+# the reference's YAML), depth_size the (height, width) of those images, None = the image size
 DEPTH_DEFAULTS = dict(depth_source="net", depth_scale=None, depth_size=None)
 _DEPTH_SOURCE = {"net": capi.DEPTH_NET, "external": capi.DEPTH_EXTERNAL}
 
 
 # dfvo_pipeline_set_pose_net: deep_pose.enable (monodepth2's two-frame pose net on the depth stream) and what reads its pose --
-# kp_selection.depth_consistency (enable, thre) here, tracking_method "deep_pose" among the option keys.  A fourth table
+# kp_selection.depth_consistency (enable, thre) here, tracking_method "deep_pose" among the option keys
 POSE_DEFAULTS = dict(pose_net=False, depth_consistency=False, depth_consistency_thre=0.05)
+
+_NUMBER = (int, float, np.integer, np.floating)
+
+
+def _ptr(t):
+    """the device (or host) pointer of a tensor for the C ABI; None stays NULL"""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _split_options(overrides):
+    """an override dict as the four blocks (DEFAULTS + OPTION_DEFAULTS, ITER_DEFAULTS, DEPTH_DEFAULTS, POSE_DEFAULTS), each with
+    its defaults filled in; a key of none of the last three goes to the first"""
+    blocks = [dict(DEFAULTS, **OPTION_DEFAULTS), dict(ITER_DEFAULTS), dict(DEPTH_DEFAULTS), dict(POSE_DEFAULTS)]
+    for k, v in overrides.items():
+        next((b for b in blocks[1:] if k in b), blocks[0])[k] = v
+    return blocks
 
 
 def _choice(o, key, table):
@@ -58,15 +73,27 @@ def _choice(o, key, table):
     return table[v]
 
 
+def _positive_int(key, v, numbers_only=True):
+    """`v` as an int; ValueError naming `key` unless it is a whole number >= 1 (numbers_only=False: whatever int() takes)"""
+    if isinstance(v, bool) or (numbers_only and not isinstance(v, _NUMBER)) or int(v) != v or v < 1:
+        raise ValueError("%s = %r: a positive integer" % (key, v))
+    return int(v)
+
+
+def _finite(key, v, what="a finite threshold", refused=(bool, str), numbers_only=False):
+    """`v` as a float; ValueError naming `key` for None, the `refused` types, with numbers_only anything but a number, and what
+    float() does not make finite"""
+    if v is None or isinstance(v, refused) or (numbers_only and not isinstance(v, _NUMBER)) or not np.isfinite(float(v)):
+        raise ValueError("%s = %r: %s" % (key, v, what))
+    return float(v)
+
+
 def check_options(o):
     """the option keys of `o` (OPTION_DEFAULTS filled in) as the fields of capi.PipelineOpts; ValueError on a bad value"""
     f = dict(kp_source=_choice(o, "kp_source", _KP_SOURCE), kp_score_method=_choice(o, "kp_score_method", _KP_SCORE),
              validity_method=_choice(o, "validity", _VALIDITY), scale_method=_choice(o, "scale_method", _SCALE_METHOD),
              tracking_method=_choice(o, "tracking_method", _TRACKING))
-    num = o["kp_sampled_num"]
-    if isinstance(num, bool) or int(num) != num or num < 1:
-        raise ValueError("kp_sampled_num = %r: a positive integer" % (num,))
-    f["kp_sampled_num"] = int(num)
+    f["kp_sampled_num"] = _positive_int("kp_sampled_num", o["kp_sampled_num"], numbers_only=False)
     try:
         (y0, y1), (x0, x1) = o["flow_crop"]
         crop = [float(v) for v in (y0, y1, x0, x1)]
@@ -75,12 +102,9 @@ def check_options(o):
     if not (0.0 <= crop[0] < crop[1] <= 1.0 and 0.0 <= crop[2] < crop[3] <= 1.0):
         raise ValueError("flow_crop = %r: 0 <= y0 < y1 <= 1 and 0 <= x0 < x1 <= 1" % (o["flow_crop"],))
     f["flow_crop"] = crop
-    thre = o["validity_thre"]
-    if o["validity"] == "GRIC":
-        thre = 0.0  # (unused: E_tracker.py:196-205)
-    elif thre is None or isinstance(thre, bool) or not np.isfinite(float(thre)):
-        raise ValueError("validity_thre = %r: validity %r needs a finite threshold" % (thre, o["validity"]))
-    f["validity_thre"] = float(thre)
+    f["validity_thre"] = 0.0  # (unused under GRIC: E_tracker.py:196-205)
+    if o["validity"] != "GRIC":
+        f["validity_thre"] = _finite("validity_thre", o["validity_thre"], "validity %r needs a finite threshold" % (o["validity"],), refused=bool)
     return f
 
 
@@ -88,15 +112,9 @@ def check_iter_options(o):
     """the iterative-scale keys of `o` (ITER_DEFAULTS filled in) as the fields of capi.PipelineIterOpts; ValueError on a bad value"""
     f = dict(enable=_choice(o, "scale_recovery", _SCALE_RECOVERY), kp_src=_choice(o, "iter_kp_src", _ITER_KP_SRC))
     for key, field in (("rigid_num_bestN", "num_bestN"), ("rigid_num_row", "num_row"), ("rigid_num_col", "num_col")):
-        v = o[key]
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or v < 1:
-            raise ValueError("%s = %r: a positive integer" % (key, v))
-        f[field] = int(v)
+        f[field] = _positive_int(key, o[key])
     for key in ("rigid_flow_thre", "optical_flow_thre"):
-        v = o[key]
-        if v is None or isinstance(v, (bool, str)) or not np.isfinite(float(v)):
-            raise ValueError("%s = %r: a finite threshold" % (key, v))
-        f[key] = float(v)
+        f[key] = _finite(key, o[key])
     if f["num_bestN"] < f["num_row"] * f["num_col"]:
         raise ValueError("rigid_num_bestN = %r: fewer than one keypoint per cell of the %d x %d grid (rigid_num_row, rigid_num_col)"
                          % (o["rigid_num_bestN"], f["num_row"], f["num_col"]))
@@ -112,19 +130,17 @@ def check_depth_options(o, img_h=None, img_w=None):
             sh, sw = size
         except (TypeError, ValueError):
             raise ValueError("depth_size = %r: (height, width) of the depth images, or None for the image size" % (size,))
-        for v in (sh, sw):
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or v < 1:
-                raise ValueError("depth_size = %r: two positive integers" % (size,))
-        f["src_h"], f["src_w"] = int(sh), int(sw)
+        try:
+            f["src_h"], f["src_w"] = _positive_int("depth_size", sh), _positive_int("depth_size", sw)
+        except ValueError:
+            raise ValueError("depth_size = %r: two positive integers" % (size,)) from None
     elif img_h is not None:
         f["src_h"], f["src_w"] = int(img_h), int(img_w)
     if o["depth_source"] == "external":
-        v = o["depth_scale"]
-        if v is None or isinstance(v, (bool, str)) or not isinstance(v, (int, float, np.integer, np.floating)) \
-                or not np.isfinite(float(v)) or v <= 0:
-            raise ValueError("depth_scale = %r: depth_source 'external' needs the depth images' scale factor, finite and > 0 "
-                             "(read_depth: 500 for KITTI, 5000 for TUM)" % (v,))
-        f["scale"] = float(v)
+        what = "depth_source 'external' needs the depth images' scale factor, finite and > 0 (read_depth: 500 for KITTI, 5000 for TUM)"
+        f["scale"] = _finite("depth_scale", o["depth_scale"], what, numbers_only=True)
+        if f["scale"] <= 0:
+            raise ValueError("depth_scale = %r: %s" % (o["depth_scale"], what))
     return f
 
 
@@ -133,14 +149,12 @@ def check_pose_options(o, kp_source="local_bestN"):
     for key in ("pose_net", "depth_consistency"):
         if not isinstance(o[key], (bool, np.bool_)):
             raise ValueError("%s = %r: True or False" % (key, o[key]))
-    v = o["depth_consistency_thre"]
-    if v is None or isinstance(v, (bool, str)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(float(v)):
-        raise ValueError("depth_consistency_thre = %r: a finite threshold" % (v,))
+    thre = _finite("depth_consistency_thre", o["depth_consistency_thre"], numbers_only=True)
     if o["depth_consistency"] and not o["pose_net"]:
         raise ValueError("depth_consistency = True without pose_net: the mask is computed from the pose net's pose")
     if o["depth_consistency"] and kp_source != "local_bestN":
         raise ValueError("depth_consistency = True with kp_source = %r: the reference masks local_bestN only" % (kp_source,))
-    return dict(enable=int(o["pose_net"]), depth_consistency=int(o["depth_consistency"]), depth_thre=float(v))
+    return dict(enable=int(o["pose_net"]), depth_consistency=int(o["depth_consistency"]), depth_thre=thre)
 
 
 def options_from_cfg(cfg):
@@ -249,35 +263,18 @@ def options_from_cfg(cfg):
                                   % (depth_src,))
     if mask:
         full.update(pose_net=True, depth_consistency=True, depth_consistency_thre=get("kp_selection.depth_consistency.thre", 0.05))
-    base = dict(DEFAULTS)
-    base.update(OPTION_DEFAULTS)
-    base.update(ITER_DEFAULTS)
-    base.update(DEPTH_DEFAULTS)
-    base.update(POSE_DEFAULTS)
+    base = {k: v for block in _split_options({}) for k, v in block.items()}
     out = {k: v for k, v in full.items() if base.get(k) != v}
-    check = dict(OPTION_DEFAULTS)
-    check.update({k: v for k, v in out.items() if k in OPTION_DEFAULTS})
-    check_options(check)
-    check = dict(ITER_DEFAULTS)
-    check.update({k: v for k, v in out.items() if k in ITER_DEFAULTS})
-    check_iter_options(check)
-    check = dict(POSE_DEFAULTS)
-    check.update({k: v for k, v in out.items() if k in POSE_DEFAULTS})
-    check_pose_options(check, source)
+    o, io, _, po = _split_options(out)
+    check_options(o)
+    check_iter_options(io)
+    check_pose_options(po, source)
     return out
 
 
 class TrackingPipeline:
     def __init__(self, img_h, img_w, feed_h, feed_w, K, flow_sd, depth_sd, pose_sd=None, **overrides):
-        o = dict(DEFAULTS)
-        o.update(OPTION_DEFAULTS)
-        io = dict(ITER_DEFAULTS)
-        io.update({k: overrides.pop(k) for k in list(overrides) if k in ITER_DEFAULTS})
-        do = dict(DEPTH_DEFAULTS)
-        do.update({k: overrides.pop(k) for k in list(overrides) if k in DEPTH_DEFAULTS})
-        po = dict(POSE_DEFAULTS)
-        po.update({k: overrides.pop(k) for k in list(overrides) if k in POSE_DEFAULTS})
-        o.update(overrides)
+        o, io, do, po = _split_options(overrides)
         fields = check_options(o)  # (before anything touches the device: a bad value is a ValueError)
         iter_fields = check_iter_options(io)
         depth_fields = check_depth_options(do, img_h, img_w)
@@ -325,33 +322,17 @@ class TrackingPipeline:
         capi.check(self.lib.dfvo_pipeline_create(C.byref(cfg), C.byref(h)))
         self.h = h
         if self.external_depth:  # (a pipeline of the depth net makes no call here: it enqueues what it always did)
-            try:
-                capi.check(self.lib.dfvo_pipeline_set_depth_source(h, C.byref(capi.PipelineDepthSrc(**depth_fields))))
-            except capi.DfvoError:
-                self.close()
-                raise
+            self._apply(self.lib.dfvo_pipeline_set_depth_source, capi.PipelineDepthSrc(**depth_fields))
         if po["pose_net"]:  # (ahead of set_options, which takes tracking_method deep_pose only behind it)
-            try:
-                capi.check(self.lib.dfvo_pipeline_set_pose_net(h, C.byref(capi.PipelinePoseOpts(**pose_fields))))
-            except capi.DfvoError:
-                self.close()
-                raise
+            self._apply(self.lib.dfvo_pipeline_set_pose_net, capi.PipelinePoseOpts(**pose_fields))
         if any(o[k] != v for k, v in OPTION_DEFAULTS.items()):
             crop = fields.pop("flow_crop")
             popts = capi.PipelineOpts(**fields)
             for i, v in enumerate(crop):
                 popts.flow_crop[i] = v
-            try:
-                capi.check(self.lib.dfvo_pipeline_set_options(h, C.byref(popts)))
-            except capi.DfvoError:
-                self.close()
-                raise
+            self._apply(self.lib.dfvo_pipeline_set_options, popts)
         if self.iterative:  # (behind set_options: the bound on the tracked keypoints depends on the keypoint source)
-            try:
-                capi.check(self.lib.dfvo_pipeline_set_iterative(h, C.byref(capi.PipelineIterOpts(**iter_fields))))
-            except capi.DfvoError:
-                self.close()
-                raise
+            self._apply(self.lib.dfvo_pipeline_set_iterative, capi.PipelineIterOpts(**iter_fields))
         # keypoints a pair can have (get_keypoints' default capacity)
         self.kp_max = {"local_bestN": o["kp_num_bestN"], "bestN": o["kp_num_bestN"], "sampled": o["kp_sampled_num"]}[o["kp_source"]]
         nh, nw = self._net_size(img_h, img_w)
@@ -383,6 +364,14 @@ class TrackingPipeline:
         from .synthetic import _net_size
         return _net_size(h, w)
 
+    def _apply(self, fn, struct):
+        """one of the library's option setters on the new pipeline; a refusal closes it before the DfvoError goes on"""
+        try:
+            capi.check(fn(self.h, C.byref(struct)))
+        except capi.DfvoError:
+            self.close()
+            raise
+
     def close(self):
         if self.h is not None:
             self.lib.dfvo_pipeline_destroy(self.h)
@@ -412,38 +401,34 @@ class TrackingPipeline:
         depth (depth_source "external": required there, refused otherwise): the current frame's 16-bit depth image, a device
         uint16 tensor [src_h, src_w] (depth_size), under the frames' contract: complete when handed over, unchanged until
         the slot's track / track_end has returned.  d_feed has no reader then and is refused."""
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         if depth is not None:
             dp = self._depth_image(depth, "enqueue_nets")
             if d_feed is not None:
                 raise capi.DfvoError("enqueue_nets: d_feed beside a depth image: the depth net it would feed does not run")
-            capi.check(self.lib.dfvo_pipeline_enqueue_nets_depth(self.h, slot, p(d_ref), p(d_cur), dp))
+            capi.check(self.lib.dfvo_pipeline_enqueue_nets_depth(self.h, slot, _ptr(d_ref), _ptr(d_cur), dp))
             return
-        capi.check(self.lib.dfvo_pipeline_enqueue_nets(self.h, slot, p(d_ref), p(d_cur), p(d_feed)))
+        capi.check(self.lib.dfvo_pipeline_enqueue_nets(self.h, slot, _ptr(d_ref), _ptr(d_cur), _ptr(d_feed)))
 
     def prefetch_track(self, slot, flow=None, diff=None):
         """enqueue keypoint selection + the homography chain of `slot` now (call right after enqueue_nets(slot));
         track(slot) then only runs the RandomState consumers"""
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        capi.check(self.lib.dfvo_pipeline_prefetch_track(self.h, slot, p(flow), p(diff)))
+        capi.check(self.lib.dfvo_pipeline_prefetch_track(self.h, slot, _ptr(flow), _ptr(diff)))
 
     def track(self, slot, flow=None, diff=None, depth=None, raw_depth=None):
         """raw_depth (iterative scale recovery, with `depth`): the raw float32 depth of the current frame, which becomes the
         next pair's ref_data['raw_depth'] in place of the depth net's"""
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         if raw_depth is not None:
             self.set_raw_depth_override(slot, raw_depth)
         out = capi.TrackOut()
-        capi.check(self.lib.dfvo_pipeline_track(self.h, slot, p(flow), p(diff), p(depth), C.byref(out)))
+        capi.check(self.lib.dfvo_pipeline_track(self.h, slot, _ptr(flow), _ptr(diff), _ptr(depth), C.byref(out)))
         return out
 
     def track_begin(self, slot, flow=None, diff=None, depth=None, raw_depth=None):
         """first half of track(): enqueues the RandomState-ordered chain of `slot` and returns; the host can feed the nets of
         the pairs ahead while it runs.  Pair k + 1 must not be begun before track_end(k) returned."""
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         if raw_depth is not None:
             self.set_raw_depth_override(slot, raw_depth)
-        capi.check(self.lib.dfvo_pipeline_track_begin(self.h, slot, p(flow), p(diff), p(depth)))
+        capi.check(self.lib.dfvo_pipeline_track_begin(self.h, slot, _ptr(flow), _ptr(diff), _ptr(depth)))
 
     def track_end(self, slot):
         out = capi.TrackOut()
@@ -453,21 +438,18 @@ class TrackingPipeline:
     def set_ref_depth(self, d_feed=None, depth=None, raw_depth=None):
         """depth of the first reference frame: the uint8 feed image (runs the depth net) or a processed depth map; raw_depth
         (with `depth`, iterative scale recovery): its raw float32 depth, ref_data['raw_depth'] of the first pair"""
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        capi.check(self.lib.dfvo_pipeline_set_ref_depth(self.h, p(d_feed), p(depth)))
+        capi.check(self.lib.dfvo_pipeline_set_ref_depth(self.h, _ptr(d_feed), _ptr(depth)))
         if raw_depth is not None:
-            capi.check(self.lib.dfvo_pipeline_set_ref_raw_depth(self.h, p(raw_depth)))
+            capi.check(self.lib.dfvo_pipeline_set_ref_raw_depth(self.h, _ptr(raw_depth)))
 
     def set_raw_depth_override(self, slot, raw_depth):
         """the raw float32 depth [H,W] of `slot`'s current frame for the roll-over, until the slot's track_end (None withdraws)"""
-        capi.check(self.lib.dfvo_pipeline_set_raw_depth_override(
-            self.h, slot, C.c_void_p(raw_depth.data_ptr()) if raw_depth is not None else None))
+        capi.check(self.lib.dfvo_pipeline_set_raw_depth_override(self.h, slot, _ptr(raw_depth)))
 
     def set_pose_override(self, slot, pose16):
         """a device float32 4x4 (contiguous) that the pair enqueued into `slot` next uses in the place of the pose net's; set
         before the slot's enqueue_nets, unchanged until its track_end, which withdraws it (as None does)"""
-        capi.check(self.lib.dfvo_pipeline_set_pose_override(
-            self.h, slot, C.c_void_p(pose16.data_ptr()) if pose16 is not None else None))
+        capi.check(self.lib.dfvo_pipeline_set_pose_override(self.h, slot, _ptr(pose16)))
 
     def get_pose_net(self, slot):
         """(pose [4,4] f32, depth_diff [H,W] f32 or None without the mask): what the slot's last pair used"""
@@ -507,7 +489,7 @@ class TrackingPipeline:
 
     def set_ref_image(self, d_img):
         """depth of the first reference frame from the full-size uint8 frame (device LANCZOS resize + depth net)"""
-        capi.check(self.lib.dfvo_pipeline_set_ref_image(self.h, C.c_void_p(d_img.data_ptr())))
+        capi.check(self.lib.dfvo_pipeline_set_ref_image(self.h, _ptr(d_img)))
 
     def sync(self):
         capi.check(self.lib.dfvo_pipeline_sync(self.h))

@@ -1,5 +1,6 @@
-// Stand-alone check of the host-only half of dfvo_pipeline_set_iterative (df-vo_amd/csrc/pipeline_iter.h): the option block's
-// refusals, the keypoint counts of the loop's scale stage, the rigid-flow keypoint configuration and the "not run" record.
+// Stand-alone check of the host-only half of dfvo_pipeline_set_iterative (df-vo_amd/csrc/pipeline_iter.h and, through it,
+// pipeline_setup.h): the option block's refusals, the keypoint counts of the loop's scale stage, the rigid-flow keypoint
+// configuration and the "not run" record.
 // No HIP library: hip_stub.h stands in for the entry points the included headers name.  Built with
 // -fsanitize=address,undefined and run by tests/test_pipeline_iter_host_cpu.py; exit status 0 = every check holds.
 #include "hip_stub.h"

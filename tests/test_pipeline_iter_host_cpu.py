@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "..", "df-vo_amd", "csrc")
 SRC = os.path.join(HERE, "host_harness", "pipeline_iter_check.cpp")
 DEPS = [SRC, os.path.join(HERE, "host_harness", "hip_stub.h"), os.path.join(HERE, "..", "include", "dfvo_hip.h")] + [
-    os.path.join(CSRC, n) for n in ("pipeline_iter.h", "tracker.h", "solver.h", "dev_mem.h", "dfvo_common.h")]
+    os.path.join(CSRC, n) for n in ("pipeline_iter.h", "pipeline_setup.h", "tracker.h", "solver.h", "dev_mem.h", "dfvo_common.h")]
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 

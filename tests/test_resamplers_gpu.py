@@ -113,7 +113,7 @@ def test_depth_post_answers_zero_for_non_finite_depth(gpu):
 
 
 def test_pipeline_depth_post_resamples_to_the_frame(gpu, conv_precision):
-    """enqueue_depth_post (feed 192x640 -> frame 200x664, a crop with all four sides inside the frame): the pipeline's raw /
+    """enqueue_depth (feed 192x640 -> frame 200x664, a crop with all four sides inside the frame): the pipeline's raw /
     processed depth are the resize and preprocess_depth of the depth net's own output on the same feed image"""
     h, w = 192 + 8, 640 + 24
     crop = RC.crop_fractions("inner", h, w)
