@@ -204,6 +204,11 @@ SIGNATURES = {
     "dfvo_frame_ring_submit_raw": (_i, [_vp, _i, _sz, _vp]),
     "dfvo_frame_ring_wait": (_i, [_vp, _i]),
     "dfvo_frame_ring_pending": (_i, [_vp, _ip]),
+    "dfvo_undistort_create": (_i, [_i, _i, _vp, C.POINTER(_vp)]),
+    "dfvo_undistort_destroy": (None, [_vp]),
+    "dfvo_undistort_mosaic_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "dfvo_undistort_rgb_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "dfvo_frame_ring_submit_mosaic": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i]),
     "dfvo_resize_bilinear": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "dfvo_flownet_create": (_i, [_i, _i, _vp, C.POINTER(_vp)]),
     "dfvo_flownet_destroy": (None, [_vp]),

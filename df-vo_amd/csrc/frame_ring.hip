@@ -8,6 +8,7 @@
 
 #include "dev_mem.h"
 #include "resize_lanczos.h"
+#include "undistort.h"
 
 using namespace dfvo;
 
@@ -20,6 +21,7 @@ struct dfvo_frame_ring {
     };
     std::vector<Slot> slots;
     size_t capacity = 0;  // bytes per slot
+    DevArr<uint8_t> rgb;  // the demosaiced, undistorted plane of a mosaic submit: one for all slots (one stream orders its uses)
     hipStream_t stream = nullptr;
 
     // every member is released here whether or not init completed (the arrays free themselves)
@@ -104,6 +106,31 @@ int dfvo_frame_ring_submit_image(dfvo_frame_ring* r, int slot, int img_h, int im
     else
         rc = dfvo_read_image_tail_u8(s.dev.p, img_h, img_w, bgr, y0, y1, x0, x1, d_dst, out_h, out_w, r->stream);
     const hipError_t e = hipEventRecord(s.done, r->stream);  // (behind the copy also when the tail's launch failed)
+    if (rc != DFVO_OK) return rc;
+    DFVO_HIP_CHECK(e);
+    return DFVO_OK;
+}
+
+int dfvo_frame_ring_submit_mosaic(dfvo_frame_ring* r, int slot, const dfvo_undistort_map* map, int pattern, int border, int img_h,
+                                  int img_w, int y0, int y1, int x0, int x1, uint8_t* d_dst, int out_h, int out_w) {
+    RING_SLOT_CHECK("dfvo_frame_ring_submit_mosaic");
+    dfvo_frame_ring::Slot& s = r->slots[slot];
+    DFVO_ARG_CHECK(!s.pending, "dfvo_frame_ring_submit_mosaic: the slot's last submit has not been waited for");
+    DFVO_ARG_CHECK(d_dst && out_h > 0 && out_w > 0, "dfvo_frame_ring_submit_mosaic: no output frame");
+    DFVO_ARG_CHECK(img_h > 0 && img_w > 0 && (size_t)img_h * (size_t)img_w <= r->capacity,
+                   "dfvo_frame_ring_submit_mosaic: the frame is larger than the staging capacity");
+    int rc = check_undistort_mosaic("dfvo_frame_ring_submit_mosaic", map, img_h, img_w, pattern, border, y0, y1, x0, x1);
+    if (rc != DFVO_OK) return rc;
+    const size_t bytes = (size_t)img_h * img_w;
+    // (a plane that has to grow is freed first, and hipFree waits for the kernels that still use it)
+    rc = r->rgb.grow(bytes * 3);
+    if (rc != DFVO_OK) return rc;
+    DFVO_HIP_CHECK(hipMemcpyAsync(s.dev.p, s.staging.p, bytes, hipMemcpyHostToDevice, r->stream));
+    // from here on the slot is in flight whatever fails: wait() drains it
+    s.pending = true;
+    rc = enqueue_undistort_mosaic(map, s.dev.p, img_h, img_w, pattern, border, y0, y1, x0, x1, r->rgb.p, r->stream);
+    if (rc == DFVO_OK) rc = dfvo_read_image_tail_u8(r->rgb.p, img_h, img_w, 0, y0, y1, x0, x1, d_dst, out_h, out_w, r->stream);
+    const hipError_t e = hipEventRecord(s.done, r->stream);
     if (rc != DFVO_OK) return rc;
     DFVO_HIP_CHECK(e);
     return DFVO_OK;

@@ -22,7 +22,11 @@ Decoding follows what cv2.imread(path) + cvtColor(BGR2RGB) hand read_image (libs
 L through the grey tail (dfvo_read_image_tail_gray_u8: a third of the upload), P / RGBA / LA through convert("RGB") (alpha
 dropped); 16-bit images are refused by name.  PNG is lossless, so the frames are exactly read_image's.  JPEG: Pillow and OpenCV
 both decode with libjpeg, but of versions and IDCT / upsampling settings this project does not pin -- parity of JPEG frames
-with the reference's is NOT established."""
+with the reference's is NOT established.
+
+Raw frames (mosaic="gbrg", undistort=UndistortMap or None, border): a mode-L file is then an 8-bit Bayer mosaic, staged and
+uploaded as it is; the ring demosaics and undistorts the crop's pixels on the device (dfvo_frame_ring_submit_mosaic, undistort.py)
+ahead of the same read-image tail.  Any other mode is refused by name: a mosaic has one channel."""
 import ctypes as C
 import operator
 import threading
@@ -69,6 +73,12 @@ class FrameRing:
         capi.check(self.lib.dfvo_frame_ring_submit_image(self.h, slot, h, w, channels, 0, box[0], box[1], box[2], box[3],
                                                          C.c_void_p(out.data_ptr()), out.shape[0], out.shape[1]))
 
+    def submit_mosaic(self, slot, umap, pattern, border, h, w, box, out):
+        from . import undistort as ud
+        capi.check(self.lib.dfvo_frame_ring_submit_mosaic(self.h, slot, None if umap is None else umap.handle, ud.pattern_code(pattern),
+                                                          ud.border_code(border), h, w, box[0], box[1], box[2], box[3],
+                                                          C.c_void_p(out.data_ptr()), out.shape[0], out.shape[1]))
+
     def submit_raw(self, slot, nbytes, out):
         capi.check(self.lib.dfvo_frame_ring_submit_raw(self.h, slot, nbytes, C.c_void_p(out.data_ptr())))
 
@@ -104,8 +114,9 @@ def probe(path):
     return h, w, per
 
 
-def decode(path, kind, staging):
-    """decode `path` into the flat uint8 array `staging`; (h, w, channels).  Raises FrameStreamError naming the path."""
+def decode(path, kind, staging, mosaic=False):
+    """decode `path` into the flat uint8 array `staging`; (h, w, channels).  Raises FrameStreamError naming the path.
+    mosaic: the file is a raw 8-bit Bayer frame -- mode L, or refused."""
     from PIL import Image
     try:
         with Image.open(path) as im:
@@ -123,6 +134,8 @@ def decode(path, kind, staging):
                 if im.mode.startswith("I") or im.mode == "F" or ";16" in _png_rawmode(im):
                     raise ValueError("mode %s (%s): 16-bit images are not read (cv2.imread would scale them to 8 bits)"
                                      % (im.mode, _png_rawmode(im) or "16-bit"))
+                if mosaic and im.mode != "L":
+                    raise ValueError("mode %s: a Bayer mosaic is a 1-channel 8-bit file (mode L)" % im.mode)
                 if im.mode in ("P", "RGBA", "LA"):
                     im = im.convert("RGB")
                 elif im.mode not in ("RGB", "L"):
@@ -154,11 +167,17 @@ class FrameStream:
     pipeline's).  A tensor handed out is valid until release() of its frame, begin() or close().
     A file that is missing, corrupt, of a refused mode or larger than the staging capacity raises FrameStreamError at the
     __getitem__ of its frame; frames before it are not affected.
+    mosaic ("rggb", "bggr", "grbg" or "gbrg"; kind "image"): the files are 8-bit Bayer mosaics of that pattern -- mode L, any
+    other mode raises FrameStreamError at its frame; frames[k] is then read_image's crop and resize of the demosaiced frame,
+    undistorted through `undistort` (an undistort.UndistortMap of the files' size, which the caller closes after the stream; None:
+    demosaic only), the mosaic extended over the border by `border` ("reflect" or "mirror"; include/dfvo_hip.h).  Without
+    `mosaic` an L file is a grey frame and nothing changes.
     capacity: bytes per staging slot (default: the first readable file's decoded size).  ring: the ring object (tests).
     close() stops and joins the workers and destroys the ring; call it after pipe.sync() (the pipeline may still read the
     frames it was handed), or use the stream as a context manager around run_sequence, which ends with pipe.sync()."""
 
-    def __init__(self, paths, out_h, out_w, crop=None, slots=12, workers=6, kind="image", capacity=None, ring=None):
+    def __init__(self, paths, out_h, out_w, crop=None, slots=12, workers=6, kind="image", capacity=None, ring=None,
+                 mosaic=None, undistort=None, border="reflect"):
         if kind not in KINDS:
             raise ValueError("kind: %r: one of %s" % (kind, ", ".join(KINDS)))
         if not (isinstance(workers, int) and 1 <= workers <= MAX_WORKERS):
@@ -167,6 +186,16 @@ class FrameStream:
             raise ValueError("slots: %r: at least 1" % (slots,))
         if crop is not None and kind != "image":
             raise ValueError("crop: read_image's, not for kind %s" % kind)
+        if mosaic is None:
+            if undistort is not None or border != "reflect":
+                raise ValueError("undistort / border: arguments of a mosaic stream (mosaic=<pattern>)")
+        else:
+            from . import undistort as ud
+            if kind != "image":
+                raise ValueError("mosaic: an image stream's, not for kind %s" % kind)
+            mosaic = ud.PATTERNS[ud.pattern_code(mosaic)]
+            ud.border_code(border)
+        self.mosaic, self.undistort, self.border = mosaic, undistort, border
         self.paths = [str(p) for p in paths]
         self.out_h, self.out_w, self.crop, self.kind, self.slots = int(out_h), int(out_w), crop, kind, slots
         if capacity is None:
@@ -192,10 +221,10 @@ class FrameStream:
         for p in self.paths[:8]:
             try:
                 h, w, per = probe(p)
-                return h * w * max(per, 3)
+                return h * w * (1 if self.mosaic else max(per, 3))
             except Exception:
                 continue
-        return self.out_h * self.out_w * 3
+        return self.out_h * self.out_w * (1 if self.mosaic else 3)
 
     def __len__(self):
         return len(self.paths)
@@ -222,7 +251,7 @@ class FrameStream:
                 self.max_live = max(self.max_live, self.slots - len(self._free))
             meta = error = None
             try:
-                meta = decode(self.paths[k], self.kind, self._ring.staging(e.slot))
+                meta = decode(self.paths[k], self.kind, self._ring.staging(e.slot), mosaic=self.mosaic is not None)
                 if self.kind == "depth_u16" and meta[:2] != (self.out_h, self.out_w):
                     raise FrameStreamError("%s: %d x %d: the stream's depth images are %d x %d" % ((self.paths[k],) + meta[:2] + (self.out_h, self.out_w)))
             except BaseException as ex:
@@ -301,7 +330,10 @@ class FrameStream:
             box = (0, h, 0, w)
             if self.crop is not None:  # utils.py:46-50
                 box = (int(h * self.crop[0][0]), int(h * self.crop[0][1]), int(w * self.crop[1][0]), int(w * self.crop[1][1]))
-            self._ring.submit_image(e.slot, h, w, ch, box, out)
+            if self.mosaic is not None:
+                self._ring.submit_mosaic(e.slot, self.undistort, self.mosaic, self.border, h, w, box, out)
+            else:
+                self._ring.submit_image(e.slot, h, w, ch, box, out)
         else:
             self._ring.submit_raw(e.slot, h * w * 2, out)
         e.state = "submitted"

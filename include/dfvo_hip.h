@@ -217,6 +217,39 @@ int dfvo_frame_ring_submit_image(dfvo_frame_ring* ring, int slot, int img_h, int
 int dfvo_frame_ring_submit_raw(dfvo_frame_ring* ring, int slot, size_t bytes, void* d_dst);
 int dfvo_frame_ring_wait(dfvo_frame_ring* ring, int slot);
 int dfvo_frame_ring_pending(dfvo_frame_ring* ring, int* n_pending);
+/* Raw camera frames: bilinear Bayer demosaic and undistortion through a per-pixel table, in one launch (what the RobotCar SDK does on
+ * the host: sdk_python/image.py load_image = demosaicing_CFA_Bayer_bilinear, camera_model.py undistort = scipy.ndimage.map_coordinates
+ * of order 1 per channel, astype(uint8)).  Only the pixels of the box [y0, y1) x [x0, x1) of d_rgb uint8 [h, w, 3] are written -- the
+ * crop the read-image tail will read; the rest of the plane is left as it is.
+ * Demosaic: plane P_c holds the mosaic where the site's colour is c and 0 elsewhere; `pattern` names the colours of sites (0,0),
+ * (0,1), (1,0), (1,1).  R and B are P convolved with [[1,2,1],[2,4,2],[1,2,1]] / 4, G with [[0,1,0],[1,4,1],[0,1,0]] / 4, the plane
+ * extended over the border by `border`: DFVO_BORDER_REFLECT maps -1 -> 0 and n -> n - 1 (scipy.ndimage.convolve's default),
+ * DFVO_BORDER_MIRROR -1 -> 1 and n -> n - 2 (needs h, w >= 2).  Every value is a multiple of 1/4, exact.  Under REFLECT the
+ * one-pixel frame of a plane can exceed 255 (a site counted twice); its byte is the truncated value's low 8 bits.
+ * Remap: the table holds, for every output pixel, the (x, y) of its sample in the source frame V (the demosaiced mosaic, float64,
+ * or the distorted uint8 RGB frame).  Outside 0 <= y <= h - 1, 0 <= x <= w - 1 the pixel is 0 on all channels; else with
+ * fy = floor(y), ty = y - fy, wy = {1 - ty, ty} (x alike): t = 0; for a, b in (0, 1): c = V[min(fy + a, h - 1)][min(fx + b, w - 1)];
+ * c = c * wy[a]; c = c * wx[b]; t = t + c -- float64, every operation rounded once, nothing contracted; the byte is t truncated.
+ * dfvo_undistort_create: map_xy float64 [2][h * w] on the host, the x coordinates then the y coordinates, row-major -- the layout
+ * of the SDK's <camera>_distortion_lut.bin; kept on the device interleaved.  A non-finite entry is DFVO_ERR_ARG.
+ * dfvo_undistort_mosaic_u8: d_mosaic uint8 [img_h, img_w]; map NULL = demosaic only, else a map of that size.
+ * dfvo_undistort_rgb_u8: d_src uint8 [h, w, 3] of the map's size, not d_rgb.  d_rgb is 4-byte aligned.  Asynchronous on `stream`.
+ * Argument errors are DFVO_ERR_ARG with a message, before anything is enqueued. */
+typedef struct dfvo_undistort_map dfvo_undistort_map;
+enum { DFVO_BAYER_RGGB = 0, DFVO_BAYER_BGGR = 1, DFVO_BAYER_GRBG = 2, DFVO_BAYER_GBRG = 3 };
+enum { DFVO_BORDER_REFLECT = 0, DFVO_BORDER_MIRROR = 1 };
+int dfvo_undistort_create(int h, int w, const double* map_xy, dfvo_undistort_map** out);
+void dfvo_undistort_destroy(dfvo_undistort_map* map);
+int dfvo_undistort_mosaic_u8(const dfvo_undistort_map* map, const uint8_t* d_mosaic, int img_h, int img_w, int pattern, int border,
+                             int y0, int y1, int x0, int x1, uint8_t* d_rgb, void* stream);
+int dfvo_undistort_rgb_u8(const dfvo_undistort_map* map, const uint8_t* d_src, int y0, int y1, int x0, int x1, uint8_t* d_rgb,
+                          void* stream);
+/* A staged mosaic through the ring: the asynchronous copy of the slot's uint8 [img_h, img_w] frame, dfvo_undistort_mosaic_u8 with
+ * these arguments into one RGB plane the ring owns (allocated at the first such submit; every submit runs on the ring's one
+ * stream, so one plane serves all slots), dfvo_read_image_tail_u8 of the box into d_dst uint8 [out_h, out_w, 3], the slot's event.
+ * `map` (or NULL) stays alive until the slot's wait has returned.  Errors as dfvo_frame_ring_submit_image's. */
+int dfvo_frame_ring_submit_mosaic(dfvo_frame_ring* ring, int slot, const dfvo_undistort_map* map, int pattern, int border, int img_h,
+                                  int img_w, int y0, int y1, int x0, int x1, uint8_t* d_dst, int out_h, int out_w);
 int dfvo_resize_bilinear(const float* d_src, int N, int H, int W, int C, float* d_dst, int Ho, int Wo,
                          int align_corners, void* stream);
 
