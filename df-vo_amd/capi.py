@@ -91,6 +91,18 @@ class PipelineIterOpts(C.Structure):
                 ("rigid_flow_thre", C.c_double), ("optical_flow_thre", C.c_double)]
 
 
+class PipelineRefineOpts(C.Structure):
+    _fields_ = [("e_enable", C.c_int), ("scale_enable", C.c_int), ("pnp_enable", C.c_int), ("e_score_rigid", C.c_int),
+                ("pnp_score_rigid", C.c_int), ("num_row", C.c_int), ("num_col", C.c_int), ("num_bestN", C.c_int),
+                ("rigid_flow_thre", C.c_double), ("optical_flow_thre", C.c_double)]
+
+
+class RefineOut(C.Structure):
+    _fields_ = [("e_ran", C.c_int), ("scale_ran", C.c_int), ("pnp_ran", C.c_int), ("empty", C.c_int), ("n_kp", C.c_int),
+                ("n_inliers", C.c_int), ("pnp_found1", C.c_int), ("pad", C.c_int), ("R1", C.c_double * 9), ("t1", C.c_double * 3),
+                ("scale1", C.c_double), ("scale2", C.c_double), ("pnp_R1", C.c_double * 9), ("pnp_t1", C.c_double * 3)]
+
+
 DEPTH_NET, DEPTH_EXTERNAL = 0, 1  # dfvo_pipeline_depth_src.source
 
 
@@ -280,6 +292,8 @@ SIGNATURES = {
     "dfvo_pipeline_set_ref_raw_depth": (_i, [_vp, _vp]),
     "dfvo_pipeline_set_raw_depth_override": (_i, [_vp, _i, _vp]),
     "dfvo_pipeline_get_iterative": (_i, [_vp, _i, C.POINTER(ScaleIterOut), _i, _vp, _vp, _vp]),
+    "dfvo_pipeline_set_refine": (_i, [_vp, C.POINTER(PipelineRefineOpts)]),
+    "dfvo_pipeline_get_refine": (_i, [_vp, _i, C.POINTER(RefineOut), _i, _vp, _vp, _vp, _vp]),
     "dfvo_pipeline_set_depth_source": (_i, [_vp, C.POINTER(PipelineDepthSrc)]),
     "dfvo_pipeline_enqueue_nets_depth": (_i, [_vp, _i, _vp, _vp, _vp]),
     "dfvo_pipeline_set_ref_depth_u16": (_i, [_vp, _vp]),

@@ -190,4 +190,17 @@ SM_HD void rigid_pose_inv_f32(const double* E, double scale, float* T /*16*/) {
     T[12] = T[13] = T[14] = 0.0f;
     T[15] = 1.0f;
 }
+
+// The PnP refinement's rigid_flow_pose (pnp_tracker.py:118,135-136): the tracker's pose is inv(X) of X = [Rodrigues(r) | t], and
+// compute_rigid_flow_kp inverts it again, so the RigidFlow layer receives np.linalg.inv(np.linalg.inv(X)).astype(float32).  The
+// two LU inverses leave X changed by a few float64 ulps at most, which the float32 cast removes: X itself, cast
+// (tests/test_pipeline_refine_cpu.py counts the matrices on which the two differ).  R: 3x3 row-major, t: 3.
+SM_HD void rigid_pose_f32(const double* R, const double* t, float* T /*16*/) {
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) T[r * 4 + c] = (float)R[r * 3 + c];
+        T[r * 4 + 3] = (float)t[r];
+    }
+    T[12] = T[13] = T[14] = 0.0f;
+    T[15] = 1.0f;
+}
 }  // namespace sm

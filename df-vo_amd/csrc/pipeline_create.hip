@@ -144,6 +144,7 @@ void dfvo_pipeline_destroy(dfvo_pipeline* p) {
     (void)hipDeviceSynchronize();
     for (int i = DFVO_PIPELINE_SLOTS - 1; i >= 0; i--) {
         Slot& sl = p->slots[i];
+        sl.tb2.release();
         sl.tb.release();  // (the sharing sets before slots[0].tb, whose RandomState and events they borrow)
         for (hipEvent_t e : {sl.e_flow, sl.e_depth, sl.e_pre, sl.e_res})
             if (e) (void)hipEventDestroy(e);

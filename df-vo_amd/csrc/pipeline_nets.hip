@@ -148,7 +148,7 @@ int roll_ref_depth(dfvo_pipeline* p, int slot, const double* d_depth_override) {
     DFVO_HIP_CHECK(hipStreamWaitEvent(p->s_trk(), sl.e_depth, 0));
     const double* depth = d_depth_override ? d_depth_override : sl.proc_depth.p;
     DFVO_HIP_CHECK(hipMemcpyAsync(p->ref_depth, depth, px * sizeof(double), hipMemcpyDeviceToDevice, p->s_trk()));
-    if (p->iter.enable) {
+    if (p->iter.enable || refine_rolls_raw(p)) {
         const float* raw = sl.raw_override ? sl.raw_override : sl.raw_depth.p;
         DFVO_HIP_CHECK(hipMemcpyAsync(p->ref_raw, raw, px * sizeof(float), hipMemcpyDeviceToDevice, p->s_trk()));
     }

@@ -15,6 +15,10 @@ void fill_solver_cfgs(dfvo_pipeline* p) {
         p->pose_cfg.KinvT[i] = c.KinvT[i];
         p->pose_cfg.Kinv[i] = p->pnp_cfg.inv_K[i] = c.Kinv[i];
     }
+    // a first pass of the keypoint refinement: max_ransac_iter = 3 (E_tracker.py:207, pnp_tracker.py:87, is_iterative False)
+    p->pose_cfg1 = p->pose_cfg;
+    p->pnp_cfg1 = p->pnp_cfg;
+    p->pose_cfg1.repeat = p->pnp_cfg1.repeat = 3;
 }
 
 extern "C" {
@@ -24,6 +28,7 @@ int dfvo_pipeline_set_options(dfvo_pipeline* p, const dfvo_pipeline_opts* o) {
     DFVO_ARG_CHECK(!p->started, "dfvo_pipeline_set_options: comes before the first dfvo_pipeline_enqueue_nets / _set_ref_*");
     const dfvo_pipeline_cfg& c = p->cfg;
     if (const char* why = options_refusal(c, *o, p->iter, p->pose)) return refuse(why);
+    if (const char* why = options_refine_refusal(*o, p->refine)) return refuse(why);
     // every buffer the chosen source needs at its final size, here: nothing on the per-pair path allocates (hipFree waits
     // for the whole device).  kp_count stays 0 for local_bestN, whose launcher sizes its own buffers as before
     const int kp_count = options_kp_count(c, *o);
@@ -68,6 +73,7 @@ int dfvo_pipeline_set_iterative(dfvo_pipeline* p, const dfvo_pipeline_iter_opts*
     }
     const dfvo_pipeline_cfg& c = p->cfg;
     if (const char* why = iter_opts_refusal(*o, c.scale_min_samples)) return refuse(why);
+    if (const char* why = iter_refine_refusal(*o, p->refine)) return refuse(why);
     const RigidKpConfig rc = iter_rigid_config(*o, c.fx, c.fy, c.cx, c.cy, c.Kinv);
     int cells, n_best, cap, par;
     size_t lds;
@@ -89,6 +95,48 @@ int dfvo_pipeline_set_iterative(dfvo_pipeline* p, const dfvo_pipeline_iter_opts*
     }
     p->iter = *o;
     p->iter_cfg = rc;
+    return DFVO_OK;
+}
+
+int dfvo_pipeline_set_refine(dfvo_pipeline* p, const dfvo_pipeline_refine_opts* o) {
+    DFVO_ARG_CHECK(p && o, "dfvo_pipeline_set_refine: null argument");
+    DFVO_ARG_CHECK(!p->started, "dfvo_pipeline_set_refine: comes before the first dfvo_pipeline_enqueue_nets / _set_ref_*");
+    if (const char* why = refine_opts_refusal(*o, p->opts, p->iter)) return refuse(why);
+    if (!refine_on(*o)) {
+        p->refine = {};
+        return DFVO_OK;
+    }
+    const dfvo_pipeline_cfg& c = p->cfg;
+    dfvo_pipeline_iter_opts grid = {};  // (the rigid-flow keypoint configuration is the iterative loop's: one builder)
+    grid.num_row = o->num_row, grid.num_col = o->num_col, grid.num_bestN = o->num_bestN;
+    grid.rigid_flow_thre = o->rigid_flow_thre, grid.optical_flow_thre = o->optical_flow_thre;
+    const RigidKpConfig rc = iter_rigid_config(grid, c.fx, c.fy, c.cx, c.cy, c.Kinv);
+    int cells, n_best, cap, par;
+    size_t lds;
+    DFVO_TRY(rigid_flow_kp_geometry(p->H, p->W, rc, &cells, &n_best, &cap, &lds, &par));  // the launcher's refusals
+    const int n_sel = cells * n_best;
+    DFVO_ARG_CHECK(refine_kp_count_ok(*o, n_sel),
+                   "dfvo_pipeline_set_refine: more kp_depth keypoints than the depth-ratio kernel holds in 64 KB of LDS (16384)");
+    // every buffer of the second passes at its final size, here: nothing on the per-pair path allocates.  The second buffer set
+    // gets the intrinsics now, so its first homography part finds them in place
+    const int kp_need = std::max(n_sel, 16);
+    double hk[18];
+    for (int i = 0; i < 9; i++) hk[i] = c.KinvT[i], hk[9 + i] = c.Kinv[i];
+    for (Slot& sl : p->slots) {
+        DFVO_TRY(sl.rigid.ensure(p->H, p->W, cells, n_best, cap));
+        if (!sl.tb2.kp_info) DFVO_TRY(sl.tb2.init_shared(p->slots[0].tb));
+        DFVO_TRY(sl.tb2.ensure_kp(kp_need, 1, 1));
+        DFVO_TRY(sl.tb2.grow_winner(p->H, p->W));
+        DFVO_HIP_CHECK(hipMemcpy(sl.tb2.small, hk, sizeof(hk), hipMemcpyHostToDevice));
+        memcpy(sl.tb2.h_small, hk, sizeof(hk));
+        sl.tb2.small_valid = true;
+        if (!sl.refine_final && sl.refine_final.alloc_zeroed(1)) return DFVO_ERR_HIP;
+        if (!sl.h_refine && sl.h_refine.alloc(1)) return DFVO_ERR_HIP;
+        *sl.h_refine.p = RefineHost();
+    }
+    if (o->pnp_enable && c.pnp_iters > 0) DFVO_TRY(p->pnp.ensure(std::max(p->pnp.cap, n_sel + 8), c.pnp_iters));
+    p->refine = *o;
+    p->refine_cfg = rc;
     return DFVO_OK;
 }
 

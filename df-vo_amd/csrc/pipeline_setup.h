@@ -3,6 +3,7 @@
 // in its own words.  No HIP call: tests/host_harness/pipeline_setup_check.cpp walks the combinations on the CPU.
 #pragma once
 #include "../../include/dfvo_hip.h"
+#include <initializer_list>
 
 namespace dfvo {
 
@@ -85,6 +86,53 @@ inline const char* options_refusal(const dfvo_pipeline_cfg& c, const dfvo_pipeli
     if (it.enable && !iter_kp_count_ok(it.kp_src, 0, options_kp_count(c, o)))
         return "dfvo_pipeline_set_options: more tracked keypoints than the iterative scale loop takes (16384)";
     return nullptr;
+}
+
+// dfvo_pipeline_set_refine.  An all-zero block is "off"; a block that enables nothing but is not all zero is a mistake
+inline bool refine_on(const dfvo_pipeline_refine_opts& r) { return r.e_enable || r.scale_enable || r.pnp_enable; }
+inline bool refine_all_zero(const dfvo_pipeline_refine_opts& r) {
+    return !refine_on(r) && !r.e_score_rigid && !r.pnp_score_rigid && !r.num_row && !r.num_col && !r.num_bestN &&
+           r.rigid_flow_thre == 0.0 && r.optical_flow_thre == 0.0;
+}
+// The rules between the refinement block and the iterative / option blocks, each asked by both setters
+inline bool refine_with_iterative(const dfvo_pipeline_refine_opts& r, const dfvo_pipeline_iter_opts& it) { return refine_on(r) && it.enable; }
+inline bool refine_with_deep_pose(const dfvo_pipeline_refine_opts& r, const dfvo_pipeline_opts& o) {
+    return refine_on(r) && o.tracking_method == DFVO_TRACKING_DEEP_POSE;
+}
+inline bool e_refine_without_e_tracker(const dfvo_pipeline_refine_opts& r, const dfvo_pipeline_opts& o) {  // dfvo.py:165
+    return r.e_enable && o.tracking_method == DFVO_TRACKING_PNP;
+}
+// the second scale stage shares k_scale_ratios' LDS layout: n_sel = the most kp_depth keypoints a selection returns
+inline bool refine_kp_count_ok(const dfvo_pipeline_refine_opts& r, int n_sel) { return !r.scale_enable || n_sel <= SETUP_ITER_MAX_KP; }
+
+// dfvo_pipeline_set_refine: the candidate block `r` beside the committed option and iterative blocks (the launcher's own
+// refusals come from rigid_flow_kp_geometry)
+inline const char* refine_opts_refusal(const dfvo_pipeline_refine_opts& r, const dfvo_pipeline_opts& o, const dfvo_pipeline_iter_opts& it) {
+    for (int v : {r.e_enable, r.scale_enable, r.pnp_enable, r.e_score_rigid, r.pnp_score_rigid})
+        if (v != 0 && v != 1) return "dfvo_pipeline_set_refine: the enables are 0 or 1, the scores DFVO_REFINE_SCORE_OPT_FLOW or _RIGID_FLOW";
+    if (!refine_on(r)) return refine_all_zero(r) ? nullptr : "dfvo_pipeline_set_refine: nothing enabled: the block is all zero then";
+    if (r.scale_enable && !r.e_enable)
+        return "dfvo_pipeline_set_refine: scale_enable without e_enable: the second scale stage runs behind the second E pass only";
+    if (!(r.num_row > 0 && r.num_col > 0 && r.num_bestN > 0)) return "dfvo_pipeline_set_refine: num_row, num_col, num_bestN are positive";
+    if (r.rigid_flow_thre != r.rigid_flow_thre || r.optical_flow_thre != r.optical_flow_thre)
+        return "dfvo_pipeline_set_refine: a threshold is NaN";
+    if (refine_with_iterative(r, it))
+        return "dfvo_pipeline_set_refine: not beside dfvo_pipeline_set_iterative's method (scale_recovery.method iterative)";
+    if (refine_with_deep_pose(r, o)) return "dfvo_pipeline_set_refine: tracking_method DFVO_TRACKING_DEEP_POSE runs no tracker to refine";
+    if (e_refine_without_e_tracker(r, o)) return "dfvo_pipeline_set_refine: e_enable under tracking_method DFVO_TRACKING_PNP: no E-tracker runs";
+    return nullptr;
+}
+// dfvo_pipeline_set_options / _set_iterative, behind their own rules: the candidate block beside the committed refinement block
+inline const char* options_refine_refusal(const dfvo_pipeline_opts& o, const dfvo_pipeline_refine_opts& r) {
+    if (refine_with_deep_pose(r, o)) return "dfvo_pipeline_set_options: tracking_method DFVO_TRACKING_DEEP_POSE beside dfvo_pipeline_set_refine";
+    if (e_refine_without_e_tracker(r, o))
+        return "dfvo_pipeline_set_options: tracking_method DFVO_TRACKING_PNP beside dfvo_pipeline_set_refine's e_enable: no E-tracker runs";
+    return nullptr;
+}
+inline const char* iter_refine_refusal(const dfvo_pipeline_iter_opts& it, const dfvo_pipeline_refine_opts& r) {
+    return refine_with_iterative(r, it) ? "dfvo_pipeline_set_iterative: not beside dfvo_pipeline_set_refine (the keypoint refinement runs under "
+                                          "scale_recovery.method simple)"
+                                        : nullptr;
 }
 
 inline const char* depth_source_refusal(const dfvo_pipeline_depth_src& d) {

@@ -40,6 +40,17 @@ static_assert(offsetof(ChainResult, scale) == sizeof(PoseState) && offsetof(Chai
                   sizeof(ChainResult) == sizeof(PoseState) + sizeof(ScaleResult) + sizeof(PnpResult),
               "ChainResult is the three results back to back");
 
+// dfvo_pipeline_set_refine: what a pair's refinement leaves in pinned host memory.  info2 / ctl arrive behind Slot::e_res with
+// pass one (the E selection is enqueued behind it); the rest is filled in by track_end as the second passes complete
+struct RefineHost {
+    int info2[4];  // the second pass's kp_info triple as the last selection wrote it
+    IterCtl ctl;   // the hand-over's gate: status ITER_NOT_RUN = the selection did not run
+    PoseState pose2;
+    ScaleResult scale2;
+    RefineFinal fin;
+    dfvo_refine_out rec;  // dfvo_pipeline_get_refine's record of the pair last collected
+};
+
 // a pair between dfvo_pipeline_track_begin and _end
 enum Begun {
     IDLE,            // no chain pending
@@ -71,6 +82,11 @@ struct Slot {
     const float* flow_in = nullptr;
     const float* diff_in = nullptr;
     const float* raw_override = nullptr;
+    // dfvo_pipeline_set_refine: the second passes' buffer set (own keypoint and RANSAC workspaces, slots[0].tb's RandomState), the
+    // device bookkeeping behind the second E pass, and what the pair's refinement left in pinned memory (RefineHost)
+    TrackerBuffers tb2;
+    DevArr<RefineFinal> refine_final;
+    PinnedArr<RefineHost> h_refine;
     // outputs of the nets
     DevArr<float> fwd, bwd, diff, raw_depth;
     DevArr<double> proc_depth;
@@ -103,6 +119,12 @@ struct dfvo_pipeline {
     DevArr<double> d_E_pose, d_prev_scale;
     dfvo_pipeline_iter_opts iter = {};
     RigidKpConfig iter_cfg = {};
+    // dfvo_pipeline_set_refine: all zero = no refinement.  refine_cfg: the rigid-flow keypoint configuration (score_rigid set per
+    // selection); pose_cfg1 / pnp_cfg1: pose_cfg / pnp_cfg with the 3 repeats of a first pass (is_iterative False)
+    dfvo_pipeline_refine_opts refine = {};
+    RigidKpConfig refine_cfg = {};
+    PoseConfig pose_cfg1;
+    PnpConfig pnp_cfg1;
     // PnP fallback: processed depth of the reference frame (= the previous pair's current frame)
     PnpBuffers pnp;
     DevArr<double> ref_depth;
@@ -165,6 +187,7 @@ inline int wait_roll(dfvo_pipeline* p, hipStream_t s) {
     return DFVO_OK;
 }
 
+inline bool refine_rolls_raw(const dfvo_pipeline* p) { return p->refine.e_enable || p->refine.pnp_enable; }
 void fill_solver_cfgs(dfvo_pipeline* p);                                         // pipeline_options.hip
 int finalize_pose_net(dfvo_pipeline* p);                                          // pipeline_create.hip
 int roll_ref_depth(dfvo_pipeline* p, int slot, const double* d_depth_override);  // pipeline_nets.hip

@@ -51,9 +51,71 @@ static void fill_pnp_out(const PnpResult& pr, dfvo_track_out* out) {
 
 // dfvo.py:225-250: PnP on (ref keypoints + ref depth) -> cur keypoints, on the chain's stream; p->pnp.result behind it.  The
 // reference depth is ordered on that stream by set_ref_depth / the previous pair's roll-over
-static int enqueue_pnp(dfvo_pipeline* p, Slot& sl, int n) {
-    TrackerBuffers& tb = sl.tb;
-    return enqueue_compute_pose_3d2d(p->pnp, tb.mt_state, tb.kp_ref, tb.kp_cur, tb.kp_info, n, p->ref_depth, p->H, p->W, p->pnp_cfg, p->s_trk());
+static int enqueue_pnp(dfvo_pipeline* p, TrackerBuffers& tb, int n, const PnpConfig& cfg) {
+    return enqueue_compute_pose_3d2d(p->pnp, tb.mt_state, tb.kp_ref, tb.kp_cur, tb.kp_info, n, p->ref_depth, p->H, p->W, cfg, p->s_trk());
+}
+// the first PnP pass of a pair: 3 repeats when a second one follows (pnp_tracker.py:87)
+static int enqueue_pnp_first(dfvo_pipeline* p, Slot& sl, int n) {
+    return enqueue_pnp(p, sl.tb, n, p->refine.pnp_enable ? p->pnp_cfg1 : p->pnp_cfg);
+}
+
+// dfvo_pipeline_set_refine: what dfvo_pipeline_get_refine reports for a pair that ran no refinement
+static void refine_record_reset(RefineHost* h) {
+    *h = RefineHost();
+    h->ctl.done = 1;
+    h->ctl.status = ITER_NOT_RUN;
+    for (int i = 0; i < 3; i++) h->rec.R1[i * 4] = h->rec.pnp_R1[i * 4] = 1.0;
+}
+
+// The hand-over behind a first pass, on the chain's stream and gated there: the rigid-flow pose from the pass's device result
+// (E: inv([R | t * scale]), skipped without a translation; PnP: [Rodrigues(r) | t]), kp_selection_good_depth on the reference
+// frame's raw depth, the best set kp_depth into the second buffer set, its count and the gate into pinned memory
+static int enqueue_refine_select(dfvo_pipeline* p, Slot& sl, bool pnp) {
+    hipStream_t s = p->s_trk();
+    TrackerBuffers& t2 = sl.tb2;
+    RigidKpConfig rc = p->refine_cfg;
+    rc.score_rigid = pnp ? p->refine.pnp_score_rigid : p->refine.e_score_rigid;
+    if (pnp)
+        DFVO_TRY(enqueue_refine_pnp_mats(sl.rigid, p->pnp.result, rc, t2.kp_info, s));
+    else
+        DFVO_TRY(enqueue_refine_e_mats(sl.rigid, sl.tb.pose, sl.tb.scale_out, rc, t2.kp_info, s));
+    DFVO_TRY(enqueue_rigid_flow_kp_dev(sl.rigid, sl.flow_in, sl.diff_in, p->ref_raw, p->H, p->W, rc, &sl.rigid.ctl.p->done, t2.kp_ref,
+                                       t2.kp_cur, t2.kp_info, s));
+    DFVO_HIP_CHECK(hipMemcpyAsync(sl.h_refine.p->info2, t2.kp_info, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+    DFVO_HIP_CHECK(hipMemcpyAsync(&sl.h_refine.p->ctl, sl.rigid.ctl, sizeof(IterCtl), hipMemcpyDeviceToHost, s));
+    return DFVO_OK;
+}
+
+// where the reference's "sampling threshold is too small." assertion fires: the pair is over, as the iterative loop ends it
+static int refine_empty_selection(dfvo_pipeline* p, int slot, const double* d_depth_override, RefineHost* h) {
+    h->rec.empty = 1;
+    DFVO_TRY(roll_ref_depth(p, slot, d_depth_override));
+    dfvo::set_last_error("dfvo_pipeline_track_end: sampling threshold is too small (no rigid-flow keypoint selected)");
+    return DFVO_ERR_EMPTY_SELECTION;
+}
+
+// the PnP branch of dfvo.py:225-250 with pnp_tracker.iterative_kp: `pr1` is pass one's result and the selection behind it has
+// arrived in pinned memory; the second pass on kp_depth with the configured repeats, waited for here
+static int refine_pnp_second(dfvo_pipeline* p, int slot, const PnpResult& pr1, const double* d_depth_override, dfvo_track_out* out) {
+    hipStream_t s = p->s_trk();
+    Slot& sl = p->slots[slot];
+    RefineHost* h = sl.h_refine.p;
+    h->rec.pnp_ran = 1;
+    h->rec.pnp_found1 = pr1.found;
+    if (pr1.found) {
+        for (int i = 0; i < 9; i++) h->rec.pnp_R1[i] = pr1.R[i];
+        for (int i = 0; i < 3; i++) h->rec.pnp_t1[i] = pr1.tvec[i];
+    }
+    const int n3 = h->rec.n_kp = h->info2[0];
+    fill_pnp_out(pr1, out);
+    if (n3 == 0) return refine_empty_selection(p, slot, d_depth_override, h);
+    DFVO_TRY(enqueue_pnp(p, sl.tb2, n3, p->pnp_cfg));
+    PnpResult pr;
+    DFVO_HIP_CHECK(hipMemcpyAsync(&pr, p->pnp.result, sizeof(pr), hipMemcpyDeviceToHost, s));
+    DFVO_HIP_CHECK(hipStreamSynchronize(s));
+    DFVO_ARG_CHECK(pr.status >= 0, "dfvo_pipeline_track: the PnP tracker's second pass reported an internal error");
+    fill_pnp_out(pr, out);
+    return DFVO_OK;
 }
 
 // RNG-independent half of the solver stage of `slot` (keypoint selection, homography RANSAC + refinement, GRIC-H):
@@ -139,6 +201,7 @@ int dfvo_pipeline_track_begin(dfvo_pipeline* p, int slot, const float* d_flow_ov
     // side stream: the scale stage's fills leave the dependent chain (the iterative loop clears the map itself, every round)
     if (!pnp_only && !iterative) DFVO_TRY(enqueue_scale_prepare(tb, p->H, p->W));
     if (iterative) iter_record_reset(sl.h_iter);  // (the slot is idle: its last record was copied long ago)
+    if (refine_on(p->refine)) refine_record_reset(sl.h_refine);
     // A pre-part nobody prefetched: in the lane layout it goes onto the chain's lane (s), whose next work needs it anyway --
     // the depth lane may already hold later pairs' nets, and it would run behind them
     if (!sl.prefetched)
@@ -153,13 +216,14 @@ int dfvo_pipeline_track_begin(dfvo_pipeline* p, int slot, const float* d_flow_ov
         // dfvo.py:225-250 on every pair: E_pose stays SE3(), so the only RandomState draws of the pair are PnP's shuffles.
         // The keypoint stage is complete (the host waited for e_pre above)
         if (!p->has_ref_depth) return begun(NO_REF_DEPTH);
-        DFVO_TRY(enqueue_pnp(p, sl, n));
+        DFVO_TRY(enqueue_pnp_first(p, sl, n));
         DFVO_HIP_CHECK(hipMemcpyAsync(&sl.h_res.p->pnp, p->pnp.result, sizeof(PnpResult), hipMemcpyDeviceToHost, s));
+        if (p->refine.pnp_enable) DFVO_TRY(enqueue_refine_select(p, sl, true));
         DFVO_HIP_CHECK(hipEventRecord(sl.e_res, s));
         return begun(CHAIN_ENQUEUED);
     }
     // waits for tb.ev_h (the prefetched half) on the device
-    DFVO_TRY(enqueue_pose_e_part(tb, n, p->pose_cfg, s, p->d_T21, iterative ? p->d_E_pose.p : nullptr));
+    DFVO_TRY(enqueue_pose_e_part(tb, n, p->refine.e_enable ? p->pose_cfg1 : p->pose_cfg, s, p->d_T21, iterative ? p->d_E_pose.p : nullptr));
     DFVO_HIP_CHECK(hipStreamWaitEvent(s, sl.e_depth, 0));
     const double* depth = d_depth_override ? d_depth_override : sl.proc_depth.p;
     if (iterative) {
@@ -173,6 +237,8 @@ int dfvo_pipeline_track_begin(dfvo_pipeline* p, int slot, const float* d_flow_ov
         DFVO_HIP_CHECK(hipMemcpyAsync(sl.h_iter.p, sl.rigid.ctl, sizeof(IterCtl), hipMemcpyDeviceToHost, s));
     } else {
         DFVO_TRY(enqueue_find_scale(tb, n, p->d_T21, depth, p->H, p->W, p->scale_cfg, s, tb.pose, true));
+        // e_tracker.iterative_kp: the kp_depth selection behind pass one, so that its count arrives with pass one's results
+        if (p->refine.e_enable) DFVO_TRY(enqueue_refine_select(p, sl, false));
     }
     if (tb.ev_t[3]) DFVO_HIP_CHECK(hipEventRecord(tb.ev_t[3], s));
     DFVO_HIP_CHECK(hipMemcpyAsync(&sl.h_res.p->pose, tb.pose, sizeof(PoseState), hipMemcpyDeviceToHost, s));
@@ -226,6 +292,10 @@ int dfvo_pipeline_track_end(dfvo_pipeline* p, int slot, dfvo_track_out* out) {
             const PnpResult pr = sl.h_res.p->pnp;
             DFVO_ARG_CHECK(pr.status >= 0, "dfvo_pipeline_track: the PnP tracker reported an internal error");
             fill_pnp_out(pr, out);
+            if (p->refine.pnp_enable) {
+                const int rc_ref = refine_pnp_second(p, slot, pr, d_depth_override, out);
+                if (rc_ref != DFVO_OK) return rc_ref;  // (an empty selection: the depths are rolled)
+            }
         }
         return roll_ref_depth(p, slot, d_depth_override);
     }
@@ -238,8 +308,49 @@ int dfvo_pipeline_track_end(dfvo_pipeline* p, int slot, dfvo_track_out* out) {
     out->best_inlier_cnt = ps.best_cnt;
     out->num_valid = ps.num_valid;
     out->cheirality = ps.cheirality;
-    const bool t_zero = ps.t[0] == 0 && ps.t[1] == 0 && ps.t[2] == 0;
+    bool t_zero = ps.t[0] == 0 && ps.t[1] == 0 && ps.t[2] == 0;
     double scale = sr.scale;
+    ScaleResult sr_last = sr;  // the counts of the last scale stage that ran
+    if (p->refine.e_enable) {
+        // dfvo.py:194-222.  Pass one and the selection behind it are in pinned memory; the second pass needs the kp_depth count
+        // on the host (launch geometry, the "more than 10 keypoints" rule), so it is enqueued here, ahead of the PnP decision
+        RefineHost* h = sl.h_refine.p;
+        for (int i = 0; i < 9; i++) h->rec.R1[i] = ps.R[i];
+        for (int i = 0; i < 3; i++) h->rec.t1[i] = ps.t[i];
+        h->rec.scale1 = t_zero ? 0.0 : sr.scale;
+        if (!t_zero) {
+            TrackerBuffers& t2 = sl.tb2;
+            const int n2 = h->info2[0];
+            h->rec.e_ran = 1;
+            h->rec.n_kp = h->rec.n_inliers = n2;
+            if (n2 == 0) {
+                h->rec.n_inliers = 0;
+                out->scale = scale;
+                out->status = DFVO_TRACK_E;
+                return refine_empty_selection(p, slot, d_depth_override, h);
+            }
+            DFVO_TRY(enqueue_compute_pose_2d2d(t2, n2, p->pose_cfg, s, p->d_T21));
+            if (p->refine.scale_enable)  // gated on the device by the second pass's translation
+                DFVO_TRY(enqueue_find_scale(t2, n2, p->d_T21, d_depth_override ? d_depth_override : sl.proc_depth.p, p->H, p->W,
+                                            p->scale_cfg, s, t2.pose, false));
+            DFVO_TRY(enqueue_refine_final(sl.tb.pose, sl.tb.scale_out, t2.pose, t2.scale_out, p->refine.scale_enable, sl.refine_final, s));
+            DFVO_HIP_CHECK(hipMemcpyAsync(&h->pose2, t2.pose, sizeof(PoseState), hipMemcpyDeviceToHost, s));
+            DFVO_HIP_CHECK(hipMemcpyAsync(&h->scale2, t2.scale_out, sizeof(ScaleResult), hipMemcpyDeviceToHost, s));
+            DFVO_HIP_CHECK(hipMemcpyAsync(&h->fin, sl.refine_final, sizeof(RefineFinal), hipMemcpyDeviceToHost, s));
+            DFVO_HIP_CHECK(hipStreamSynchronize(s));
+            const RefineFinal& fin = h->fin;
+            for (int i = 0; i < 9; i++) out->R[i] = fin.R[i];
+            for (int i = 0; i < 3; i++) out->t[i] = fin.t[i];
+            out->best_inlier_cnt = h->pose2.best_cnt;
+            out->num_valid = h->pose2.num_valid;
+            out->cheirality = h->pose2.cheirality;
+            t_zero = fin.t2_zero != 0;
+            scale = fin.scale;
+            h->rec.scale_ran = fin.scale_ran;
+            h->rec.scale2 = fin.scale2;
+            if (fin.scale_ran) sr_last = h->scale2;
+        }
+    }
     if (p->iter.enable) {
         const IterCtl ctl = *sl.h_iter.p;
         scale = ctl.scale;  // the last completed round's
@@ -258,18 +369,23 @@ int dfvo_pipeline_track_end(dfvo_pipeline* p, int slot, dfvo_track_out* out) {
         }
     }
     out->scale = t_zero ? 0.0 : scale;  // dfvo.py:198: scale recovery only when ||t|| != 0
-    out->scale_n_valid = sr.n_valid;
-    out->scale_n_trials = sr.n_trials;
-    out->scale_n_inliers = sr.n_inliers;
+    out->scale_n_valid = sr_last.n_valid;
+    out->scale_n_trials = sr_last.n_trials;
+    out->scale_n_inliers = sr_last.n_inliers;
     if (t_zero || scale == -1.0) {  // the PnP fallback
         out->status = DFVO_TRACK_NEEDS_PNP;
         if (p->has_ref_depth) {
-            DFVO_TRY(enqueue_pnp(p, sl, n));
+            DFVO_TRY(enqueue_pnp_first(p, sl, n));
             PnpResult pr;
             DFVO_HIP_CHECK(hipMemcpyAsync(&pr, p->pnp.result, sizeof(pr), hipMemcpyDeviceToHost, s));
+            if (p->refine.pnp_enable) DFVO_TRY(enqueue_refine_select(p, sl, true));
             DFVO_HIP_CHECK(hipStreamSynchronize(s));
             DFVO_ARG_CHECK(pr.status >= 0, "dfvo_pipeline_track: the PnP fallback reported an internal error");
             fill_pnp_out(pr, out);
+            if (p->refine.pnp_enable) {
+                const int rc_ref = refine_pnp_second(p, slot, pr, d_depth_override, out);
+                if (rc_ref != DFVO_OK) return rc_ref;  // (an empty selection: the depths are rolled)
+            }
         }
     } else {
         out->status = DFVO_TRACK_E;
@@ -358,6 +474,23 @@ int dfvo_pipeline_get_iterative(dfvo_pipeline* p, int slot, dfvo_scale_iter_out*
     if (ctl.sel_round >= 0 && h_rigid_flow_diff)
         DFVO_HIP_CHECK(hipMemcpy(h_rigid_flow_diff, sl.rigid.rdiff_of(ctl.sel_round, p->H, p->W), sizeof(float) * (size_t)p->H * p->W,
                                  hipMemcpyDeviceToHost));
+    return DFVO_OK;
+}
+
+int dfvo_pipeline_get_refine(dfvo_pipeline* p, int slot, dfvo_refine_out* out, int cap, double* h_kp_ref, double* h_kp_cur,
+                             uint8_t* h_inliers, float* h_rigid_flow_diff) {
+    DFVO_ARG_CHECK(p && out && slot_ok(slot) && cap >= 0, "dfvo_pipeline_get_refine: bad argument");
+    DFVO_ARG_CHECK(refine_on(p->refine), "dfvo_pipeline_get_refine: no keypoint refinement is on (dfvo_pipeline_set_refine)");
+    Slot& sl = p->slots[slot];
+    DFVO_ARG_CHECK(sl.begun == IDLE, "dfvo_pipeline_get_refine: the slot's pair is not collected yet (track_end)");
+    DFVO_HIP_CHECK(hipDeviceSynchronize());
+    *out = sl.h_refine.p->rec;
+    const int m = out->n_kp < cap ? out->n_kp : cap, mi = out->n_inliers < cap ? out->n_inliers : cap;
+    if (m > 0 && h_kp_ref) DFVO_HIP_CHECK(hipMemcpy(h_kp_ref, sl.tb2.kp_ref, sizeof(double) * 2 * m, hipMemcpyDeviceToHost));
+    if (m > 0 && h_kp_cur) DFVO_HIP_CHECK(hipMemcpy(h_kp_cur, sl.tb2.kp_cur, sizeof(double) * 2 * m, hipMemcpyDeviceToHost));
+    if (mi > 0 && h_inliers) DFVO_HIP_CHECK(hipMemcpy(h_inliers, sl.tb2.best_inliers, mi, hipMemcpyDeviceToHost));
+    if ((out->e_ran || out->pnp_ran) && h_rigid_flow_diff)
+        DFVO_HIP_CHECK(hipMemcpy(h_rigid_flow_diff, sl.rigid.rdiff, sizeof(float) * (size_t)p->H * p->W, hipMemcpyDeviceToHost));
     return DFVO_OK;
 }
 

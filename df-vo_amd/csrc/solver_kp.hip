@@ -588,6 +588,31 @@ int enqueue_rigid_flow_kp(RigidKpBuffers& rb, const float* d_flow, const float* 
     return DFVO_OK;
 }
 
+// the same behind a device-side hand-over (solver_refine.hip): rb.mats and the skip flag were written on the device, the best
+// set goes straight to the second pass's keypoint buffers
+int enqueue_rigid_flow_kp_dev(RigidKpBuffers& rb, const float* d_flow, const float* d_odiff, const float* d_depth32, int H, int W,
+                              const RigidKpConfig& cfg, const int* d_skip, double* d_kp1, double* d_kp2, int* d_info, hipStream_t s) {
+    DFVO_ARG_CHECK(d_flow && d_odiff && d_depth32 && d_kp1 && d_kp2 && d_info, "rigid_flow_kp (device matrices): null argument");
+    int cells, n_best, cap, par;
+    size_t lds;
+    if (int rc_g = rigid_flow_kp_geometry(H, W, cfg, &cells, &n_best, &cap, &lds, &par)) return rc_g;
+    DFVO_ARG_CHECK((size_t)H * W <= rb.depth32.n && cells * n_best <= rb.sel_cap && (size_t)cells * cap <= rb.lidx.n,
+                   "rigid_flow_kp (device matrices): buffers not ensured for this size");
+    if (int rc_lds = ensure_dyn_lds((const void*)k_kp_cell_rigid, lds)) return rc_lds;
+    hipLaunchKernelGGL(k_rigid_flow_diff, dim3(cdiv(H * W, 256)), dim3(256), 0, s, d_depth32, d_flow, H, W, rb.mats, rb.rdiff.p,
+                       (float*)nullptr, d_skip);
+    hipLaunchKernelGGL(k_kp_cell_rigid, dim3(cells), dim3(256), lds, s, d_odiff, (const float*)rb.rdiff.p, H, W, cfg.num_row,
+                       cfg.num_col, cfg.opt_thre, cfg.rigid_thre, cfg.score_rigid, n_best, cap, rb.cell_count, rb.cell_sel,
+                       rb.cell_sel_uni, rb.lidx, par, 0, d_skip);
+    const size_t sc = (size_t)rb.sel_cap * 2;
+    hipLaunchKernelGGL(k_kp_gather, dim3(1), dim3(256), 0, s, rb.cell_count, rb.cell_sel, cells, n_best, d_flow, H, W, rb.zero,
+                       (const int*)nullptr, 0, 0, d_kp1, d_kp2, d_info, d_skip);
+    hipLaunchKernelGGL(k_kp_gather, dim3(1), dim3(256), 0, s, rb.cell_count, rb.cell_sel_uni, cells, n_best, d_flow, H, W,
+                       rb.zero, (const int*)nullptr, 0, 0, rb.kp + 2 * sc, rb.kp + 3 * sc, rb.info + 4, d_skip);
+    DFVO_HIP_CHECK(hipGetLastError());
+    return DFVO_OK;
+}
+
 // sampled_kp (kp_selection.py:327-378): the k-th pixel (row-major) of the cropped grid [y0:y1, x0:x1] for every k of
 // the uniform index list; kp1 = (x, y), kp2 = kp1 + flow (float32 promoted to float64, as numpy does)
 __global__ void k_kp_sampled(const float* __restrict__ flow, int H, int W, int y0, int x0, int cw,

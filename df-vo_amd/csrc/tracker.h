@@ -299,6 +299,33 @@ int enqueue_scale_recovery_iterative(TrackerBuffers& tb, RigidKpBuffers& rb, con
                                      const RigidKpConfig& cfg, const ScaleConfig& scfg, const double* d_E_pose,
                                      const double* d_T21, double prev_scale, int kp_src, int n_kp_best, hipStream_t s,
                                      const IterDevice* dev = nullptr);
+// The trackers' iterative keypoint refinement (dfvo.py:194-222, 236-244; solver_refine.hip): the device-side hand-over between a
+// first pass and the second pass on kp_depth.  Each builds Kinv | T | K in rb.mats from the first pass's device results and
+// sets the skip flag of the selection behind it, rb.ctl->done (status ITER_NOT_RUN when set); a skipped hand-over writes
+// d_kp_info2 = [0, 0, 0], the second pass's keypoint triple.
+//   e_mats:   T = inv([R | t * scale]) (scale -1: inv([R | 0])) of the E-tracker's pose; skipped when ||t|| == 0
+//   pnp_mats: T = [Rodrigues(r) | t] of the PnP tracker's result, the identity when no repeat found a model; never skipped
+int enqueue_refine_e_mats(RigidKpBuffers& rb, const PoseState* d_pose, const ScaleResult* d_scale, const RigidKpConfig& cfg,
+                          int* d_kp_info2, hipStream_t s);
+int enqueue_refine_pnp_mats(RigidKpBuffers& rb, const PnpResult* d_pnp, const RigidKpConfig& cfg, int* d_kp_info2, hipStream_t s);
+// enqueue_rigid_flow_kp with the matrices already in rb.mats and a device skip flag (null: none): the distance map goes to
+// rb.rdiff, the best set and its kp_info triple [n, 1, regions] to d_kp1 / d_kp2 / d_info (the second pass's buffers, at least
+// cells * n_best keypoints), the uniform set to rb.kp as before.  rb is ensured by the caller: nothing allocates here.
+int enqueue_rigid_flow_kp_dev(RigidKpBuffers& rb, const float* d_flow, const float* d_odiff, const float* d_depth32, int H, int W,
+                              const RigidKpConfig& cfg, const int* d_skip, double* d_kp1, double* d_kp2, int* d_info, hipStream_t s);
+// the bookkeeping of dfvo.py:206-221 behind the second E pass (and, scale_ran, the second scale stage), one lane
+struct RefineFinal {
+    double R[9], t[3];  // the second pass's
+    double scale;       // the last scale assigned (pass one's, or the second stage's when it ran)
+    double scale2;      // the second stage's result (0: it did not run)
+    int t2_zero;        // the second pass was rejected
+    int scale_ran;
+    int needs_pnp;      // dfvo.py:227
+    int pad;
+};
+int enqueue_refine_final(const PoseState* d_pose1, const ScaleResult* d_scale1, const PoseState* d_pose2, const ScaleResult* d_scale2,
+                         int scale_enable, RefineFinal* d_out, hipStream_t s);
+
 int enqueue_ransac_regressor(TrackerBuffers& tb, int n, bool y_is_ones, const ScaleConfig& cfg, hipStream_t s);
 int set_sklearn_compat(const char* version);  // "0.20" (the reference's pin, default) | "0.22" and later
 

@@ -18,6 +18,7 @@ def default_configuration(height, width, flow_weight_path, depth_model_dir):
     """default_configuration.yml: hybrid tracking, local_bestN 2000 keypoints in 10 x 10 cells, GRIC validity, simple
     depth-ratio scale recovery, PnP fallback (5 x 100 iterations), monodepth2 + LiteFlowNet with forward-backward flow"""
     it = Cfg(enable=False, kp_src="kp_depth", score_method="opt_flow")
+    it_rigid = Cfg(it, score_method="rigid_flow")  # (scale_recovery and pnp_tracker: default_configuration.yml:157,168)
     return Cfg(
         dataset="kitti_odom", seed=4869, tracking_method="hybrid",
         image=Cfg(height=height, width=width),
@@ -34,6 +35,6 @@ def default_configuration(height, width, flow_weight_path, depth_model_dir):
                          depth_consistency=Cfg(enable=False, thre=0.05)),
         e_tracker=Cfg(ransac=Cfg(reproj_thre=0.2, repeat=5), validity=Cfg(method="GRIC", thre=None), kp_src="kp_best",
                       iterative_kp=Cfg(it)),
-        scale_recovery=Cfg(method="simple", kp_src="kp_best", iterative_kp=Cfg(it),
+        scale_recovery=Cfg(method="simple", kp_src="kp_best", iterative_kp=Cfg(it_rigid),
                            ransac=Cfg(method="depth_ratio", min_samples=3, max_trials=100, stop_prob=0.99, thre=0.1)),
-        pnp_tracker=Cfg(ransac=Cfg(iter=100, reproj_thre=1.0, repeat=5), kp_src="kp_best", iterative_kp=Cfg(it)))
+        pnp_tracker=Cfg(ransac=Cfg(iter=100, reproj_thre=1.0, repeat=5), kp_src="kp_best", iterative_kp=Cfg(it_rigid)))

@@ -38,6 +38,13 @@ _SCALE_RECOVERY = {"simple": 0, "iterative": 1}
 _ITER_KP_SRC = {"kp_depth": 0, "kp_best": 1}
 ITER_STATUS = {0: "finished", 1: "empty_selection", 2: "no_consensus", 3: "not_run"}
 
+# dfvo_pipeline_set_refine: the iterative_kp blocks of e_tracker / scale_recovery / pnp_tracker under scale_recovery.method simple
+# (a second tracker pass on the rigid-flow keypoints kp_depth, dfvo.py:194-222, 236-244).  The grid and the thresholds are
+# ITER_DEFAULTS' rigid_* / *_flow_thre keys (kp_selection.rigid_flow_kp), shared with the iterative scale loop
+REFINE_DEFAULTS = dict(e_iterative_kp=False, scale_iterative_kp=False, pnp_iterative_kp=False, e_iterative_score="opt_flow",
+                       pnp_iterative_score="rigid_flow")
+_REFINE_SCORE = {"opt_flow": 0, "rigid_flow": 1}
+
 # dfvo_pipeline_set_depth_source: depth.depth_src.  "external" (depth_src: gt) tracks on a 16-bit depth image per frame in the
 # place of the depth net; depth_scale is the loader's scale_factor of read_depth (500 kitti.py, 5000 tum.py / kinect.py: not in
 # the reference's YAML), depth_size the (height, width) of those images, None = the image size
@@ -58,9 +65,9 @@ def _ptr(t):
 
 
 def _split_options(overrides):
-    """an override dict as the four blocks (DEFAULTS + OPTION_DEFAULTS, ITER_DEFAULTS, DEPTH_DEFAULTS, POSE_DEFAULTS), each with
-    its defaults filled in; a key of none of the last three goes to the first"""
-    blocks = [dict(DEFAULTS, **OPTION_DEFAULTS), dict(ITER_DEFAULTS), dict(DEPTH_DEFAULTS), dict(POSE_DEFAULTS)]
+    """an override dict as the five blocks (DEFAULTS + OPTION_DEFAULTS, ITER_DEFAULTS, DEPTH_DEFAULTS, POSE_DEFAULTS,
+    REFINE_DEFAULTS), each with its defaults filled in; a key of none of the last four goes to the first"""
+    blocks = [dict(DEFAULTS, **OPTION_DEFAULTS), dict(ITER_DEFAULTS), dict(DEPTH_DEFAULTS), dict(POSE_DEFAULTS), dict(REFINE_DEFAULTS)]
     for k, v in overrides.items():
         next((b for b in blocks[1:] if k in b), blocks[0])[k] = v
     return blocks
@@ -121,6 +128,32 @@ def check_iter_options(o):
     return f
 
 
+def check_refine_options(o, io=None, tracking_method="hybrid"):
+    """the refinement keys of `o` (REFINE_DEFAULTS filled in) beside the iterative block `io` (ITER_DEFAULTS filled in: the grid,
+    the thresholds, the scale method) as the fields of capi.PipelineRefineOpts, None when no refinement is on; ValueError on a
+    bad value"""
+    io = dict(ITER_DEFAULTS) if io is None else io
+    for key in ("e_iterative_kp", "scale_iterative_kp", "pnp_iterative_kp"):
+        if not isinstance(o[key], (bool, np.bool_)):
+            raise ValueError("%s = %r: True or False" % (key, o[key]))
+    f = dict(e_enable=int(o["e_iterative_kp"]), scale_enable=int(o["scale_iterative_kp"]), pnp_enable=int(o["pnp_iterative_kp"]),
+             e_score_rigid=_choice(o, "e_iterative_score", _REFINE_SCORE), pnp_score_rigid=_choice(o, "pnp_iterative_score", _REFINE_SCORE))
+    if not (f["e_enable"] or f["scale_enable"] or f["pnp_enable"]):
+        return None
+    if f["scale_enable"] and not f["e_enable"]:
+        raise ValueError("scale_iterative_kp = True without e_iterative_kp: the second scale stage runs behind the second E pass")
+    if io["scale_recovery"] != "simple":
+        raise ValueError("the keypoint refinement (e_ / scale_ / pnp_iterative_kp) runs under scale_recovery 'simple', not %r"
+                         % (io["scale_recovery"],))
+    if tracking_method == "deep_pose":
+        raise ValueError("the keypoint refinement under tracking_method 'deep_pose': no tracker runs")
+    if tracking_method == "PnP" and f["e_enable"]:
+        raise ValueError("e_iterative_kp = True under tracking_method 'PnP': no E-tracker runs")
+    g = check_iter_options(dict(io, scale_recovery="simple"))
+    f.update({k: g[k] for k in ("num_row", "num_col", "num_bestN", "rigid_flow_thre", "optical_flow_thre")})
+    return f
+
+
 def check_depth_options(o, img_h=None, img_w=None):
     """the depth-source keys of `o` (DEPTH_DEFAULTS filled in) as the fields of capi.PipelineDepthSrc; ValueError on a bad value"""
     f = dict(source=_choice(o, "depth_source", _DEPTH_SOURCE), scale=0.0, src_h=0, src_w=0)
@@ -173,10 +206,24 @@ def options_from_cfg(cfg):
     if method not in _SCALE_RECOVERY:
         raise NotImplementedError("scale_recovery.method: %s: not run by the fused pipeline" % method)
     iterative = method == "iterative"
-    for path in ("e_tracker.iterative_kp.enable", "scale_recovery.iterative_kp.enable", "pnp_tracker.iterative_kp.enable",
-                 "kp_selection.rigid_flow_kp.enable", "online_finetune.enable"):
-        if get(path, False) and not (iterative and path == "kp_selection.rigid_flow_kp.enable"):
-            raise NotImplementedError("%s: not run by the fused pipeline" % path)
+    if get("online_finetune.enable", False):
+        raise NotImplementedError("online_finetune.enable: not run by the fused pipeline")
+    # the trackers' iterative keypoint refinement (dfvo.py:194-222, 236-244): under the simple scale method, on kp_depth
+    refine = {k: bool(get(k + ".iterative_kp.enable", False)) for k in ("e_tracker", "scale_recovery", "pnp_tracker")}
+    rigid_kp = bool(get("kp_selection.rigid_flow_kp.enable", False))
+    for k, on in refine.items():
+        if on and iterative:
+            raise NotImplementedError("%s.iterative_kp.enable: under scale_recovery.method: iterative: not run by the fused pipeline" % k)
+        if on and not rigid_kp:  # (kp_selection_good_depth returns nothing then: the reference dies on the missing key)
+            raise NotImplementedError("%s.iterative_kp.enable: without kp_selection.rigid_flow_kp.enable nothing selects kp_depth" % k)
+        if on and get(k + ".iterative_kp.kp_src", "kp_depth") != "kp_depth":
+            raise NotImplementedError("%s.iterative_kp.kp_src: %s: the second pass runs on kp_depth"
+                                      % (k, get(k + ".iterative_kp.kp_src")))
+    if rigid_kp and not iterative and not any(refine.values()):
+        raise NotImplementedError("kp_selection.rigid_flow_kp.enable: nothing reads the rigid-flow keypoints (no iterative_kp block "
+                                  "is enabled, scale_recovery.method is simple)")
+    if refine["scale_recovery"] and not refine["e_tracker"]:
+        raise NotImplementedError("scale_recovery.iterative_kp.enable: without e_tracker.iterative_kp.enable nothing reads it")
     # the pose net runs for a consumer: tracking_method deep_pose (dfvo.py:252-255) or the depth mask of hybrid / PnP tracking
     tracking = get("tracking_method", "hybrid")
     deep, mask = bool(get("deep_pose.enable", False)), bool(get("kp_selection.depth_consistency.enable", False))
@@ -186,6 +233,14 @@ def options_from_cfg(cfg):
         raise NotImplementedError("tracking_method: deep_pose without deep_pose.enable: there is no pose net to track with")
     if tracking == "deep_pose":
         mask = False  # (dfvo.py:139-143: the map is computed in the hybrid / PnP branch only)
+        for k, on in refine.items():
+            if on:
+                raise NotImplementedError("%s.iterative_kp.enable: under tracking_method: deep_pose no tracker runs" % k)
+    if tracking == "PnP":  # (dfvo.py:165: the E-tracker's blocks are not read)
+        refine["e_tracker"] = refine["scale_recovery"] = False
+        if rigid_kp and not iterative and not refine["pnp_tracker"]:
+            raise NotImplementedError("kp_selection.rigid_flow_kp.enable: nothing reads the rigid-flow keypoints under "
+                                      "tracking_method: PnP without pnp_tracker.iterative_kp.enable")
     if deep and not mask and tracking != "deep_pose":
         raise NotImplementedError("deep_pose.enable: nothing reads the pose (tracking_method is not deep_pose, "
                                   "kp_selection.depth_consistency is off): the fused pipeline does not run the net")
@@ -250,11 +305,20 @@ def options_from_cfg(cfg):
         fc = get("crop.flow_crop")
         if fc is not None:
             full["flow_crop"] = tuple(tuple(float(v) for v in r) for r in fc)
-    if iterative:
+    if iterative or any(refine.values()):
         rk = "kp_selection.rigid_flow_kp."
-        full.update(scale_recovery="iterative", iter_kp_src=iter_kp_src, rigid_num_bestN=get(rk + "num_bestN", 2000),
+        full.update(rigid_num_bestN=get(rk + "num_bestN", 2000),
                     rigid_num_row=get(rk + "num_row", 10), rigid_num_col=get(rk + "num_col", 10),
                     rigid_flow_thre=get(rk + "rigid_flow_thre", 5), optical_flow_thre=get(rk + "optical_flow_thre", 0.1))
+    if iterative:
+        full.update(scale_recovery="iterative", iter_kp_src=iter_kp_src)
+    if any(refine.values()):
+        full.update(e_iterative_kp=refine["e_tracker"], scale_iterative_kp=refine["scale_recovery"],
+                    pnp_iterative_kp=refine["pnp_tracker"])
+        if refine["e_tracker"]:
+            full["e_iterative_score"] = get("e_tracker.iterative_kp.score_method", "opt_flow")
+        if refine["pnp_tracker"]:
+            full["pnp_iterative_score"] = get("pnp_tracker.iterative_kp.score_method", "rigid_flow")
     depth_src = get("depth.depth_src")
     if depth_src == "gt":  # dfvo.py:296-319: read_depth's image in the place of the depth net (depth_scale: the loader's, an override)
         full["depth_source"] = "external"
@@ -265,18 +329,20 @@ def options_from_cfg(cfg):
         full.update(pose_net=True, depth_consistency=True, depth_consistency_thre=get("kp_selection.depth_consistency.thre", 0.05))
     base = {k: v for block in _split_options({}) for k, v in block.items()}
     out = {k: v for k, v in full.items() if base.get(k) != v}
-    o, io, _, po = _split_options(out)
+    o, io, _, po, ro = _split_options(out)
     check_options(o)
     check_iter_options(io)
     check_pose_options(po, source)
+    check_refine_options(ro, io, tracking)
     return out
 
 
 class TrackingPipeline:
     def __init__(self, img_h, img_w, feed_h, feed_w, K, flow_sd, depth_sd, pose_sd=None, **overrides):
-        o, io, do, po = _split_options(overrides)
+        o, io, do, po, ro = _split_options(overrides)
         fields = check_options(o)  # (before anything touches the device: a bad value is a ValueError)
         iter_fields = check_iter_options(io)
+        refine_fields = check_refine_options(ro, io, o["tracking_method"])
         depth_fields = check_depth_options(do, img_h, img_w)
         pose_fields = check_pose_options(po, o["kp_source"])
         self.deep_pose = o["tracking_method"] == "deep_pose"
@@ -296,6 +362,8 @@ class TrackingPipeline:
         self.iter_opts = io
         self.depth_opts = do
         self.pose_opts = po
+        self.refine_opts = ro
+        self.refine = refine_fields is not None
         self.depth_size = (depth_fields["src_h"], depth_fields["src_w"])
         self.iterative = io["scale_recovery"] == "iterative"
         self.H, self.W, self.feed_h, self.feed_w = img_h, img_w, feed_h, feed_w
@@ -333,6 +401,8 @@ class TrackingPipeline:
             self._apply(self.lib.dfvo_pipeline_set_options, popts)
         if self.iterative:  # (behind set_options: the bound on the tracked keypoints depends on the keypoint source)
             self._apply(self.lib.dfvo_pipeline_set_iterative, capi.PipelineIterOpts(**iter_fields))
+        if self.refine:  # (behind set_options: what it refuses depends on the tracking method)
+            self._apply(self.lib.dfvo_pipeline_set_refine, capi.PipelineRefineOpts(**refine_fields))
         # keypoints a pair can have (get_keypoints' default capacity)
         self.kp_max = {"local_bestN": o["kp_num_bestN"], "bestN": o["kp_num_bestN"], "sampled": o["kp_sampled_num"]}[o["kp_source"]]
         nh, nw = self._net_size(img_h, img_w)
@@ -481,6 +551,24 @@ class TrackingPipeline:
         return dict(status=ITER_STATUS[out.status], scale=out.scale, n_iter=out.n_iter, kp_round=out.kp_round,
                     scale_in=list(out.scale_in), scale_out=list(out.scale_out), n_kp_round=list(out.n_kp_round),
                     ref_kp=kr[:out.n_kp], cur_kp=kc[:out.n_kp], rigid_flow_diff=m if out.kp_round >= 0 else None)
+
+    def get_refine(self, slot, want_map=False):
+        """the keypoint refinement's record of the pair last collected from `slot`: dict(e_ran, scale_ran, pnp_ran, empty, R1 [3,3],
+        t1 [3], scale1: E pass one; scale2; pnp_found1, pnp_R1, pnp_t1: PnP pass one; ref_kp / cur_kp [n,2]: kp_depth of the pair's
+        last selection; inliers [m] bool: the second E pass's mask over ITS kp_depth (m = n unless a PnP selection followed);
+        rigid_flow_diff [H,W] f32 with want_map, None when no selection ran)"""
+        cap = max(1, self.iter_opts["rigid_num_bestN"])
+        out = capi.RefineOut()
+        kr, kc, inl = np.zeros((cap, 2)), np.zeros((cap, 2)), np.zeros(cap, np.uint8)
+        m = np.zeros((self.H, self.W), np.float32) if want_map else None
+        capi.check(self.lib.dfvo_pipeline_get_refine(self.h, slot, C.byref(out), cap, capi.as_ptr(kr), capi.as_ptr(kc),
+                                                     capi.as_ptr(inl), capi.as_ptr(m)))
+        assert out.n_kp <= cap and out.n_inliers <= cap
+        return dict(e_ran=bool(out.e_ran), scale_ran=bool(out.scale_ran), pnp_ran=bool(out.pnp_ran), empty=bool(out.empty),
+                    R1=np.array(out.R1[:]).reshape(3, 3), t1=np.array(out.t1[:]), scale1=out.scale1, scale2=out.scale2,
+                    pnp_found1=bool(out.pnp_found1), pnp_R1=np.array(out.pnp_R1[:]).reshape(3, 3), pnp_t1=np.array(out.pnp_t1[:]),
+                    ref_kp=kr[:out.n_kp], cur_kp=kc[:out.n_kp], inliers=inl[:out.n_inliers].astype(bool),
+                    rigid_flow_diff=m if (out.e_ran or out.pnp_ran) else None)
 
     def set_ref_depth_image(self, d_depth_u16):
         """depth of the first reference frame from its 16-bit depth image (depth_source "external"; device uint16

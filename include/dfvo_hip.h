@@ -760,6 +760,72 @@ typedef struct dfvo_pipeline_iter_opts {
     double optical_flow_thre; /* kp_selection.rigid_flow_kp.optical_flow_thre */
 } dfvo_pipeline_iter_opts;
 int dfvo_pipeline_set_iterative(dfvo_pipeline* p, const dfvo_pipeline_iter_opts* opts);
+/* The trackers' iterative keypoint refinement in the fused pipeline (the iterative_kp blocks of e_tracker, scale_recovery and
+ * pnp_tracker, dfvo.py:194-222 and :236-244, under scale_recovery.method simple): a tracker runs once on the pipeline's tracked
+ * keypoints with 3 shuffled RANSACs (compute_pose_2d2d / compute_pose_3d2d with is_iterative False), the rigid-flow keypoints
+ * "kp_depth" are selected where the forward flow agrees with the rigid flow of the reference frame's raw depth under the pose
+ * just found (kp_selection_good_depth, E_tracker.py:645-705: the best set, scored by e_score_rigid / pnp_score_rigid), and the
+ * tracker runs again on them with the configured `repeat`.
+ *   e_enable      second E pass when pass one has a translation; the rigid-flow pose is inv([R | t * scale]), inv([R | 0]) when
+ *                 the scale is -1.  R, t and the inlier mask become the second pass's; a second pass without translation takes
+ *                 the PnP fallback.
+ *   scale_enable  (needs e_enable) find_scale_from_depth again on kp_depth when the second pass has a translation; a scale
+ *                 other than -1 replaces pass one's, -1 takes the PnP fallback.
+ *   pnp_enable    inside the PnP branch (the hybrid fallback and tracking_method PNP): PnP on the tracked keypoints with 3
+ *                 repeats, kp_depth under that pose (the identity when no repeat found a model), PnP on kp_depth.
+ * RandomState draws of a pair, in order: shuffles of E pass one, scale RANSAC one, shuffles of E pass two, scale RANSAC two,
+ * shuffles of PnP one, shuffles of PnP two; a stage that does not run draws nothing.
+ * The hand-over between the passes stays on the device (a one-lane kernel builds the rigid-flow pose from the device results
+ * and reads its gate there); the host reads the kp_depth count from pinned memory, because the second pass's launch geometry
+ * and its "more than 10 keypoints" rule need it.  dfvo_pipeline_track_begin enqueues pass one and the E selection behind it,
+ * dfvo_pipeline_track_end the second passes: a pair refined by the E-tracker has three host waits (keypoint count, pass one
+ * with the kp_depth count, pass two), one more for each PnP pass of the fallback.
+ * State rule of dfvo_pipeline_set_options (call that one first when both are used).  DFVO_ERR_ARG, with a message: all three
+ * enables zero together with a non-zero score; scale_enable without e_enable; dfvo_pipeline_set_iterative's method or
+ * tracking_method DFVO_TRACKING_DEEP_POSE beside it; e_enable under DFVO_TRACKING_PNP (no E-tracker runs); what the rigid-flow
+ * keypoint launcher refuses at img_h x img_w; more than 16384 kp_depth keypoints with scale_enable.  An all-zero block switches
+ * the refinement off.  Allocates every buffer of the second passes; a pipeline on which this is never called enqueues,
+ * allocates and waits for exactly what it did before.
+ * An empty selection (the reference's "sampling threshold is too small." assertion) makes dfvo_pipeline_track_end return
+ * DFVO_ERR_EMPTY_SELECTION after the pair is over, as under dfvo_pipeline_set_iterative: the slot idle, the depths rolled
+ * over, the RandomState what the reference had at the raise, `out` the pose of the pass before the selection.
+ * dfvo_track_out keeps its meaning: the final R, t, scale and the last pass's counts.  dfvo_pipeline_get_keypoints keeps
+ * returning the tracked set with pass one's inlier mask. */
+#define DFVO_REFINE_SCORE_OPT_FLOW 0
+#define DFVO_REFINE_SCORE_RIGID_FLOW 1
+typedef struct dfvo_pipeline_refine_opts {
+    int e_enable;             /* e_tracker.iterative_kp.enable */
+    int scale_enable;         /* scale_recovery.iterative_kp.enable */
+    int pnp_enable;           /* pnp_tracker.iterative_kp.enable */
+    int e_score_rigid;        /* e_tracker.iterative_kp.score_method: DFVO_REFINE_SCORE_* */
+    int pnp_score_rigid;      /* pnp_tracker.iterative_kp.score_method */
+    int num_row, num_col;     /* kp_selection.rigid_flow_kp.num_row / num_col */
+    int num_bestN;            /* kp_selection.rigid_flow_kp.num_bestN */
+    double rigid_flow_thre;   /* kp_selection.rigid_flow_kp.rigid_flow_thre */
+    double optical_flow_thre; /* kp_selection.rigid_flow_kp.optical_flow_thre */
+} dfvo_pipeline_refine_opts;
+int dfvo_pipeline_set_refine(dfvo_pipeline* p, const dfvo_pipeline_refine_opts* opts);
+/* what the refinement did for the pair last collected from `slot` (until the slot's next dfvo_pipeline_track_begin) */
+typedef struct dfvo_refine_out {
+    int e_ran;         /* the kp_depth selection of the E refinement ran (pass one had a translation) */
+    int scale_ran;     /* the second scale stage ran (second pass with a translation, scale_enable) */
+    int pnp_ran;       /* the kp_depth selection of the PnP refinement ran */
+    int empty;         /* 1: that selection was empty (dfvo_pipeline_track_end returned DFVO_ERR_EMPTY_SELECTION) */
+    int n_kp;          /* kp_depth keypoints of the pair's last selection (0: none ran) */
+    int n_inliers;     /* kp_depth keypoints of the E refinement = entries of the second pass's inlier mask (0: it did not run) */
+    int pnp_found1;    /* PnP pass one found a model */
+    int pad;
+    double R1[9], t1[3]; /* E pass one's pose (identity, 0 when the pair ran no E-tracker) */
+    double scale1;       /* pass one's scale (0: no scale stage ran) */
+    double scale2;       /* the second scale stage's result (0: it did not run) */
+    double pnp_R1[9], pnp_t1[3]; /* PnP pass one: Rodrigues(rvec), tvec (identity, 0 without a model) */
+} dfvo_refine_out;
+/* h_kp_ref / h_kp_cur (optional, double [cap,2]): kp_depth of the reference / current frame, the first min(n_kp, cap) rows;
+ * h_inliers (optional, uint8 [cap]): the second E pass's inlier mask, min(n_inliers, cap) entries; h_rigid_flow_diff (optional,
+ * float [H,W]): the distance map of the pair's last selection.  DFVO_ERR_ARG unless dfvo_pipeline_set_refine switched a
+ * refinement on.  Waits for the device. */
+int dfvo_pipeline_get_refine(dfvo_pipeline* p, int slot, dfvo_refine_out* out, int cap, double* h_kp_ref, double* h_kp_cur,
+                             uint8_t* h_inliers, float* h_rigid_flow_diff);
 /* EssTracker.prev_scale as the pipeline carries it (host double in / out; both wait for the chain stream; _set needs no pair
  * pending) */
 int dfvo_pipeline_get_prev_scale(dfvo_pipeline* p, double* h_scale);
