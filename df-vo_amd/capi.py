@@ -103,6 +103,16 @@ class RefineOut(C.Structure):
                 ("scale1", C.c_double), ("scale2", C.c_double), ("pnp_R1", C.c_double * 9), ("pnp_t1", C.c_double * 3)]
 
 
+class JpegInfo(C.Structure):
+    """dfvo_jpeg_info: the header dfvo_jpeg_entropy_decode writes at byte 0 of its buffer"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("h_samp", C.c_int32), ("v_samp", C.c_int32),
+                ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3), ("comp_w", C.c_int32 * 3), ("comp_h", C.c_int32 * 3),
+                ("quant", (C.c_uint16 * 64) * 3), ("reserved", C.c_int32), ("plane_offset", C.c_uint64 * 3), ("bytes", C.c_uint64)]
+
+
+JPEG_HEADER_BYTES = 512  # DFVO_JPEG_HEADER_BYTES
+ERR_JPEG = -7            # DFVO_ERR_JPEG: dfvo_jpeg_probe / _entropy_decode refused the file; the message names the reason
+
 DEPTH_NET, DEPTH_EXTERNAL = 0, 1  # dfvo_pipeline_depth_src.source
 
 
@@ -221,6 +231,10 @@ SIGNATURES = {
     "dfvo_undistort_mosaic_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "dfvo_undistort_rgb_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "dfvo_frame_ring_submit_mosaic": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i]),
+    "dfvo_jpeg_probe": (_i, [_vp, _sz, C.POINTER(JpegInfo)]),
+    "dfvo_jpeg_entropy_decode": (_i, [_vp, _sz, _vp, _sz, C.POINTER(JpegInfo)]),
+    "dfvo_jpeg_decode_u8": (_i, [_vp, C.POINTER(JpegInfo), _vp, _vp]),
+    "dfvo_frame_ring_submit_jpeg": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i]),
     "dfvo_resize_bilinear": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "dfvo_flownet_create": (_i, [_i, _i, _vp, C.POINTER(_vp)]),
     "dfvo_flownet_destroy": (None, [_vp]),

@@ -4,9 +4,12 @@
 // hand-over point of the pipeline's frame contract (complete when enqueue_nets / set_ref_image is called).
 #include "../../include/dfvo_hip.h"
 
+#include <string.h>
+
 #include <vector>
 
 #include "dev_mem.h"
+#include "jpeg.h"
 #include "resize_lanczos.h"
 #include "undistort.h"
 
@@ -21,7 +24,7 @@ struct dfvo_frame_ring {
     };
     std::vector<Slot> slots;
     size_t capacity = 0;  // bytes per slot
-    DevArr<uint8_t> rgb;  // the demosaiced, undistorted plane of a mosaic submit: one for all slots (one stream orders its uses)
+    DevArr<uint8_t> rgb;  // the demosaiced, undistorted plane of a mosaic submit, the decoded plane of a JPEG submit: one for all slots (one stream orders its uses)
     hipStream_t stream = nullptr;
 
     // every member is released here whether or not init completed (the arrays free themselves)
@@ -130,6 +133,35 @@ int dfvo_frame_ring_submit_mosaic(dfvo_frame_ring* r, int slot, const dfvo_undis
     s.pending = true;
     rc = enqueue_undistort_mosaic(map, s.dev.p, img_h, img_w, pattern, border, y0, y1, x0, x1, r->rgb.p, r->stream);
     if (rc == DFVO_OK) rc = dfvo_read_image_tail_u8(r->rgb.p, img_h, img_w, 0, y0, y1, x0, x1, d_dst, out_h, out_w, r->stream);
+    const hipError_t e = hipEventRecord(s.done, r->stream);
+    if (rc != DFVO_OK) return rc;
+    DFVO_HIP_CHECK(e);
+    return DFVO_OK;
+}
+
+int dfvo_frame_ring_submit_jpeg(dfvo_frame_ring* r, int slot, int y0, int y1, int x0, int x1, uint8_t* d_dst, int out_h, int out_w) {
+    RING_SLOT_CHECK("dfvo_frame_ring_submit_jpeg");
+    dfvo_frame_ring::Slot& s = r->slots[slot];
+    DFVO_ARG_CHECK(!s.pending, "dfvo_frame_ring_submit_jpeg: the slot's last submit has not been waited for");
+    DFVO_ARG_CHECK(d_dst && out_h > 0 && out_w > 0, "dfvo_frame_ring_submit_jpeg: no output frame");
+    DFVO_ARG_CHECK(r->capacity >= sizeof(dfvo_jpeg_info), "dfvo_frame_ring_submit_jpeg: the staging capacity holds no header");
+    dfvo_jpeg_info info;  // (a copy: the decoder thread is done with the slot, but the checks and the launches see one header)
+    memcpy(&info, s.staging.p, sizeof(info));
+    DFVO_ARG_CHECK(info.bytes >= DFVO_JPEG_HEADER_BYTES && info.bytes <= r->capacity,
+                   "dfvo_frame_ring_submit_jpeg: the header and coefficients are larger than the staging capacity");
+    DFVO_ARG_CHECK(info.width > 0 && info.height > 0 && 0 <= y0 && y0 < y1 && y1 <= info.height && 0 <= x0 && x0 < x1 && x1 <= info.width,
+                   "dfvo_frame_ring_submit_jpeg: crop outside the frame");
+    const int channels = info.components == 1 ? 1 : 3;
+    // (a plane that has to grow is freed first, and hipFree waits for the kernels that still use it)
+    int rc = r->rgb.grow((size_t)info.height * info.width * channels);
+    if (rc != DFVO_OK) return rc;
+    DFVO_HIP_CHECK(hipMemcpyAsync(s.dev.p, s.staging.p, (size_t)info.bytes, hipMemcpyHostToDevice, r->stream));
+    // from here on the slot is in flight whatever fails: wait() drains it
+    s.pending = true;
+    rc = enqueue_jpeg_decode(s.dev.p, &info, r->rgb.p, r->stream, "dfvo_frame_ring_submit_jpeg");
+    if (rc == DFVO_OK)
+        rc = channels == 1 ? dfvo_read_image_tail_gray_u8(r->rgb.p, info.height, info.width, y0, y1, x0, x1, d_dst, out_h, out_w, r->stream)
+                           : dfvo_read_image_tail_u8(r->rgb.p, info.height, info.width, 0, y0, y1, x0, x1, d_dst, out_h, out_w, r->stream);
     const hipError_t e = hipEventRecord(s.done, r->stream);
     if (rc != DFVO_OK) return rc;
     DFVO_HIP_CHECK(e);

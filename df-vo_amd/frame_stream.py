@@ -22,7 +22,17 @@ Decoding follows what cv2.imread(path) + cvtColor(BGR2RGB) hand read_image (libs
 L through the grey tail (dfvo_read_image_tail_gray_u8: a third of the upload), P / RGBA / LA through convert("RGB") (alpha
 dropped); 16-bit images are refused by name.  PNG is lossless, so the frames are exactly read_image's.  JPEG: Pillow and OpenCV
 both decode with libjpeg, but of versions and IDCT / upsampling settings this project does not pin -- parity of JPEG frames
-with the reference's is NOT established.
+with the reference's (OpenCV's decoder) is NOT established.
+
+jpeg="device" (default "host": everything above, untouched): a worker reads the file's bytes; bytes that start with FF D8 go
+through the host entropy pass (dfvo_jpeg_entropy_decode, without the GIL) straight into the staging slot -- a header and the
+quantised coefficients, up to 6 bytes per pixel -- and the ring dequantises, inverts the DCT, upsamples and converts the colours
+on the device (dfvo_frame_ring_submit_jpeg, csrc/jpeg.hip) ahead of the same read-image tail.  That arithmetic is pinned: it is
+Pillow's (libjpeg-turbo: 13-bit slow-integer IDCT, triangle upsampling, 16-bit colour tables) byte for byte for files a
+conforming encoder wrote, so the frames are those of jpeg="host" (docs/parity.md); it is pinned to that decoder and to nothing
+else.  Baseline sequential 8-bit files of one or three components (4:4:4, 4:2:2, 4:2:0) are decoded; a progressive, CMYK,
+otherwise refused or corrupt JPEG raises FrameStreamError naming the file and the reason.  Any other file goes through Pillow as
+above, and a sequence may mix both.
 
 Raw frames (mosaic="gbrg", undistort=UndistortMap or None, border): a mode-L file is then an 8-bit Bayer mosaic, staged and
 uploaded as it is; the ring demosaics and undistorts the crop's pixels on the device (dfvo_frame_ring_submit_mosaic, undistort.py)
@@ -38,6 +48,7 @@ from . import capi
 
 MAX_WORKERS = 16  # `workers` is a plain argument capped here, never derived from the machine's core count (4 carry the pair rate)
 KINDS = ("image", "depth_u16")
+JPEG_MODES = ("host", "device")
 
 
 class FrameStreamError(RuntimeError):
@@ -78,6 +89,10 @@ class FrameRing:
         capi.check(self.lib.dfvo_frame_ring_submit_mosaic(self.h, slot, None if umap is None else umap.handle, ud.pattern_code(pattern),
                                                           ud.border_code(border), h, w, box[0], box[1], box[2], box[3],
                                                           C.c_void_p(out.data_ptr()), out.shape[0], out.shape[1]))
+
+    def submit_jpeg(self, slot, box, out):
+        capi.check(self.lib.dfvo_frame_ring_submit_jpeg(self.h, slot, box[0], box[1], box[2], box[3], C.c_void_p(out.data_ptr()),
+                                                        out.shape[0], out.shape[1]))
 
     def submit_raw(self, slot, nbytes, out):
         capi.check(self.lib.dfvo_frame_ring_submit_raw(self.h, slot, nbytes, C.c_void_p(out.data_ptr())))
@@ -152,6 +167,28 @@ def decode(path, kind, staging, mosaic=False):
         raise FrameStreamError("%s: %s: %s" % (path, type(e).__name__, e)) from e
 
 
+def jpeg_capacity(h, w):
+    """staging bytes that hold any decodable JPEG of h x w: the header and 2 bytes per sample of three full-size planes padded
+    to whole MCUs"""
+    return capi.JPEG_HEADER_BYTES + 6 * (-(-h // 16) * 16) * (-(-w // 16) * 16)
+
+
+def decode_any(path, staging):
+    """jpeg="device": a file that starts with FF D8 through the host entropy pass into `staging`, (h, w, channels, True); any
+    other file through decode(), (h, w, channels, False).  Raises FrameStreamError naming the path (and the reason)."""
+    from . import jpeg
+    try:
+        with open(path, "rb") as f:
+            head = f.read(2)
+            data = np.frombuffer(head + f.read(), np.uint8) if jpeg.is_jpeg(head) else None
+        if data is not None:
+            info = jpeg.entropy_decode_into(data, staging)
+            return info.height, info.width, (1 if info.components == 1 else 3), True
+    except Exception as e:
+        raise FrameStreamError("%s: %s: %s" % (path, type(e).__name__, e)) from e
+    return decode(path, "image", staging) + (False,)
+
+
 class _Entry:
     __slots__ = ("slot", "state", "meta", "error", "dropped")
 
@@ -160,7 +197,7 @@ class _Entry:
 
 
 class FrameStream:
-    """FrameStream(paths, out_h, out_w, crop=None, slots=12, workers=6, kind="image"): indexable by frame number.
+    """FrameStream(paths, out_h, out_w, crop=None, slots=12, workers=6, kind="image", jpeg="host"): indexable by frame number.
     kind "image": frames[k] is the device uint8 tensor [out_h, out_w, 3] of read_image(paths[k], out_h, out_w, crop)
     (crop: [[y0, y1], [x0, x1]] fractions); kind "depth_u16": the device uint16 tensor [out_h, out_w] of the 16-bit depth image as
     it is in the file (out_h, out_w: the files' own size, TrackingPipeline's depth_size; the division and the resize are the
@@ -172,14 +209,22 @@ class FrameStream:
     undistorted through `undistort` (an undistort.UndistortMap of the files' size, which the caller closes after the stream; None:
     demosaic only), the mosaic extended over the border by `border` ("reflect" or "mirror"; include/dfvo_hip.h).  Without
     `mosaic` an L file is a grey frame and nothing changes.
-    capacity: bytes per staging slot (default: the first readable file's decoded size).  ring: the ring object (tests).
+    jpeg "device" (kind "image", no mosaic): JPEG files are entropy-decoded by the workers and decoded on the device, to the
+    frames jpeg="host" gives (module docstring); a refused or corrupt JPEG raises FrameStreamError with the reason at its frame.
+    capacity: bytes per staging slot (default: the first readable file's decoded size; under jpeg="device" what any decodable
+    JPEG of that size needs, jpeg_capacity).  ring: the ring object (tests).
     close() stops and joins the workers and destroys the ring; call it after pipe.sync() (the pipeline may still read the
     frames it was handed), or use the stream as a context manager around run_sequence, which ends with pipe.sync()."""
 
     def __init__(self, paths, out_h, out_w, crop=None, slots=12, workers=6, kind="image", capacity=None, ring=None,
-                 mosaic=None, undistort=None, border="reflect"):
+                 mosaic=None, undistort=None, border="reflect", jpeg="host"):
         if kind not in KINDS:
             raise ValueError("kind: %r: one of %s" % (kind, ", ".join(KINDS)))
+        if jpeg not in JPEG_MODES:
+            raise ValueError("jpeg: %r: one of %s" % (jpeg, ", ".join(JPEG_MODES)))
+        if jpeg == "device" and (mosaic is not None or kind != "image"):
+            raise ValueError("jpeg=\"device\": for an image stream without mosaic= (a raw Bayer frame or a 16-bit depth image is no JPEG)")
+        self.jpeg = jpeg
         if not (isinstance(workers, int) and 1 <= workers <= MAX_WORKERS):
             raise ValueError("workers: %r: 1 .. %d" % (workers, MAX_WORKERS))
         if not (isinstance(slots, int) and slots >= 1):
@@ -220,6 +265,16 @@ class FrameStream:
             return self.out_h * self.out_w * 2
         for p in self.paths[:8]:
             try:
+                if self.jpeg == "device":  # (dfvo_jpeg_probe for a JPEG; a sequence may mix samplings and PNG files of that size)
+                    from . import jpeg
+                    with open(p, "rb") as f:
+                        data = f.read()
+                    if jpeg.is_jpeg(data):
+                        info = jpeg.probe(data)
+                        h, w = info.height, info.width
+                    else:
+                        h, w, _ = probe(p)
+                    return max(jpeg_capacity(h, w), h * w * 3)
                 h, w, per = probe(p)
                 return h * w * (1 if self.mosaic else max(per, 3))
             except Exception:
@@ -251,7 +306,10 @@ class FrameStream:
                 self.max_live = max(self.max_live, self.slots - len(self._free))
             meta = error = None
             try:
-                meta = decode(self.paths[k], self.kind, self._ring.staging(e.slot), mosaic=self.mosaic is not None)
+                if self.jpeg == "device":
+                    meta = decode_any(self.paths[k], self._ring.staging(e.slot))
+                else:
+                    meta = decode(self.paths[k], self.kind, self._ring.staging(e.slot), mosaic=self.mosaic is not None)
                 if self.kind == "depth_u16" and meta[:2] != (self.out_h, self.out_w):
                     raise FrameStreamError("%s: %d x %d: the stream's depth images are %d x %d" % ((self.paths[k],) + meta[:2] + (self.out_h, self.out_w)))
             except BaseException as ex:
@@ -325,12 +383,14 @@ class FrameStream:
 
     def _submit(self, e):
         out = self._out[e.slot]
-        h, w, ch = e.meta
+        h, w, ch = e.meta[:3]
         if self.kind == "image":
             box = (0, h, 0, w)
             if self.crop is not None:  # utils.py:46-50
                 box = (int(h * self.crop[0][0]), int(h * self.crop[0][1]), int(w * self.crop[1][0]), int(w * self.crop[1][1]))
-            if self.mosaic is not None:
+            if len(e.meta) > 3 and e.meta[3]:
+                self._ring.submit_jpeg(e.slot, box, out)
+            elif self.mosaic is not None:
                 self._ring.submit_mosaic(e.slot, self.undistort, self.mosaic, self.border, h, w, box, out)
             else:
                 self._ring.submit_image(e.slot, h, w, ch, box, out)

@@ -100,12 +100,13 @@ def load_weights(cfg):
 
 def run_kitti_odom(cfg, flow_sd=None, depth_sd=None, pose_sd=None, seq=None, out_dir=None, gt_poses=None, world=1, rank=0,
                    dist=None, comm=None, feed_h=None, feed_w=None, slots=12, workers=6, ahead=3, carry_features=True, rng_mode=None,
-                   compose="host", alignment=None, n_frames=None, **overrides):
+                   compose="host", alignment=None, n_frames=None, jpeg="host", **overrides):
     """DFVO.main over one KITTI odometry sequence (apis/run.py) on the fused pipeline, frames read from disk as it tracks:
       1. TrackingPipeline.from_cfg(cfg, K of <img_seq_dir>/<seq>/calib.txt, weights, **overrides) -- a configuration that
          pipeline.options_from_cfg refuses is refused here with its message;
       2. a FrameStream over image_2/*.<image.ext> (read_image: resize to image.height x image.width) and, under depth.depth_src
-         gt, a second one over the 16-bit depth images (their size is the first file's);
+         gt, a second one over the 16-bit depth images (their size is the first file's); jpeg ("host" or "device") is the
+         image stream's: "device" decodes JPEG frames on the device, to the same frames (frame_stream.py);
       3. sequence.run_sequence (world / rank / dist / comm: its frame-parallel chunking);
       4. out_dir/<seq>.txt through evaluation.save_traj (rank 0);
       5. with gt_poses ([n,4,4] or the path of a KITTI pose file) evaluation.evaluate.
@@ -131,7 +132,7 @@ def run_kitti_odom(cfg, flow_sd=None, depth_sd=None, pose_sd=None, seq=None, out
     pipe = TrackingPipeline.from_cfg(cfg, K, flow_sd, depth_sd, feed_h or 192, feed_w or 640, pose_sd=pose_sd, **overrides)
     frames = depths = None
     try:
-        frames = FrameStream(files["images"][:n], h, w, slots=slots, workers=workers)
+        frames = FrameStream(files["images"][:n], h, w, slots=slots, workers=workers, jpeg=jpeg)
         if external:
             depths = FrameStream(files["depths"][:n], pipe.depth_size[0], pipe.depth_size[1], slots=slots, workers=workers,
                                  kind="depth_u16")

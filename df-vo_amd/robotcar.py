@@ -56,11 +56,12 @@ def robotcar_paths(img_seq_dir, seq, source="raw", ext="png"):
 
 def run_robotcar(cfg, flow_sd=None, depth_sd=None, pose_sd=None, seq=None, source="raw", out_dir=None, gt_poses=None, feed_h=None,
                  feed_w=None, slots=12, workers=6, ahead=3, carry_features=True, compose="host", alignment=None, n_frames=None,
-                 border="reflect", raw_size=(RAW_H, RAW_W), **overrides):
+                 border="reflect", raw_size=(RAW_H, RAW_W), jpeg="host", **overrides):
     """DFVO.main over one RobotCar sequence on the fused pipeline, frames read from disk as it tracks (kitti.run_kitti_odom's
     shape): K of the model file, a FrameStream over the mosaics with the SDK's table (raw_size: the files' size, which the table
     is for) or over the pre-made undistorted files, sequence.run_sequence, out_dir/<seq>.txt, evaluation against gt_poses
-    ([n,4,4] or a KITTI pose file).  Returns {"poses", "gathered", "metrics"}."""
+    ([n,4,4] or a KITTI pose file).  jpeg ("host" or "device"; source "undistorted" only, a mosaic is no JPEG): the stream's, "device"
+    decodes JPEG frames on the device to the same frames (frame_stream.py).  Returns {"poses", "gathered", "metrics"}."""
     from . import evaluation as ev
     from .undistort import UndistortMap
     seq = str(cfg["seq"] if seq is None else seq)
@@ -76,12 +77,14 @@ def run_robotcar(cfg, flow_sd=None, depth_sd=None, pose_sd=None, seq=None, sourc
     pipe = TrackingPipeline.from_cfg(cfg, K, flow_sd, depth_sd, feed_h or 192, feed_w or 640, pose_sd=pose_sd, **overrides)
     frames = umap = None
     try:
+        if source == "raw" and jpeg != "host":
+            raise ValueError("jpeg=%r: for source \"undistorted\" (the raw mosaics are PNG files)" % (jpeg,))
         if source == "raw":
             umap = UndistortMap.from_lut_file(files["lut"], raw_size[0], raw_size[1])
             frames = FrameStream(files["images"][:n], h, w, crop=CROP, slots=slots, workers=workers, mosaic=PATTERN, undistort=umap,
                                  border=border)
         else:
-            frames = FrameStream(files["images"][:n], h, w, crop=CROP, slots=slots, workers=workers)
+            frames = FrameStream(files["images"][:n], h, w, crop=CROP, slots=slots, workers=workers, jpeg=jpeg)
         poses, gathered = sequence.run_sequence(pipe, frames, n, seed=int(cfg.get("seed", 4869)), ahead=ahead, compose=compose,
                                                 carry_features=carry_features)
     finally:

@@ -31,6 +31,7 @@ extern "C" {
 #define DFVO_ERR_RANGE (-4) /* f16x3 / f16 packing: an activation left f16's range in this call (see dfvo_f16s_overflow_count) */
 #define DFVO_ERR_EMPTY_SELECTION (-5) /* dfvo_scale_recovery_iterative: a round selected no rigid-flow keypoint (the reference asserts) */
 #define DFVO_ERR_NO_CONSENSUS (-6)    /* dfvo_scale_recovery_iterative: sklearn's "RANSAC could not find a valid consensus set" */
+#define DFVO_ERR_JPEG (-7)            /* dfvo_jpeg_probe / _entropy_decode: a file that is refused or corrupt; the message says which */
 
 const char* dfvo_last_error(void);
 /* number of visible HIP devices (0 when there is none); never fails */
@@ -252,6 +253,45 @@ int dfvo_frame_ring_submit_mosaic(dfvo_frame_ring* ring, int slot, const dfvo_un
                                   int img_w, int y0, int y1, int x0, int x1, uint8_t* d_dst, int out_h, int out_w);
 int dfvo_resize_bilinear(const float* d_src, int N, int H, int W, int C, float* d_dst, int Ho, int Wo,
                          int align_corners, void* stream);
+/* Baseline JPEG frames: the bit-serial Huffman pass on the host, everything behind it on the device, with the arithmetic of
+ * libjpeg-turbo's default decompression path restated exactly -- the pixels are Pillow's (libjpeg-turbo) byte for byte for every
+ * file a conforming encoder wrote (docs/parity.md; parity with OpenCV's decoder is not established).
+ * Decoded: baseline sequential (SOF0), 8-bit samples, 8-bit quantisation tables, Huffman coding, one interleaved scan of one
+ * component (grey) or three (YCbCr, luma sampling 1x1, 2x1 or 2x2, chroma 1x1), restart intervals.  DFVO_ERR_JPEG with a message
+ * that names the reason: progressive and every other SOFn, 12-bit samples, 16-bit tables, arithmetic coding, four components, any
+ * other sampling, more than one scan, a missing table, a Huffman code that is not in its table, a coefficient index past 63, data
+ * that ends early, a bad restart marker, bytes that are no JPEG, a capacity that is too small (nothing is truncated).  No input
+ * makes either host call read outside h_bytes[0 .. n) or write outside h_dst[0 .. capacity_bytes).
+ * The buffer (dfvo_jpeg_entropy_decode's h_dst, 8-byte aligned; dfvo_jpeg_decode_u8's d_coeffs is its device copy): the
+ * dfvo_jpeg_info at byte 0, and from byte plane_offset[c] the quantised coefficients of component c as int16 in natural
+ * (de-zigzagged) order, 64 per block, the blocks in raster order of the component's padded grid blocks_h[c] x blocks_w[c] (whole
+ * MCUs); info.bytes in all, at most DFVO_JPEG_HEADER_BYTES + 6 bytes per pixel of the padded frame.
+ * dfvo_jpeg_probe: the header only (sizes a ring: info.bytes).  dfvo_jpeg_entropy_decode: the whole host pass; neither touches
+ * the device, both are re-entrant (decoder threads call them).
+ * dfvo_jpeg_decode_u8: dequantisation, the 13-bit "slow integer" IDCT (columns, then rows), triangle-filter upsampling over the
+ * component's own downsampled size with the edge sample replicated, 16-bit fixed-point YCbCr -> RGB; d_dst uint8 [height, width,
+ * 3], or [height, width] for a one-component file.  At most two launches, asynchronous on `stream`.  d_coeffs is the workspace:
+ * its coefficients are overwritten.  `info` (host) is checked against the layout of its own size and sampling (DFVO_ERR_ARG).
+ * Coefficient data no conforming encoder writes decodes deterministically and memory-safely, to pixels that need not be libjpeg's. */
+#define DFVO_JPEG_HEADER_BYTES 512
+typedef struct dfvo_jpeg_info {
+    int32_t width, height, components;  /* components: 1 (grey) or 3 (YCbCr) */
+    int32_t h_samp, v_samp;             /* luma sampling factors; chroma is 1x1 */
+    int32_t blocks_w[3], blocks_h[3];   /* padded block grid per component */
+    int32_t comp_w[3], comp_h[3];       /* the component's own (downsampled) size in samples */
+    uint16_t quant[3][64];              /* the component's quantisation table, natural order */
+    int32_t reserved;
+    uint64_t plane_offset[3];           /* bytes from the start of the buffer to the component's coefficients */
+    uint64_t bytes;                     /* header and coefficients */
+} dfvo_jpeg_info;
+int dfvo_jpeg_probe(const uint8_t* h_bytes, size_t n, dfvo_jpeg_info* info);
+int dfvo_jpeg_entropy_decode(const uint8_t* h_bytes, size_t n, void* h_dst, size_t capacity_bytes, dfvo_jpeg_info* info);
+int dfvo_jpeg_decode_u8(uint8_t* d_coeffs, const dfvo_jpeg_info* info, uint8_t* d_dst, void* stream);
+/* A staged JPEG through the ring: the slot's staging memory holds what dfvo_jpeg_entropy_decode wrote.  The asynchronous copy of
+ * its header and coefficients, dfvo_jpeg_decode_u8 into the ring's shared plane (dfvo_frame_ring_submit_mosaic's, grown the same
+ * way), dfvo_read_image_tail_u8 -- _gray_u8 for a one-component file -- of the box into d_dst uint8 [out_h, out_w, 3], the slot's
+ * event.  Errors as dfvo_frame_ring_submit_image's; a header that is not the layout of its own size is DFVO_ERR_ARG. */
+int dfvo_frame_ring_submit_jpeg(dfvo_frame_ring* ring, int slot, int y0, int y1, int x0, int x1, uint8_t* d_dst, int out_h, int out_w);
 
 /* =====================================================================================
  * LiteFlowNet forward/backward flow + consistency   (replaces LiteFlow.inference_flow,

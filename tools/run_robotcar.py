@@ -28,6 +28,8 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=None, help="track the first N frames only")
     ap.add_argument("--slots", type=int, default=12, help="ring slots")
     ap.add_argument("--workers", type=int, default=6, help="decoder threads (at most 16)")
+    ap.add_argument("--jpeg", default="host", choices=("host", "device"),
+                    help="--source undistorted: device decodes JPEG frames on the device (the same frames)")
     a = ap.parse_args(argv)
     robotcar = importlib.import_module("df-vo_amd.robotcar")
     cfg = robotcar.cfg_from_yaml(a.default_configuration, a.configuration)
@@ -37,7 +39,7 @@ def main(argv=None):
     seq = str(cfg["seq"] if a.seq is None else a.seq)
     t0 = time.perf_counter()
     r = robotcar.run_robotcar(cfg, seq=seq, source=a.source, border=a.border, out_dir=out, gt_poses=a.gt, n_frames=a.frames,
-                              slots=a.slots, workers=a.workers)
+                              slots=a.slots, workers=a.workers, jpeg=a.jpeg)
     dt = time.perf_counter() - t0
     print(json.dumps(dict(tool="run_robotcar", seq=seq, source=a.source, frames=len(r["poses"]), seconds_with_setup=dt,
                           trajectory=None if out is None else os.path.join(out, "%s.txt" % seq), metrics=r["metrics"]), default=float))
