@@ -212,6 +212,9 @@ SIGNATURES = {
     "dfvo_reg_head": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _f, _vp, _f, _i, _i, _i, _vp, _i, _i, _vp]),
     "dfvo_flow_post": (_i, [_vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp]),
     "dfvo_img_u8_to_flow_input": (_i, [_vp, _i, _i, _vp, _i, _i, _vp]),
+    "dfvo_deconv_variant": (_i, [_i, _i]),
+    "dfvo_correlation_variant": (_i, [_i, _i, _i, _i, _i]),
+    "dfvo_reg_head_variant": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _i]),
     "dfvo_deconv_dw4x4s2": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "dfvo_maxpool3x3s2": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "dfvo_lanczos_coeffs": (_i, [_i, _i, _vp, _vp, _i, _ip]),

@@ -247,7 +247,7 @@ int dfvo_reg_prep(const float* d_img, const float* d_flow, int fcs, int fco, flo
 
 int dfvo_reg_head(const float* d_dist, int dist_cs, int k, const float* d_flow, int fcs, int fco, const float* h_wx, float bx,
                   const float* h_wy, float by, int N, int H, int W, float* d_dst, int dcs, int dco, void* stream) {
-    DFVO_ARG_CHECK(d_dist && d_flow && d_dst && N > 0 && H > 0 && W > 0 && (k == 3 || k == 5 || k == 7), "dfvo_reg_head: bad argument");
+    DFVO_ARG_CHECK(d_dist && d_flow && d_dst && N > 0 && H > 0 && W > 0 && k >= 1 && k <= 9 && (k & 1), "dfvo_reg_head: bad argument");
     DFVO_ARG_CHECK(dist_cs >= k * k && fco + 2 <= fcs && dco + 2 <= dcs, "dfvo_reg_head: view too narrow");
     hipStream_t s = (hipStream_t)stream;
     DevArr<float> wx, wy;
@@ -255,6 +255,15 @@ int dfvo_reg_head(const float* d_dist, int dist_cs, int k, const float* d_flow, 
     if (rc == DFVO_OK) rc = upload_table(h_wy, k * k, &wy);
     if (rc == DFVO_OK) rc = launch_reg_head(d_dist, dist_cs, k, d_flow, fcs, fco, wx, bx, wy, by, N, H, W, d_dst, dcs, dco, s);
     return finish(rc, s);
+}
+
+int dfvo_deconv_variant(int C, int cs) { return deconv_dw_variant(cs, 0, cs, 0, C, deconv_blk_enabled()); }
+int dfvo_correlation_variant(int C, int cs1, int co1, int cs2, int co2) {
+    return correlation_variant(C, cs1, co1, cs2, co2, correlation_rt_enabled());
+}
+int dfvo_reg_head_variant(const float* d_dist, int dist_cs, int k, const float* d_flow, int fcs, int fco, const float* d_dst, int dcs,
+                          int dco) {
+    return reg_head_variant(d_dist, dist_cs, k, d_flow, fcs, fco, d_dst, dcs, dco, reg_head_vec_enabled());
 }
 
 int dfvo_flow_post(const float* d_netflow, int fcs, int fco, int h, int w, float scale, int H, int W, float* d_fwd,

@@ -38,6 +38,22 @@ int launch_reg_prep(const float* img, const float* flow, int fcs, int fco, float
 // depthwise ConvTranspose2d k4 s2 p1 no bias (lite_flow_net.py:109,117). w[C][4][4].
 int launch_deconv_dw(const float* src, int scs, int sco, int N, int H, int W, int C, const float* w, float* dst,
                      int dcs, int dco, hipStream_t s);
+// The kernel launch_deconv_dw runs for a pair of views: the 2 x 2 block kernel (16-byte views with room for the last quad,
+// taps within 32 KB of LDS), the quad-per-output kernel (such views, wider C or blk off) or the scalar kernel (any view).
+// Pure: the launcher calls it with its DFVO_DECONV_BLK switch, dfvo_deconv_variant with the same switch.
+enum { DECONV_BLK = 0, DECONV_QUAD = 1, DECONV_SCALAR = 2 };
+int deconv_dw_variant(int scs, int sco, int dcs, int dco, int C, bool blk);
+bool deconv_blk_enabled();  // DFVO_DECONV_BLK, read once
+// The kernel and tile of launch_correlation: 100 K + 10 TH + TW with K = C / 32 for k_correlation_rt<K> and K = 0 for
+// k_correlation, or -1 where the launcher refuses (a channel count or view that is no multiple of 4, a tile beyond 160 KB of
+// LDS).  Pure; rt = the DFVO_CORR_RT switch.
+int correlation_variant(int C, int cs1, int co1, int cs2, int co2, bool rt);
+bool correlation_rt_enabled();  // DFVO_CORR_RT, read once
+// The kernel of launch_reg_head: k for k_reg_head_v<k> (k = 3 / 5 / 7 on 16-byte distance vectors and 8-byte flow and
+// destination views), 0 for k_reg_head.  Pure; vec = the DFVO_REG_HEAD_V switch.
+int reg_head_variant(const float* dist, int dist_cs, int k, const float* flow, int fcs, int fco, const float* dst, int dcs, int dco,
+                     bool vec);
+bool reg_head_vec_enabled();  // DFVO_REG_HEAD_V, read once
 // correlation volume (49 displacements) + leaky-ReLU 0.1; correlation.py:38-106,294 and
 // lite_flow_net.py:145,148.  first = f1[n], second = f2[swap2 ? N-1-n : n]; output [N,Ho,Wo,52] (49 used).
 int launch_correlation(const float* f1, int cs1, int co1, const float* f2, int cs2, int co2, int swap2, int N,

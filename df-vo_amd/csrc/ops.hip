@@ -197,6 +197,7 @@ int launch_warp(const float* src, int scs, int sco, int swap, const float* flow,
                 int N, int H, int W, int C, const float* lin_x, const float* lin_y, float* dst, int dcs, int dco,
                 int append_flow, hipStream_t s, int step) {
     DFVO_ARG_CHECK(C % 4 == 0 && scs % 4 == 0 && sco % 4 == 0 && dcs % 4 == 0 && dco % 4 == 0 && step >= 1, "warp: alignment");
+    DFVO_ARG_CHECK(H >= 2 && W >= 2, "warp: a map one pixel wide or high has no (size - 1) / 2 grid");
     const long long total = (long long)N * cdiv(H, step) * cdiv(W, step) * (C / 4 + (append_flow ? 1 : 0));
     hipLaunchKernelGGL(k_warp, dim3(grid1d(total, 256)), dim3(256), 0, s, src, scs, sco, swap, flow, fcs, fco, mult,
                        N, H, W, C / 4, lin_x, lin_y, dst, dcs, dco, append_flow, step);
@@ -303,6 +304,7 @@ __global__ void k_reg_prep(const float* __restrict__ img, const float* __restric
 
 int launch_reg_prep(const float* img, const float* flow, int fcs, int fco, float mult, const float* mean, int N,
                     int H, int W, const float* lin_x, const float* lin_y, float* dst, hipStream_t s) {
+    DFVO_ARG_CHECK(H >= 2 && W >= 2, "reg_prep: a map one pixel wide or high has no (size - 1) / 2 grid");
     hipLaunchKernelGGL(k_reg_prep, dim3(grid1d((long long)N * H * W, 256)), dim3(256), 0, s, img, flow, fcs, fco,
                        mult, mean, N, H, W, lin_x, lin_y, dst);
     DFVO_HIP_CHECK(hipGetLastError());
@@ -445,18 +447,30 @@ __global__ __launch_bounds__(256) void k_deconv_dw4_blk(const float* __restrict_
         }
 }
 
+bool deconv_blk_enabled() {
+    static const bool blk = env_flag("DFVO_DECONV_BLK", true);
+    return blk;
+}
+
+int deconv_dw_variant(int scs, int sco, int dcs, int dco, int C, bool blk) {
+    const int C4 = (C + 3) >> 2;
+    if (((scs | sco | dcs | dco) & 3) == 0 && C4 * 4 <= scs - sco && C4 * 4 <= dcs - dco)  // 16-byte views with room for the quad
+        return blk && C4 * 4 * 16 * sizeof(float) <= 32 * 1024 ? DECONV_BLK : DECONV_QUAD;
+    return DECONV_SCALAR;
+}
+
 int launch_deconv_dw(const float* src, int scs, int sco, int N, int H, int W, int C, const float* w, float* dst,
                      int dcs, int dco, hipStream_t s) {
     const int C4 = (C + 3) >> 2;
-    if (((scs | sco | dcs | dco) & 3) == 0 && C4 * 4 <= scs - sco && C4 * 4 <= dcs - dco) {  // 16-byte views with room for the quad
-        static const bool blk = env_flag("DFVO_DECONV_BLK", true);
-        if (blk && C4 * 4 * 16 * sizeof(float) <= 32 * 1024) {
-            const long long totalb = (long long)N * H * W * C4;
-            hipLaunchKernelGGL(k_deconv_dw4_blk, dim3(grid1d(totalb, 256)), dim3(256), (size_t)C4 * 4 * 16 * sizeof(float), s, src, scs, sco,
-                               N, H, W, C, w, dst, dcs, dco);
-            DFVO_HIP_CHECK(hipGetLastError());
-            return DFVO_OK;
-        }
+    const int variant = deconv_dw_variant(scs, sco, dcs, dco, C, deconv_blk_enabled());
+    if (variant == DECONV_BLK) {
+        const long long totalb = (long long)N * H * W * C4;
+        hipLaunchKernelGGL(k_deconv_dw4_blk, dim3(grid1d(totalb, 256)), dim3(256), (size_t)C4 * 4 * 16 * sizeof(float), s, src, scs, sco,
+                           N, H, W, C, w, dst, dcs, dco);
+        DFVO_HIP_CHECK(hipGetLastError());
+        return DFVO_OK;
+    }
+    if (variant == DECONV_QUAD) {
         const long long total4 = (long long)N * 2 * H * 2 * W * C4;
         hipLaunchKernelGGL(k_deconv_dw4, dim3(grid1d(total4, 256)), dim3(256), 0, s, src, scs, sco, N, H, W, C, w, dst, dcs, dco);
         DFVO_HIP_CHECK(hipGetLastError());
@@ -651,15 +665,32 @@ __global__ __launch_bounds__(256) void k_correlation_rt(const float* __restrict_
     }
 }
 
+bool correlation_rt_enabled() {
+    static const bool rt = env_flag("DFVO_CORR_RT", true);
+    return rt;
+}
+
+int correlation_variant(int C, int cs1, int co1, int cs2, int co2, bool rt) {
+    if (!(C % 4 == 0 && cs1 % 4 == 0 && cs2 % 4 == 0 && co1 % 4 == 0 && co2 % 4 == 0)) return -1;
+    int K = 0, P = C + 1, TH = 8, TW = 8;
+    if (rt && C % 32 == 0 && C >= 32 && C <= 192 && C != 160) {  // k_correlation_rt<1, 2, 3, 4, 6>
+        K = C / 32;
+        P = C + 4;
+        if ((size_t)(TH * TW + (TH + 6) * (TW + 6)) * P * sizeof(float) > 150 * 1024) TH = 4;
+    } else {
+        if (C > 64) { TH = 4; TW = 8; }
+        if (C > 96) { TH = 4; TW = 4; }
+    }
+    if ((size_t)(TH * TW + (TH + 6) * (TW + 6)) * P * sizeof(float) > 160 * 1024) return -1;
+    return 100 * K + 10 * TH + TW;
+}
+
 template <int K32>
 static int launch_correlation_rt(const float* f1, int cs1, int co1, const float* f2, int cs2, int co2, int swap2, int N,
-                                 int H, int W, int stride, float* dst, int dcs, float slope, hipStream_t s) {
+                                 int H, int W, int stride, int TH, int TW, float* dst, int dcs, float slope, hipStream_t s) {
     constexpr int C = 32 * K32, P = C + 4;
     const int Ho = cdiv(H, stride), Wo = cdiv(W, stride);
-    int TH = 8, TW = 8;
-    if ((size_t)(TH * TW + (TH + 6) * (TW + 6)) * P * sizeof(float) > 150 * 1024) TH = 4;
     const size_t lds = (size_t)(TH * TW + (TH + 6) * (TW + 6)) * P * sizeof(float);
-    DFVO_ARG_CHECK(lds <= 160 * 1024, "correlation: channel count too large for the LDS tile");
     if (int rc_lds = ensure_dyn_lds((const void*)k_correlation_rt<K32>, lds)) return rc_lds;
     dim3 grid(cdiv(Wo, TW), cdiv(Ho, TH), N);
     hipLaunchKernelGGL(k_correlation_rt<K32>, grid, dim3(256), lds, s, f1, cs1, co1, f2, cs2, co2, swap2, N, H, W, stride, Ho,
@@ -672,23 +703,19 @@ int launch_correlation(const float* f1, int cs1, int co1, const float* f2, int c
                        int H, int W, int C, int stride, float* dst, int dcs, float slope, hipStream_t s) {
     DFVO_ARG_CHECK(C % 4 == 0 && cs1 % 4 == 0 && cs2 % 4 == 0 && co1 % 4 == 0 && co2 % 4 == 0,
                    "correlation: alignment");
-    static const bool rt = env_flag("DFVO_CORR_RT", true);
-    if (rt && C % 32 == 0 && C >= 32 && C <= 192) {
-        switch (C / 32) {
-            case 1: return launch_correlation_rt<1>(f1, cs1, co1, f2, cs2, co2, swap2, N, H, W, stride, dst, dcs, slope, s);
-            case 2: return launch_correlation_rt<2>(f1, cs1, co1, f2, cs2, co2, swap2, N, H, W, stride, dst, dcs, slope, s);
-            case 3: return launch_correlation_rt<3>(f1, cs1, co1, f2, cs2, co2, swap2, N, H, W, stride, dst, dcs, slope, s);
-            case 4: return launch_correlation_rt<4>(f1, cs1, co1, f2, cs2, co2, swap2, N, H, W, stride, dst, dcs, slope, s);
-            case 6: return launch_correlation_rt<6>(f1, cs1, co1, f2, cs2, co2, swap2, N, H, W, stride, dst, dcs, slope, s);
-            default: break;
-        }
+    const int variant = correlation_variant(C, cs1, co1, cs2, co2, correlation_rt_enabled());
+    DFVO_ARG_CHECK(variant >= 0, "correlation: channel count too large for the LDS tile");
+    const int TH = variant / 10 % 10, TW = variant % 10;
+    switch (variant / 100) {
+        case 1: return launch_correlation_rt<1>(f1, cs1, co1, f2, cs2, co2, swap2, N, H, W, stride, TH, TW, dst, dcs, slope, s);
+        case 2: return launch_correlation_rt<2>(f1, cs1, co1, f2, cs2, co2, swap2, N, H, W, stride, TH, TW, dst, dcs, slope, s);
+        case 3: return launch_correlation_rt<3>(f1, cs1, co1, f2, cs2, co2, swap2, N, H, W, stride, TH, TW, dst, dcs, slope, s);
+        case 4: return launch_correlation_rt<4>(f1, cs1, co1, f2, cs2, co2, swap2, N, H, W, stride, TH, TW, dst, dcs, slope, s);
+        case 6: return launch_correlation_rt<6>(f1, cs1, co1, f2, cs2, co2, swap2, N, H, W, stride, TH, TW, dst, dcs, slope, s);
+        default: break;
     }
     const int Ho = cdiv(H, stride), Wo = cdiv(W, stride);
-    int TH = 8, TW = 8;
-    if (C > 64) { TH = 4; TW = 8; }
-    if (C > 96) { TH = 4; TW = 4; }
     const size_t lds = (size_t)(TH * TW + (TH + 6) * (TW + 6)) * (C + 1) * sizeof(float);
-    DFVO_ARG_CHECK(lds <= 160 * 1024, "correlation: channel count too large for the LDS tile");
     if (int rc_lds = ensure_dyn_lds((const void*)k_correlation, lds)) return rc_lds;
     dim3 grid(cdiv(Wo, TW), cdiv(Ho, TH), N);
     hipLaunchKernelGGL(k_correlation, grid, dim3(256), lds, s, f1, cs1, co1, f2, cs2, co2, swap2, N, H, W, C, stride,
@@ -787,17 +814,27 @@ __global__ __launch_bounds__(256) void k_reg_head_v(const float* __restrict__ di
 // (Round 6: the distance vectors of a workgroup's 256 consecutive pixels staged through LDS -- one contiguous, fully coalesced
 // run instead of 16-byte loads at a 208-byte lane stride -- measured SLOWER: 49.1 vs 45.9 us on the level-2 map, 11.4 vs 10.1
 // on level 3, profiles/r6i_mirrors_kernel_stats_lds{0,1}.csv.  The kernel is not bound by its load pattern; removed.)
+bool reg_head_vec_enabled() {
+    static const bool vec = env_flag("DFVO_REG_HEAD_V", true);
+    return vec;
+}
+
+int reg_head_variant(const float* dist, int dist_cs, int k, const float* flow, int fcs, int fco, const float* dst, int dcs, int dco,
+                     bool vec) {
+    const bool aligned = dist_cs % 4 == 0 && ((uintptr_t)dist & 15) == 0 && dist_cs >= ((k * k + 3) & ~3) && fcs % 2 == 0 &&
+                         fco % 2 == 0 && ((uintptr_t)flow & 7) == 0 && dcs % 2 == 0 && dco % 2 == 0 && ((uintptr_t)dst & 7) == 0;
+    return vec && aligned && (k == 3 || k == 5 || k == 7) ? k : 0;
+}
+
 int launch_reg_head(const float* dist, int dist_cs, int k, const float* flow, int fcs, int fco, const float* wx,
                     float bx, const float* wy, float by, int N, int H, int W, float* dst, int dcs, int dco,
                     hipStream_t s) {
-    static const bool vec = env_flag("DFVO_REG_HEAD_V", true);
     const dim3 grid(grid1d((long long)N * H * W, 256));
-    const bool aligned = dist_cs % 4 == 0 && ((uintptr_t)dist & 15) == 0 && dist_cs >= ((k * k + 3) & ~3) && fcs % 2 == 0 &&
-                         fco % 2 == 0 && ((uintptr_t)flow & 7) == 0 && dcs % 2 == 0 && dco % 2 == 0 && ((uintptr_t)dst & 7) == 0;
-    if (vec && aligned && (k == 3 || k == 5 || k == 7)) {
-        if (k == 3)
+    const int variant = reg_head_variant(dist, dist_cs, k, flow, fcs, fco, dst, dcs, dco, reg_head_vec_enabled());
+    if (variant) {
+        if (variant == 3)
             hipLaunchKernelGGL(k_reg_head_v<3>, grid, dim3(256), 0, s, dist, dist_cs, flow, fcs, fco, wx, bx, wy, by, N, H, W, dst, dcs, dco);
-        else if (k == 5)
+        else if (variant == 5)
             hipLaunchKernelGGL(k_reg_head_v<5>, grid, dim3(256), 0, s, dist, dist_cs, flow, fcs, fco, wx, bx, wy, by, N, H, W, dst, dcs, dco);
         else
             hipLaunchKernelGGL(k_reg_head_v<7>, grid, dim3(256), 0, s, dist, dist_cs, flow, fcs, fco, wx, bx, wy, by, N, H, W, dst, dcs, dco);

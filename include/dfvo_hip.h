@@ -136,7 +136,9 @@ int dfvo_backward_warp(const float* d_src, const float* d_flow, float flow_mult,
  * tests.  NHWC float views (pointer, floats per pixel, channel offset); h_lin_x / h_lin_y: torch.linspace(-1,1,W/H) on the
  * HOST.  Each call returns after the launch has finished on `stream`.
  * dfvo_warp_view: Backward() of source sample (swap ? N-1-n : n) at (x, y) + flow * mult into dst channels [dco, dco + C);
- * append_flow: dst channels C, C+1 = the flow, C+2, C+3 = 0; step > 1: only the pixels y % step == 0, x % step == 0. */
+ * append_flow: dst channels C, C+1 = the flow, C+2, C+3 = 0; step > 1: only the pixels y % step == 0, x % step == 0.
+ * C, scs, sco, dcs and dco are multiples of 4.  dfvo_warp_view and dfvo_reg_prep refuse H < 2 or W < 2 with DFVO_ERR_ARG (and so
+ * do the launchers under them): the sampling grid divides by (W - 1) / 2 and (H - 1) / 2. */
 int dfvo_warp_view(const float* d_src, int scs, int sco, int swap, const float* d_flow, int fcs, int fco, float mult, int N,
                    int H, int W, int C, const float* h_lin_x, const float* h_lin_y, float* d_dst, int dcs, int dco,
                    int append_flow, int step, void* stream);
@@ -150,9 +152,23 @@ int dfvo_flow_mean(const float* d_flow, int fcs, int fco, int N, int HW, float* 
 int dfvo_reg_prep(const float* d_img, const float* d_flow, int fcs, int fco, float mult, const float* d_mean, int N, int H,
                   int W, const float* h_lin_x, const float* h_lin_y, float* d_dst, void* stream);
 /* Regularization output head, lite_flow_net.py:256-264: softmax of -dist^2 over the k*k taps, weighted with the zero-padded
- * k x k unfold of the flow and moduleScaleX / Y (h_wx, h_wy: k*k floats each) */
+ * k x k unfold of the flow and moduleScaleX / Y (h_wx, h_wy: k*k floats each); k odd, 1 .. 9 */
 int dfvo_reg_head(const float* d_dist, int dist_cs, int k, const float* d_flow, int fcs, int fco, const float* h_wx, float bx,
                   const float* h_wy, float by, int N, int H, int W, float* d_dst, int dcs, int dco, void* stream);
+/* Which kernel the three dispatching launchers run for given arguments: the launchers call the same pure functions
+ * (df-vo_amd/csrc/ops.h), with the same environment switches, read once per process.  Nothing is launched.
+ * dfvo_deconv_variant: dfvo_deconv_dw4x4s2(C, cs) -> 0 k_deconv_dw4_blk (cs a multiple of 4 with room for C's last quad, C <= 512,
+ *   DFVO_DECONV_BLK not 0), 1 k_deconv_dw4 (such a view otherwise), 2 k_deconv_dw (any other cs).  The two quad kernels write the
+ *   pad channels [C, round_up(C, 4)) of the destination as zeros; the scalar kernel writes channels [0, C) alone.
+ * dfvo_correlation_variant: 100 K + 10 TH + TW, K = C / 32 for k_correlation_rt<K> (C = 32, 64, 96, 128, 192 unless DFVO_CORR_RT=0)
+ *   and 0 for k_correlation, TH x TW the output tile; -1 where dfvo_correlation_view refuses (C or a view no multiple of 4, a tile
+ *   beyond 160 KB of LDS: C > 352).
+ * dfvo_reg_head_variant: k for k_reg_head_v<k> (k = 3, 5, 7; d_dist 16-byte aligned with dist_cs a multiple of 4 and at least
+ *   round_up(k * k, 4); flow and destination views 8-byte aligned; DFVO_REG_HEAD_V not 0), 0 for k_reg_head. */
+int dfvo_deconv_variant(int C, int cs);
+int dfvo_correlation_variant(int C, int cs1, int co1, int cs2, int co2);
+int dfvo_reg_head_variant(const float* d_dist, int dist_cs, int k, const float* d_flow, int fcs, int fco, const float* d_dst, int dcs,
+                          int dco);
 /* the net's output stage: level-2 flow x scale, bilinear (align_corners) to H x W, x (W/w, H/h) -> d_fwd / d_bwd [2,H,W]
  * (samples 0 / 1), d_diff [H,W] = forward-backward consistency (deep_flow.py:107-129,171-196) */
 int dfvo_flow_post(const float* d_netflow, int fcs, int fco, int h, int w, float scale, int H, int W, float* d_fwd,

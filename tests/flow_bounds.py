@@ -13,7 +13,10 @@ warp coordinate
     intermediates whose size in pixels is at most 2s + |f mult|: dx = 6u (s + |f mult|) (5u, rounded up for the
     second-order terms).
 resize / input coordinate
-    real = scale * o (align_corners) or 2 o + 0.5 (x2 down): dx = 2u (|real| + 1).
+    real = scale * o (align_corners) or 2 o + 0.5 (x2 down): dx = 2u (|real| + 1).  The general src_index (any size, either
+    align_corners setting: resize_bound) has the same two roundings -- the fp32 scale and the product, or the fp32 scale and
+    the rounding of the double scale (o + 0.5) - 0.5 to float -- so the same dx holds; past the last pixel the kernel
+    clamps where bilinear_bound pads with zeros, which only enlarges M, Lx and Ly there.
 consistency coordinate
     px = ((x + fx) / (W - 1) - 0.5) * 2, then (px + 1) (W - 1) / 2: five roundings of intermediates of at most
     |x + fx| + W pixels: dx = 6u (|x + fx| + W).
@@ -33,6 +36,8 @@ reg head
     rho_c = 1.01 u (|v_c| + |v_c - m|) + 4u (expf within two ulp); the error of m is a common factor that cancels.  The
     weighted mean y = (sum w_c e_c f_c + b) / sum e_c, accumulated in double, then moves by at most
     sum_c p_c rho_c |w_c f_c - y| (p_c = e_c / sum e), plus u |y| for the final rounding.
+    k_reg_head (any k, any view) runs the operations of k_reg_head_v<k> in the same order -- fp32 -(d d), fmaxf, expf of the
+    fp32 difference, the three sums in double, one rounding of the quotient -- so the same bound holds for it.
 flow post
     resize: rw (17u M + dx Lx + dy Ly) + 2u |out| on the x10 flow (the x10 is one more rounding per corner, rw = float(W / w)
     and the product one each); consistency: sqrt(sum_c (e_c + u |d_c|)^2) + 3u diff, e_c the bilinear bound of -bwd."""
@@ -94,6 +99,20 @@ def resize_half_bound(src):
     ho, wo = h // 2, w // 2
     ix = (2.0 * torch.arange(wo, dtype=torch.float64) + 0.5).view(1, 1, wo).expand(n, ho, wo)
     iy = (2.0 * torch.arange(ho, dtype=torch.float64) + 0.5).view(1, ho, 1).expand(n, ho, wo)
+    return 1.01 * bilinear_bound(src, ix, iy, 2 * U * (ix + 1), 2 * U * (iy + 1))
+
+
+def resize_bound(src, ho, wo, align_corners):
+    """launch_resize_bilinear of src [N,C,H,W] to ho x wo with the general src_index: dx = 2u (|real| + 1)"""
+    n, c, h, w = src.shape
+
+    def real(n_out, n_in):
+        o = torch.arange(n_out, dtype=torch.float64)
+        if align_corners:
+            return o * ((n_in - 1) / (n_out - 1) if n_out > 1 else 0.0)
+        return ((n_in / n_out) * (o + 0.5) - 0.5).clamp(min=0.0)
+    ix = real(wo, w).view(1, 1, wo).expand(n, ho, wo)
+    iy = real(ho, h).view(1, ho, 1).expand(n, ho, wo)
     return 1.01 * bilinear_bound(src, ix, iy, 2 * U * (ix + 1), 2 * U * (iy + 1))
 
 

@@ -152,8 +152,8 @@ def net_input(u8, th, tw, dtype=torch.float64):
     return F.interpolate(x, (th, tw), mode="bilinear", align_corners=True)
 
 
-def resize_ref(x, size):
-    return F.interpolate(x, size=size, mode="bilinear", align_corners=False)
+def resize_ref(x, size, align_corners=False):
+    return F.interpolate(x, size=size, mode="bilinear", align_corners=align_corners)
 
 
 def deconv_ref(x, w):
