@@ -7,13 +7,13 @@ struct TrackTrace {
     static double ms_since(Clock::time_point a) { return std::chrono::duration<double, std::milli>(Clock::now() - a).count(); }
     static TrackTrace& get() { static TrackTrace t; return t; }
     const bool on = getenv("DFVO_TRACK_TRACE") != nullptr;
-    double acc[2] = {0, 0}, dev[3] = {0, 0, 0};
-    int dev_n = 0, n = 0;
+    double acc[2] = {0, 0}, dev[3] = {0, 0, 0}, lead[3] = {0, 0, 0};
+    int dev_n = 0, lead_n = 0, n = 0;
 
-    // track_begin: the events the chain's launchers record between its segments
+    // track_begin: the events the chain's launchers record between its segments, and the homography half on its stream
     int begin(TrackerBuffers& tb) const {
         if (on && !tb.ev_t[0])
-            for (int i = 0; i < 4; i++) DFVO_HIP_CHECK(hipEventCreate(&tb.ev_t[i]));
+            for (int i = 0; i < TrackerBuffers::N_EV_T; i++) DFVO_HIP_CHECK(hipEventCreate(&tb.ev_t[i]));
         return DFVO_OK;
     }
     // track_end of a pair with n_kp keypoints that took the E path: entered at t0, waited wait_ms for the chain
@@ -29,6 +29,19 @@ struct TrackTrace {
                     dev[0] / 20, dev[1] / 20, dev[2] / 20);
             dev[0] = dev[1] = dev[2] = 0;
             dev_n = 0;
+        }
+        // how long before the chain's marks the run-ahead half had passed its own (negative: the chain waited for it)
+        float l[3] = {0, 0, 0};
+        const int from[3] = {4, 5, 5}, to[3] = {0, 0, 1};
+        bool okl = ok && tb.ev_t_half;
+        for (int i = 0; i < 3 && okl; i++) okl = hipEventElapsedTime(&l[i], tb.ev_t[from[i]], tb.ev_t[to[i]]) == hipSuccess;
+        for (int i = 0; i < 3 && okl; i++) lead[i] += l[i];
+        lead_n += okl;
+        if (lead_n == 20) {
+            fprintf(stderr, "run-ahead half, ms ahead: ev_start before the shuffles %.3f | ev_h before the shuffles %.3f | ev_h before the "
+                            "end of the five-point batch %.3f\n", lead[0] / 20, lead[1] / 20, lead[2] / 20);
+            lead[0] = lead[1] = lead[2] = 0;
+            lead_n = 0;
         }
         acc[0] += wait_ms;
         acc[1] += ms_since(t0);
@@ -222,7 +235,8 @@ int dfvo_pipeline_track_begin(dfvo_pipeline* p, int slot, const float* d_flow_ov
         DFVO_HIP_CHECK(hipEventRecord(sl.e_res, s));
         return begun(CHAIN_ENQUEUED);
     }
-    // waits for tb.ev_h (the prefetched half) on the device
+    // the shuffles and the five-point batch start behind tb.ev_start; s waits for tb.ev_h (the prefetched half) on the device
+    // only in front of the validity bookkeeping, the first kernel that reads the homography
     DFVO_TRY(enqueue_pose_e_part(tb, n, p->refine.e_enable ? p->pose_cfg1 : p->pose_cfg, s, p->d_T21, iterative ? p->d_E_pose.p : nullptr));
     DFVO_HIP_CHECK(hipStreamWaitEvent(s, sl.e_depth, 0));
     const double* depth = d_depth_override ? d_depth_override : sl.proc_depth.p;

@@ -212,7 +212,7 @@ void TrackerBuffers::release() {
     if (ev_start) (void)hipEventDestroy(ev_start);
     if (ev_h) (void)hipEventDestroy(ev_h);
     ev_fork = ev_start = ev_h = nullptr;
-    for (int i = 0; i < 4; i++) {
+    for (int i = 0; i < N_EV_T; i++) {
         if (ev_t[i]) (void)hipEventDestroy(ev_t[i]);
         ev_t[i] = nullptr;
     }

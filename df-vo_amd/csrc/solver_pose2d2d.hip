@@ -343,13 +343,19 @@ int enqueue_pose_h_part(TrackerBuffers& tb, int n_bound, const PoseConfig& cfg, 
         tb.e_pre_iters = cfg.max_iters;
     }
     DFVO_HIP_CHECK(hipEventRecord(tb.ev_start, sh));
+    tb.ev_t_half = tb.ev_t[4] != nullptr;
+    if (tb.ev_t_half) DFVO_HIP_CHECK(hipEventRecord(tb.ev_t[4], sh));
     if (tb.mark(0, sh) != DFVO_OK) return DFVO_ERR_HIP;
+    auto done = [&]() -> int {
+        DFVO_HIP_CHECK(hipEventRecord(tb.ev_h, sh));
+        if (tb.ev_t_half) DFVO_HIP_CHECK(hipEventRecord(tb.ev_t[5], sh));
+        DFVO_HIP_CHECK(hipGetLastError());
+        return DFVO_OK;
+    };
     if (cfg.validity == 1) {  // "flow": no homography; the mean displacement decides whether the pair is tracked
         hipLaunchKernelGGL(k_flow_gate, dim3(1), dim3(256), 0, sh, tb.kp_info, tb.kp_ref, tb.kp_cur, cfg.validity_thre,
                            tb.pa, tb.small + SMALL_H_GRIC, tb.kp_total + KPT_FLOW_GATE);
-        DFVO_HIP_CHECK(hipEventRecord(tb.ev_h, sh));
-        DFVO_HIP_CHECK(hipGetLastError());
-        return DFVO_OK;
+        return done();
     }
     // ---- homography + GRIC-H (kp_cur -> kp_ref); with 10 or fewer keypoints the result is never consumed
     // (E_tracker.py:196) and with fewer than 5 the chain marks itself "no model"
@@ -365,13 +371,16 @@ int enqueue_pose_h_part(TrackerBuffers& tb, int n_bound, const PoseConfig& cfg, 
                            tb.kp_ref, 0, 0.8, 8, 2, tb.small + SMALL_H_GRIC);
         if (tb.mark(2, sh) != DFVO_OK) return DFVO_ERR_HIP;
     }
-    DFVO_HIP_CHECK(hipEventRecord(tb.ev_h, sh));
-    DFVO_HIP_CHECK(hipGetLastError());
-    return DFVO_OK;
+    return done();
 }
 
 // RNG-consuming half: `repeat` x (shuffle, findEssentialMat, GRIC-E) as one batch on tb.s_rep[0] (after tb.ev_start),
 // then on s (after tb.ev_h): validity bookkeeping, recoverPose, pose / T21.  n_host = the keypoint count.
+// s waits for tb.ev_h where the homography half is first read -- in front of k_rep_update_* (ws_h.state, SMALL_H_GRIC) --
+// and not at the top: tb.s_rep[0] may be s itself (the fused pipeline's lane layout), and the batch reads nothing of that
+// half (keypoints, count and the prefetched subsets are complete at tb.ev_start; pa / pb / perm / ws_rep are its own).
+// validity "flow" is the exception: the gate (k_flow_gate, scratch tb.pa) feeds the shuffles, so the batch waits for
+// tb.ev_h itself.  A pair with too few keypoints for the batch still leaves s behind tb.ev_h.
 // one lane: the accepted pose as a 4 x 4 (E_pose.pose of dfvo.py:172), for the iterative scale loop
 __global__ void k_pose_matrix(const PoseState* __restrict__ ps, double* __restrict__ E) {
     if (threadIdx.x != 0) return;
@@ -386,7 +395,6 @@ __global__ void k_pose_matrix(const PoseState* __restrict__ ps, double* __restri
 int enqueue_pose_e_part(TrackerBuffers& tb, int n_host, const PoseConfig& cfg, hipStream_t s, double* d_T21, double* d_E_pose) {
     DFVO_ARG_CHECK(n_host >= 0 && n_host <= tb.kp_cap, "compute_pose_2d2d: keypoint capacity");
     DFVO_ARG_CHECK(cfg.repeat >= 1 && cfg.repeat <= MAX_REP, "compute_pose_2d2d: repeat out of range");
-    DFVO_HIP_CHECK(hipStreamWaitEvent(s, tb.ev_h, 0));
     const bool by_flow = cfg.validity == 1, by_ratio = cfg.validity == 2;
     // GRIC: only when more than 10 keypoints (E_tracker.py:196); flow / homo_ratio: whenever the five-point solver has
     // its 5 points
@@ -435,6 +443,7 @@ int enqueue_pose_e_part(TrackerBuffers& tb, int n_host, const PoseConfig& cfg, h
         if (!by_flow && !by_ratio && tb.mark(5, sr) != DFVO_OK) return DFVO_ERR_HIP;
         DFVO_HIP_CHECK(hipEventRecord(tb.ev_rep[0], sr));
         DFVO_HIP_CHECK(hipStreamWaitEvent(s, tb.ev_rep[0], 0));
+        DFVO_HIP_CHECK(hipStreamWaitEvent(s, tb.ev_h, 0));  // the homography half: read from here on
         {
             RepBatch RB;
             for (int rep = 0; rep < MAX_REP; ++rep) {
@@ -463,6 +472,8 @@ int enqueue_pose_e_part(TrackerBuffers& tb, int n_host, const PoseConfig& cfg, h
         if (d_E_pose) hipLaunchKernelGGL(k_pose_matrix, dim3(1), dim3(64), 0, s, (const PoseState*)tb.pose.p, d_E_pose);
         if (tb.ev_t[2]) DFVO_HIP_CHECK(hipEventRecord(tb.ev_t[2], s));
         if (tb.mark(7, s) != DFVO_OK) return DFVO_ERR_HIP;
+    } else {
+        DFVO_HIP_CHECK(hipStreamWaitEvent(s, tb.ev_h, 0));  // no batch: whatever follows on s still comes behind that half
     }
     DFVO_HIP_CHECK(hipGetLastError());
     return DFVO_OK;

@@ -124,6 +124,8 @@ struct StreamPlan {
 //          dealt its stream onto (creation order on four queues: 249 frames/s against 305, profiles/lanes_ab.txt).
 //          Measured against it: the pre-part of pair j right behind flow(j) on the flow lane of its parity, where it waits
 //          for nothing -- 287-294 frames/s: 1.4 ms of one-workgroup kernels per pair keep that lane's net from the machine.
+//          Its keypoint stage and start group alone there (0.2 ms), the homography part left on the depth lane: no gain over
+//          the lanes as they are -- the homography part then ends behind the five-point batch (profiles/lanes_chain_ab.txt).
 // auto: lanes with 4 .. 7 queues, wide with 8 or more (8 streams), creation order below four.
 static inline StreamPlan plan_stream_layout(int ngroups, int nqueues, int choice) {
     StreamPlan p;

@@ -131,8 +131,11 @@ struct TrackerBuffers {
     hipEvent_t ev_rep[MAX_REP] = {};
     hipEvent_t ev_fork = nullptr, ev_start = nullptr, ev_h = nullptr;
     // DFVO_TRACK_TRACE: device-side timestamps of the RNG-ordered chain (start of the shuffles, end of the five-point batch,
-    // end of recoverPose, end of the scale stage); null unless tracing
-    hipEvent_t ev_t[4] = {nullptr, nullptr, nullptr, nullptr};
+    // end of recoverPose, end of the scale stage), and of the homography half on its stream ([4] beside ev_start, [5] beside
+    // ev_h; ev_t_half: recorded for the pair at hand); null unless tracing
+    static constexpr int N_EV_T = 6;
+    hipEvent_t ev_t[N_EV_T] = {};
+    bool ev_t_half = false;
     // Stage timestamps for the reference's Timer sub-keys (E_tracker.py:197-296,597-638), created on demand by
     // enable_stage_timing() (the drop-in mirrors' tracker; the fused pipeline leaves them null).  Marks: 0 start of the
     // homography part | 1 findHomography done | 2 GRIC-H done | 3 first shuffle | 4 five-point batch done | 5 GRIC-E done |
